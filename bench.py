@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- CsrMV throughput of the MI355X-native merge-based SpMV.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: under torch.distributed.run, or plainly -- self_launch)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--extras]]
+                                                           (N > 1: under torch.distributed.run, or plainly -- self_launch)
 
 A "step" is one y = A*x through the C ABI (include/mspmv.h); inputs are resident in HBM before timing.
 
@@ -10,25 +11,35 @@ N = 1: BASELINE.json config 2 -- fp32, 3 125 000^2, 32 nnz/row = 100 000 000 nnz
 N > 1: the same matrix family, WEAK scaling -- N x 3 125 000 rows over the same 3 125 000 columns, cut by merge-path diagonals into N
        swaths (mspmv_mg_partition: every GPU holds what the N = 1 line's GPU holds), one rank per GPU, ONE RCCL all-gather of the N
        boundary-row carries per step below the C ABI: the per-N values of a scaling series are about one workload.
-       Then, as a second leg in the same job (`c5_strong`; --no-c5-leg skips it), BASELINE.json config 5 -- fp64 R-MAT scale 26,
-       2 000 000 000 edges, ONE matrix whatever N, strong scaling.  `--workload c5` makes config 5 the headline instead; rank 0 then also runs that whole
-       matrix alone (`single_gpu_same_workload`; --no-single-gpu-leg skips it; --c5-single-gpu-leg adds it to the default run's leg).
+       With --full, as a second leg in the same job (`c5_strong`; --no-c5-leg skips it), BASELINE.json config 5 -- fp64 R-MAT scale 26,
+       2 000 000 000 edges, ONE matrix whatever N, strong scaling.  `--workload c5` makes config 5 the headline instead; with --full rank 0
+       then also runs that whole matrix alone (`single_gpu_same_workload`; --no-single-gpu-leg skips it; --c5-single-gpu-leg adds it to
+       the default run's leg).
        `--preflight`: communicator, one all-gather, one step, exit (< 10 s; a failure names the rank).
 
+A plain run is lean: it builds the inputs, warms up W steps, times K steps, writes y of the last timed step if --dump-outputs is
+given (DIR/y.npy, or DIR/y_rank<r>.npy per rank when N > 1; a fixed, seeded sample of rows -- DIR/y_rows.npy -- when y exceeds
+DUMP_BYTES) and prints the line.  The inputs are generated from fixed seeds, so two builds given the same arguments compute on
+identical inputs and their dumps can be compared output for output.
+
 The LAST stdout line is ONE JSON object under 4 KB, numbers only (what the reference prints is one perf line, gpu_spmv.cu:459-471):
-  value        2 * nnz_total / t  (GFLOP/s, whole job; gpu_spmv.cu:451-465)
+  value        2 * nnz_total / t  (GFLOP/s, whole job; gpu_spmv.cu:451-465); ms_per_step = t / K, t the wall time of the K timed steps
+--full adds what takes runs or checks of its own:
   roofline     algorithmic bytes of one tile-kernel launch (every array once) / its average duration from hipEvents on
-               the launch stream, read against the 8 TB/s HBM3E spec peak (`frac`); arrays that fit the 256 MB Infinity Cache carry `frac_ic`
-               as context (against a bare read stream over a buffer of that size measured in this run); `traffic` = L2<->fabric bytes per launch
-               (FETCH_SIZE x 2 + WRITE_SIZE, the guide's gfx950 correction; Infinity-Cache hits included) -- replayed from the
-               committed rocprofv3 --pmc passes of the same workload (`traffic_src` names the file), measured live with --full
+               the launch stream (K more steps), read against the 8 TB/s HBM3E spec peak (`frac`); arrays that fit the 256 MB Infinity
+               Cache carry `frac_ic` as context (against a bare read stream over a buffer of that size measured in this run); `traffic` =
+               L2<->fabric bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, the guide's gfx950 correction; Infinity-Cache hits included) --
+               replayed from the committed rocprofv3 --pmc passes of the same workload (`traffic_src` names the file), measured live
+               with --extras
+  sampled_worst_ratio  the untimed correctness witness (sampled_check) of the headline's y
   cpu_baseline the product's OpenMP merge-path kernel (host/merge_csrmv.hpp, what cpu_spmv runs; bit for bit the oracle's,
                tests/test_cpu_product_parity.py) on the same matrix on this box's host cores: bounded sample
   configs      one compact object per remaining single-GPU configuration of BASELINE.json (+ the circuit5M-shaped matrix of the
                reference's one published number); `worst` = sampled_check's worst |y - g| / bound (< 1 passes)
+  N > 1        per-rank kernel and exchange times, the config-5 leg, rank 0's single-GPU run of the same matrix
 Everything longer -- notes, sources, per-run CPU variants, vendor column, plans -- goes to the side file named in `detail`
-(default gpurun_out/bench_detail.json) and, with --full, includes live counters, rocSPARSE, the prepared plans and config 5 at G = 1
-(tools/bench_full.py)."""
+(default bench_out/bench_detail.json, written by --full runs; --detail or $MSPMV_BENCH_DETAIL names another, '' none).  --extras (implies --full)
+adds the legs that take minutes: live counters, rocSPARSE, the prepared plans and config 5 at G = 1 (tools/bench_full.py)."""
 import argparse
 import ctypes
 import json
@@ -48,6 +59,9 @@ C2_ROWS_PER_GPU, C2_NPR = 3_125_000, 32
 REFERENCE_PUBLISHED_PCT = 62.96        # circuit5M fp64 on a K40: 181.6 effective GB/s of 288.4 (README.md:116,137-138)
 REAL_FILES = {"c3_web": "webbase-1M.mtx", "c3_orkut": "com-Orkut.mtx", "circuit": "circuit5M.mtx"}      # SuiteSparse names (ufl_matrices.txt)
 STANDIN_MARK = "STAND-IN written by tools/make_standin_mtx.py"
+DUMP_BYTES = 48 << 20                  # --dump-outputs writes at most this many bytes; beyond it, a seeded sample of rows
+DUMP_SEED = 0x5EED0D0
+DEFAULT_DETAIL = os.path.join(ROOT, "bench_out", "bench_detail.json")
 
 
 def algorithmic_bytes(rows, cols, nnz, vb):
@@ -141,6 +155,24 @@ def cpu_baseline(A, x, label, budget_s=12.0, max_iters=200):
             "variant": best["variant"], "runs": runs, "hardware_threads": int(H.mspmv_host_hardware_threads()), "cpu_quota": quota}
 
 
+def dump_outputs(directory, name, y, budget=DUMP_BYTES):
+    """--dump-outputs: `y`, what a caller of the timed path receives, as DIR/<name>.npy in its own precision (float32 / float64).
+    A y of more than `budget` bytes is replaced by a fixed, seeded sample of its rows, their numbers in DIR/<name>_rows.npy (float64,
+    exact); the sample depends on the length of y alone, so two builds given the same arguments write the same rows."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    n, item = y.numel(), y.element_size()
+    if n * item > budget:
+        rows = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, budget // (item + 8)))
+        y = y[torch.as_tensor(rows, device=y.device)]
+        np.save(os.path.join(directory, f"{name}_rows.npy"), rows.astype(np.float64))
+    a = y.detach().cpu().numpy()
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def time_stateless(M, torch, A, x, steps, warmup):
     """(ms per SpMV by the wall clock around `steps` back-to-back calls, per-kernel averages from hipEvents over `steps` more)"""
     ws = M.CsrMVWorkspace(A.rows, A.nnz, A.values.dtype, device=A.values.device)
@@ -194,7 +226,7 @@ def config_specs(torch, G, dev, steps):
          lambda: (G.degenerate_csr(dtype=f32, device=dev, ones=False), G.SEED_C4 + 2)),
         ("dense32", "dense32", "the reference's streaming input --dense=32 --size=100000000 (gpu_spmv.cu:645-650), fp32", f32, steps,
          lambda: (G.dense_csr(C2_ROWS_PER_GPU, C2_NPR, dtype=f32, device=dev, ones=False), G.SEED_C2 + 2)),
-        ("C5 G=1", "c5", "BASELINE config 5 on ONE GPU: fp64 R-MAT scale 26, 2 000 000 000 edges (--full only)", f64, 5,
+        ("C5 G=1", "c5", "BASELINE config 5 on ONE GPU: fp64 R-MAT scale 26, 2 000 000 000 edges (--extras only)", f64, 5,
          lambda: (G.rmat_csr(26, 2_000_000_000, dtype=f64, device=dev, seed=G.SEED_C5), G.SEED_C5 + 2)),
     ]
 
@@ -260,7 +292,7 @@ def roofline_record(M, A, cols, prof, ms, ws, workload_label, dtype_name):
 def config_records(M, torch, G, dev, steps, warmup, budget_s, mtx_dir=None, full=None):
     """The `configs` array (full form): every single-GPU configuration of BASELINE.json that the headline does not cover, through
     the same stateless call.  Generation is on the GPU and not timed; a configuration that would start after `budget_s` is
-    reported as skipped.  `full` (tools/bench_full.py, --full) adds live counters, the vendor column, the plans and config 5."""
+    reported as skipped.  `full` (tools/bench_full.py, --extras) adds live counters, the vendor column, the plans and config 5."""
     out = []
     t_start = time.perf_counter()
     for name, label, desc, tdt, k, make in config_specs(torch, G, dev, steps):
@@ -339,8 +371,9 @@ def compact_line(detail, detail_path=None):
     line = {k: detail.get(k) for k in keep}
     cfg = detail.get("config", {})
     line["config"] = {"workload": str(cfg.get("workload", ""))[:160], "tile": cfg.get("tile"), "partition": str(cfg.get("partition", ""))[:120]}
-    r = detail.get("roofline", {})
-    line["roofline"] = {k: r[k] for k in _ROOF_KEYS if k in r}
+    r = detail.get("roofline")
+    if r:
+        line["roofline"] = {k: r[k] for k in _ROOF_KEYS if k in r}
     cb = detail.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = ({"error": str(cb["error"])[:80]} if "error" in cb else
@@ -519,19 +552,21 @@ def preflight(torch, dist, MG, rank, world, local_rank, dev, backend, one_device
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS), help="default: c2 (N > 1: weak scaling, the same per-GPU matrix, then config 5 as a second leg); c5 = one R-MAT matrix cut N ways, strong scaling")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed steps before them")
+    ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS), help="default: c2 (N > 1: weak scaling, the same per-GPU matrix, then with --full config 5 as a second leg); c5 = one R-MAT matrix cut N ways, strong scaling")
     ap.add_argument("--dtype", default=None, choices=["f32", "f64"])
     ap.add_argument("--c5-scale", type=int, default=26)
     ap.add_argument("--c5-edges", type=int, default=2_000_000_000)
-    ap.add_argument("--full", action="store_true", help="N = 1: add live rocprofv3 --pmc traffic, the rocSPARSE column, the prepared plans and config 5 at G = 1 (minutes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the `configs` sub-records")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write y of the last timed step to DIR/y.npy (N > 1: DIR/y_rank<r>.npy; a seeded sample beyond DUMP_BYTES)")
+    ap.add_argument("--full", action="store_true", help="add what the headline does not need: roofline (an event-timed pass), sampled check, cpu_baseline, `configs`; N > 1: per-rank times, the config-5 leg")
+    ap.add_argument("--extras", action="store_true", help="implies --full; N = 1: add live rocprofv3 --pmc traffic, the rocSPARSE column, the prepared plans and config 5 at G = 1 (minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`")
+    ap.add_argument("--no-configs", action="store_true", help="--full, N = 1: skip the `configs` sub-records")
     ap.add_argument("--configs-budget", type=float, default=60.0, help="seconds the `configs` leg may take before it stops starting new ones")
     ap.add_argument("--mtx-dir", default=os.environ.get("MSPMV_C3_DIR"),
                     help="N = 1: a directory that may hold webbase-1M.mtx, com-Orkut.mtx, circuit5M.mtx (default: $MSPMV_C3_DIR); a file found replaces the generated stand-in")
-    ap.add_argument("--detail", default=os.environ.get("MSPMV_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json")),
+    ap.add_argument("--detail", default=os.environ.get("MSPMV_BENCH_DETAIL"),
                     help="side file for everything that is not in the line ('' = none)")
     ap.add_argument("--no-c5-leg", action="store_true", help="N > 1, default workload: skip the config-5 leg (one R-MAT matrix cut N ways, strong scaling) after the headline")
     ap.add_argument("--c5-single-gpu-leg", action="store_true", help="N > 1, default workload: after the config-5 leg rank 0 also runs the WHOLE R-MAT matrix alone (another ~80 s)")
@@ -540,6 +575,9 @@ def main():
     ap.add_argument("--preflight", action="store_true", help="N > 1: communicator init, one all-gather, one step; exits in seconds naming a failing rank")
     ap.add_argument("--dist-timeout", type=int, default=900, help="N > 1: seconds a collective may block before the job aborts")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    args.full = args.full or args.extras
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
 
@@ -576,7 +614,7 @@ def main():
             dist.init_process_group("nccl", device_id=dev, timeout=tmo)          # "nccl" is RCCL on ROCm
         else:
             dist.init_process_group(backend, timeout=tmo)
-    detail_path = args.detail or None
+    detail_path = (args.detail if args.detail is not None else DEFAULT_DETAIL if args.full else None) or None
 
     if args.preflight:
         if not mg:
@@ -589,7 +627,7 @@ def main():
         dist.barrier(); dist.destroy_process_group()
         raise SystemExit(0 if res["ok"] else 3)
 
-    def measure(workload, steps, warmup, single_leg=True):
+    def measure(workload, steps, warmup, single_leg=True, dump_dir=None):
         """One workload through the whole protocol (every rank calls it); rank 0 gets the record, the others None."""
         dtype_name = args.dtype or WORKLOADS[workload]
         tdt = torch.float32 if dtype_name == "f32" else torch.float64
@@ -638,6 +676,9 @@ def main():
 
             def op():
                 M.csrmv(A.values, A.row_offsets, A.column_indices, x, y=y, num_cols=cols, workspace=ws)
+
+            def last_y():
+                return y
 
             def op_sync():
                 torch.cuda.synchronize()
@@ -708,6 +749,9 @@ def main():
 
                 def op_sync():
                     plan.synchronize(); torch.cuda.synchronize()
+
+                def last_y():
+                    return plan.y(0)
             else:
                 sharded = MG.ShardedCsrMV(shard, group=None)
                 exchange = {"exchange": "python twin over " + backend, "carry_bytes_per_step": world * vb, "fallbacks": fallbacks}
@@ -717,6 +761,9 @@ def main():
 
                 def op_sync():
                     torch.cuda.synchronize()
+
+                def last_y():
+                    return sharded.y_local[: shard.owned_rows]
         else:
             local_rows, local_nnz = shard.local_rows, shard.local_nnz
             sharded = MG.ShardedCsrMV(shard, group=None)
@@ -727,6 +774,9 @@ def main():
 
             def op_sync():
                 torch.cuda.synchronize()
+
+            def last_y():
+                return sharded.y_local[: shard.owned_rows]
 
         def barrier():
             op_sync()
@@ -749,16 +799,23 @@ def main():
             elapsed = float(t.item())
         ms_per_step = elapsed * 1e3 / steps
 
-        # ---- per-kernel durations: the same K steps again with hipEvents on the launch stream
-        M.profile_begin(steps)
-        for _ in range(steps):
-            op()
-        op_sync()
-        prof = M.profile_end()
+        # ---- --dump-outputs: y of the last timed step (this rank's owned rows when N > 1)
+        if dump_dir:
+            op_sync()
+            dump_outputs(dump_dir, "y" if not mg else f"y_rank{rank}", last_y(), DUMP_BYTES // world)
 
-        # ---- N > 1 through the C operator: what the step's exchange alone takes (events around it, per rank)
+        # ---- --full: per-kernel durations, the same K steps again with hipEvents on the launch stream
+        prof = None
+        if args.full:
+            M.profile_begin(steps)
+            for _ in range(steps):
+                op()
+            op_sync()
+            prof = M.profile_end()
+
+        # ---- --full, N > 1 through the C operator: what the step's exchange alone takes (events around it, per rank)
         exchange_ms = None
-        if plan is not None:
+        if args.full and plan is not None:
             ex = []
             for _ in range(5):
                 op(); op_sync()
@@ -768,9 +825,9 @@ def main():
                     break
             exchange_ms = sum(ex) / len(ex) if ex else None
 
-        # ---- N > 1, c5: rank 0 runs the WHOLE matrix alone on its GPU in the same job -----------------------------------
+        # ---- --full, N > 1, c5: rank 0 runs the WHOLE matrix alone on its GPU in the same job ----------------------------
         single = None
-        if mg and workload == "c5" and single_leg and not args.no_single_gpu_leg:
+        if args.full and mg and workload == "c5" and single_leg and not args.no_single_gpu_leg:
             y0 = None
             if plan is not None:
                 if rank == 0:
@@ -809,7 +866,7 @@ def main():
 
         sys.stdout.flush()
         per_rank = None
-        if dist is not None:
+        if args.full and dist is not None:
             mine = torch.tensor([prof["search_ms"], prof["tile_ms"], prof["fixup_ms"], elapsed_local * 1e3 / steps, float(local_nnz),
                                  float("nan") if exchange_ms is None else exchange_ms], dtype=torch.float64, device=dev)
             allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -847,13 +904,13 @@ def main():
                                          f"merge-path diagonal split over {world} GPUs: {local_rows - 1} rows + {local_nnz} nnz on rank 0; one exchange of {world} carries per step")},
                 "effective_GBs_reference_formula": round(eff, 1), "effective_pct_of_peak": round(100.0 * eff / HBM_PEAK_GBS, 2),
             }
-            if not mg:
+            if args.full and not mg:
                 label = "c2_f32" if (workload, dtype_name) == ("c2", "f32") else workload
                 out["roofline"] = roofline_record(M, A, cols, prof, ms_per_step, ws, label, dtype_name)
                 chk = M.sampled_check(A, x, y)
                 out["sampled_worst_ratio"] = chk["worst_ratio"]
                 out["sampled_check"] = chk
-            else:
+            elif args.full:
                 b_alg = algorithmic_bytes(local_rows, cols, local_nnz, vb)
                 tile_s = prof["tile_ms"] * 1e-3
                 achieved = b_alg / tile_s / 1e9 if tile_s > 0 else 0.0
@@ -870,24 +927,25 @@ def main():
             if single is not None:
                 out["single_gpu_same_workload"] = single
             full = None
-            if args.full and not mg:
+            if args.extras and not mg:
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
                 import bench_full as full
                 full.extend_headline(out, M, torch, G, A, x, y, ws, workload, dtype_name, args)
-            if not mg and not args.no_cpu_baseline and A.nnz <= 400_000_000:
+            if args.full and not mg and not args.no_cpu_baseline and A.nnz <= 400_000_000:
                 out["cpu_baseline"] = cpu_baseline(A, x, "same " + workload.upper() + " matrix")
-            if not mg and workload == "c2" and dtype_name == "f32" and not args.no_configs:
+            if args.full and not mg and workload == "c2" and dtype_name == "f32" and not args.no_configs:
                 del A, ws, y
                 torch.cuda.empty_cache()
-                out["configs"] = config_records(M, torch, G, dev, min(steps, 50), warmup, args.configs_budget if not args.full else 600.0,
+                out["configs"] = config_records(M, torch, G, dev, min(steps, 50), warmup, args.configs_budget if not args.extras else 600.0,
                                                 mtx_dir=args.mtx_dir, full=full)
             return out
         return None
     # N > 1 (default): config 2's matrix family, weak scaling -- the SAME per-GPU matrix as the N = 1 line, so the per-N values
-    # of a scaling series are comparable -- and then BASELINE config 5 (one R-MAT matrix cut N ways, strong scaling) as a second leg
+    # of a scaling series are comparable -- and then, with --full, BASELINE config 5 (one R-MAT matrix cut N ways, strong scaling) as a
+    # second leg
     primary = args.workload or "c2"
-    out = measure(primary, args.steps, args.warmup)
-    if mg and args.workload is None and not args.no_c5_leg:
+    out = measure(primary, args.steps, args.warmup, dump_dir=args.dump_outputs)
+    if args.full and mg and args.workload is None and not args.no_c5_leg:
         c5 = None
         try:
             c5 = measure("c5", min(args.steps, 20), min(args.warmup, 3), single_leg=args.c5_single_gpu_leg)

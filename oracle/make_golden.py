@@ -46,6 +46,49 @@ def coords_for(row_offsets, rows, nnz):
     return [[int(t) for t in line.split()[1:]] for line in out.strip().splitlines()]
 
 
+def fresh_offsets(seed):
+    """The row offsets of tests/test_oracle_golden.py's fresh-input search test for `seed` (0 .. FRESH_SEEDS - 1): short rows, a few
+    long rows among empty ones, heavy-tailed lengths."""
+    import numpy as np
+    rng = np.random.default_rng(1000 + seed)
+    rows = int(rng.integers(1, 400))
+    kind = seed % 3
+    lens = (rng.integers(0, 6, rows) if kind == 0 else
+            np.where(rng.random(rows) < 0.03, rng.integers(50, 900, rows), 0) if kind == 1 else
+            np.minimum((rng.pareto(1.0, rows) * 2).astype(np.int64), 500))
+    off = np.zeros(rows + 1, np.int64); np.cumsum(lens, out=off[1:])
+    return off
+
+
+FRESH_SEEDS = 6
+
+
+def search_all_diagonals(off):
+    """The reference's MergePathSearch on every diagonal 0 .. rows+nnz+3 of `off`: int32 rows (d, x, y)."""
+    import numpy as np
+    rows, nnz = len(off) - 1, int(off[-1])
+    with tempfile.NamedTemporaryFile("w", suffix=".txt", delete=False) as f:
+        f.write(f"{rows} {nnz}\n" + " ".join(map(str, off)) + "\n")
+        name = f.name
+    try:
+        out = run(REF_SEARCH, name)
+    finally:
+        os.unlink(name)
+    return np.array([[int(t) for t in line.split()] for line in out.strip().splitlines()], np.int32)
+
+
+def write_fresh_search():
+    """tests/golden/ref_search_fresh.npz: offsets and every diagonal's coordinates for the fresh-input search test, so that it runs
+    where oracle/_ref/ref_search is not built."""
+    import numpy as np
+    arrays = {}
+    for seed in range(FRESH_SEEDS):
+        off = fresh_offsets(seed)
+        arrays[f"off{seed}"] = off.astype(np.int32)
+        arrays[f"coords{seed}"] = search_all_diagonals(off)
+    np.savez_compressed(os.path.join(GOLD, "ref_search_fresh.npz"), **arrays)
+
+
 def matrix_case(kind, args, label):
     case = {"label": label, "kind": kind, "args": args}
     for prec in ("f32", "f64"):
@@ -136,6 +179,7 @@ def main():
     }
     with open(os.path.join(GOLD, "kat_device_spmv.json"), "w") as f:
         json.dump(kat, f)
+    write_fresh_search()
     print("wrote", os.listdir(GOLD))
 
 

@@ -149,8 +149,40 @@ def test_nan_and_inf_never_reach_the_line():
 
 
 def test_replayed_traffic_finds_the_committed_counter_passes():
-    """roofline.traffic of the default run is replayed from profiles/*/pmc_latest.json (live with --full): the headline's and every config's label
+    """roofline.traffic of a --full run is replayed from profiles/*/pmc_latest.json (live with --extras): the headline's and every config's label
     must resolve to a committed pass of the same workload and precision."""
     for label, dt in (("c2_f32", "f32"), ("c2", "f64"), ("dense5", "f64"), ("circuit", "f64"), ("c3_web", "f64"), ("c3_orkut", "f64"), ("c4", "f32"), ("dense32", "f32"), ("c5", "f64")):
         tr, src = bench.replayed_traffic(label, dt)
         assert tr and tr > 0 and src.startswith("profiles/") and os.path.exists(os.path.join(ROOT, src)), (label, dt)
+
+
+def test_the_line_of_a_plain_run_holds_the_contract_keys_alone():
+    """A plain run measures the headline only: its line is the contract's keys and the workload, no empty `roofline`."""
+    import json
+    d = {k: v for k, v in _fake_detail(0).items() if k not in ("roofline", "sampled_worst_ratio", "sampled_check", "prepared_plan", "vendor",
+                                                              "cpu_baseline", "configs", "per_rank", "exchange", "single_gpu_same_workload")}
+    line = json.loads(bench.compact_line(bench._finite(d)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert line[k] == d[k], k
+    assert not {"roofline", "cpu_baseline", "configs", "detail"} & set(line)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_dump_outputs_writes_y_whole_or_a_seeded_sample(tmp_path, dtype):
+    """--dump-outputs: y in its own precision as <name>.npy; beyond the byte budget a fixed sample of rows, their numbers (float64,
+    exact) in <name>_rows.npy, the same rows for every y of that length, the whole dump within the budget."""
+    y = torch.arange(10_000, dtype=dtype) * 0.5 - 7.0
+    bench.dump_outputs(str(tmp_path / "whole"), "y", y, budget=1 << 20)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["y.npy"]
+    a = np.load(tmp_path / "whole" / "y.npy")
+    assert a.dtype == y.numpy().dtype and np.array_equal(a, y.numpy())
+    budget = 16_000
+    for sub, yy in (("s1", y), ("s2", -y)):
+        bench.dump_outputs(str(tmp_path / sub), "y", yy, budget=budget)
+        assert sorted(os.listdir(tmp_path / sub)) == ["y.npy", "y_rows.npy"]
+    rows = np.load(tmp_path / "s1" / "y_rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "s2" / "y_rows.npy"))
+    r = rows.astype(np.int64)
+    assert np.array_equal(r, rows) and (np.diff(r) > 0).all() and 0 <= r[0] and r[-1] < y.numel()
+    s = np.load(tmp_path / "s1" / "y.npy")
+    assert s.dtype == a.dtype and np.array_equal(s, a[r]) and s.nbytes + rows.nbytes <= budget

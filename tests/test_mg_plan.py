@@ -289,7 +289,7 @@ def _run_bench(env_extra, nproc, *args, timeout=600, preflight=False):
     with tempfile.TemporaryDirectory() as tmp:
         detail = os.path.join(tmp, "detail.json")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--detail", detail, *args]
+               "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--full", "--detail", detail, *args]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env)
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         if preflight:                    # (a line only: nothing goes to a detail file)
@@ -378,7 +378,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
     with tempfile.TemporaryDirectory() as tmp:
         detail = os.path.join(tmp, "detail.json")
         r = _run_bench_plain({"MSPMV_BENCH_ONE_DEVICE": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--c5-scale", "18", "--c5-edges", "3000000",
-                             "--c5-single-gpu-leg", "--detail", detail)
+                             "--c5-single-gpu-leg", "--full", "--detail", detail)
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
         assert len(r.stdout.splitlines()[-1].encode()) < 4096
         out = _line_and_detail(r.stdout, detail)
@@ -390,6 +390,21 @@ def test_bench_gpus_n_starts_its_own_ranks():
     assert c5["per_rank"]["nnz_per_rank_max"] > 0 and c5["single_gpu_same_workload"]["value"] > 0
     cmp = c5["single_gpu_same_workload"]["rank0_rows_vs_single_gpu"]
     assert cmp["not_bitwise_equal"] == 0 or cmp["rows"] - cmp["first_differing_row"] <= cmp["tile_items"]
+
+
+@gpu
+def test_bench_gpus_n_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full an N > 1 run times the headline and stops: no per-rank pass, no config-5 leg, no detail file; --dump-outputs
+    leaves every rank's owned rows of y, together the whole weak-scaled matrix's."""
+    import json
+    r = _run_bench_plain({"MSPMV_BENCH_ONE_DEVICE": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    out = json.loads(r.stdout.splitlines()[-1])
+    assert out["n_gpus"] == 2 and out["steps"] == 3 and out["scaling"] == "weak" and out["dtype"] == "f32" and out["ms_per_step"] > 0
+    for k in ("per_rank", "c5_strong", "roofline", "detail"):
+        assert k not in out, k
+    ys = [np.load(tmp_path / f"y_rank{i}.npy") for i in range(2)]
+    assert all(y.dtype == np.float32 and np.isfinite(y).all() for y in ys) and sum(y.size for y in ys) == 2 * 3_125_000
 
 
 def test_bench_gpus_n_self_launch_reports_failure_of_its_ranks():

@@ -123,31 +123,24 @@ def test_strict_check_behaviour():
 
 
 REF_SEARCH = os.path.join(ROOT, "oracle", "_ref", "ref_search")
+FRESH = os.path.join(ROOT, "tests", "golden", "ref_search_fresh.npz")
 
 
-@pytest.mark.skipif(not os.access(REF_SEARCH, os.X_OK), reason="oracle/_ref/ref_search (the reference's cub::MergePathSearch compiled here by oracle/Makefile) is not present")
 @pytest.mark.parametrize("seed", range(6))
-def test_oracle_search_against_the_compiled_reference_on_fresh_inputs(tmp_path, seed):
-    """Beyond the committed golden vectors: the oracle's MergePathSearch against the REFERENCE's own cub::MergePathSearch
-    (cub/thread/thread_search.cuh:53-84, compiled from /root/reference by oracle/Makefile into oracle/_ref/ref_search -- a binary that
-    travels with the snapshot, not a source) on freshly drawn row-length patterns: every diagonal of every matrix, clamped ones included.
-    Runs wherever the binary is (the authoring container, the GPU box); skipped where it is not."""
-    import subprocess
-    rng = np.random.default_rng(1000 + seed)
-    rows = int(rng.integers(1, 400))
-    kind = seed % 3
-    lens = (rng.integers(0, 6, rows) if kind == 0 else
-            np.where(rng.random(rows) < 0.03, rng.integers(50, 900, rows), 0) if kind == 1 else
-            np.minimum((rng.pareto(1.0, rows) * 2).astype(np.int64), 500))
-    off = np.zeros(rows + 1, np.int64); np.cumsum(lens, out=off[1:])
-    nnz = int(off[-1])
-    path = tmp_path / "offsets.txt"
-    path.write_text(f"{rows} {nnz}\n" + " ".join(map(str, off)) + "\n")
-    out = subprocess.run([REF_SEARCH, str(path)], check=True, capture_output=True, text=True).stdout
+def test_oracle_search_against_the_compiled_reference_on_fresh_inputs(seed):
+    """Beyond the matrices of the golden cases: the oracle's MergePathSearch against the REFERENCE's own cub::MergePathSearch
+    (cub/thread/thread_search.cuh:53-84, compiled from the reference by oracle/Makefile into oracle/_ref/ref_search) on seeded
+    row-length patterns: every diagonal of every matrix, clamped ones included.  What the reference answered is stored in
+    tests/golden/ref_search_fresh.npz (oracle/make_golden.py); where the binary is built it is asked again and must agree."""
+    from oracle import make_golden
+    off = make_golden.fresh_offsets(seed)
+    rows, nnz = len(off) - 1, int(off[-1])
+    stored = np.load(FRESH)
+    assert np.array_equal(stored[f"off{seed}"], off), "the seeded inputs no longer match the stored ones"
+    coords = stored[f"coords{seed}"]
+    if os.access(REF_SEARCH, os.X_OK):
+        assert np.array_equal(make_golden.search_all_diagonals(off), coords)
     row_end = off[1:].astype(np.int32)
-    n = 0
-    for line in out.splitlines():
-        d, x, y = map(int, line.split())
+    assert coords.shape == (rows + nnz + 4, 3) and np.array_equal(coords[:, 0], np.arange(rows + nnz + 4))
+    for d, x, y in coords.tolist():
         assert O.merge_path_search(d, row_end, rows, nnz) == (x, y), (seed, d)
-        n += 1
-    assert n == rows + nnz + 4

@@ -1,4 +1,4 @@
-"""bench.py --full: the legs that take minutes and do not belong in the driver's default run -- live L2<->fabric counters by two
+"""bench.py --extras (with --full): the legs that take minutes and do not belong in the driver's default run -- live L2<->fabric counters by two
 rocprofv3 --pmc child runs per record, the rocSPARSE comparison column, the opt-in plans (band-major, hot columns) and config 5 on
 one GPU.  Everything lands in the detail file; bench.compact_line keeps a few numbers of it."""
 import csv

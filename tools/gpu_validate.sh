@@ -20,14 +20,14 @@ tests)
   ( time timeout 1500 python -m pytest tests -m gpu -x -q -s 2>&1 | tail -12 ) > $O/tests.txt 2>&1
   python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 ;;
 bench)
-  timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_c2.txt 2>&1
-  timeout 600 python bench.py --steps 20 --warmup 5 --dtype f64 --no-cpu-baseline > $O/bench_c2_f64.txt 2>&1
-  timeout 600 python bench.py --steps 20 --warmup 5 --workload dense32 --no-cpu-baseline > $O/bench_dense32.txt 2>&1
-  timeout 600 python bench.py --workload c5 --steps 20 --warmup 3 > $O/bench_c5_n1.txt 2>&1
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_c2.txt 2>&1
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --dtype f64 --no-cpu-baseline > $O/bench_c2_f64.txt 2>&1
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --workload dense32 --no-cpu-baseline > $O/bench_dense32.txt 2>&1
+  timeout 600 python bench.py --full --workload c5 --steps 20 --warmup 3 > $O/bench_c5_n1.txt 2>&1
   MSPMV_BENCH_FORCE_MG=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 \
-      bench.py --gpus 1 --steps 10 --warmup 2 > $O/bench_c5_forced_mg.txt 2>&1
+      bench.py --full --gpus 1 --steps 10 --warmup 2 > $O/bench_c5_forced_mg.txt 2>&1
   MSPMV_BENCH_ONE_DEVICE=1 MSPMV_BENCH_BACKEND=gloo timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-      --master-port 29512 bench.py --gpus 2 --steps 5 --warmup 2 > $O/bench_c5_2ranks_one_device.txt 2>&1 ;;
+      --master-port 29512 bench.py --full --gpus 2 --steps 5 --warmup 2 > $O/bench_c5_2ranks_one_device.txt 2>&1 ;;
 profiles)
   bash tools/gpu_profile.sh c2 > $O/prof_c2.log 2>&1
   bash tools/gpu_profile.sh c2_f64 --dtype f64 > $O/prof_c2_f64.log 2>&1
