@@ -55,7 +55,7 @@ extern "C" {
  * no HIP headers (NULL = the default stream). */
 typedef void *mspmv_stream_t;
 
-#define MSPMV_VERSION 102 /* 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
+#define MSPMV_VERSION 102 /* (the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
 int mspmv_version(void);
 
 /* hipGetErrorString for codes returned by this library. */
@@ -238,6 +238,54 @@ int mspmv_csrmv_hotcols_apply_permuted_f64(void *d_plan, size_t plan_bytes, cons
  * and the renumbered column indices (nnz entries) */
 const int32_t *mspmv_csrmv_hotcols_order(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes);
 const int32_t *mspmv_csrmv_hotcols_columns(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes);
+
+/* ---- extension: the TRANSPOSE.  A^T as CSR (= A as CSC), built on the device by a stable least-significant-digit radix sort
+ * of the nonzeros by column (csrc/mspmv_transpose.hip: 8 bits per pass, max(1, ceil(bits(cols - 1) / 8)) passes of upsweep ->
+ * scan -> downsweep, the (row, value, position) payload carried through every pass; no workgroup waits on another).  Outputs:
+ * row_offsets_t[cols + 1], column_indices_t[nnz] (the original row of each entry), values_t[nnz], and optionally
+ * permutation[nnz] with values_t[j] = values[permutation[j]].  STABLE: the entries of each row of A^T appear in their order in A
+ * (ascending original row; entries that share a column inside one row -- duplicates or unsorted rows -- in their original
+ * order), so the result is canonical and bit for bit what a stable transpose on the host gives.  d_values == NULL and
+ * d_values_t == NULL: structure (+ permutation) only, for either precision.  Same two-phase temp storage, 16-byte alignment,
+ * ownership, stream, debug_sync and error conventions as mspmv_csrmv_*; column indices are assumed to lie in [0, cols) as for
+ * the forward call; empty rows and empty columns, rows == 0, cols == 0 and nnz == 0 are accepted.  Temp storage: about
+ * 2 x nnz x (12 + value bytes) + 4 x nnz bytes when cols > 65536 (fewer for fewer passes; C2 fp32 3.7 GB).  Any forward entry point
+ * (prepared coordinates, the plans, SpMM, the multi-GPU operator) then applies to A^T as to any CSR matrix.
+ * Measured on MI355X (profiles/transpose_bench.txt): C2 (100 M nonzeros) 6.4 ms fp32 / 7.0 ms fp64 against rocsparse_csr2csc's
+ * 6.7 / 6.9 ms; A^T x through the built transpose then runs as the forward call does (C2 fp32 0.68 ms, A x 0.71 ms). ---- */
+int mspmv_csr_transpose_f32(void *d_temp, size_t *temp_bytes,
+                            const float *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                            int32_t rows, int32_t cols, int32_t nnz,
+                            float *d_values_t, int32_t *d_row_offsets_t, int32_t *d_column_indices_t,
+                            int32_t *d_permutation /* may be NULL */, mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_transpose_f64(void *d_temp, size_t *temp_bytes,
+                            const double *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                            int32_t rows, int32_t cols, int32_t nnz,
+                            double *d_values_t, int32_t *d_row_offsets_t, int32_t *d_column_indices_t,
+                            int32_t *d_permutation /* may be NULL */, mspmv_stream_t stream, int debug_sync);
+/* New values on the same pattern (Newton steps, training): values_t[j] = values[permutation[j]]. */
+int mspmv_csr_transpose_values_f32(const float *d_values, const int32_t *d_permutation, float *d_values_t,
+                                   int32_t nnz, mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_transpose_values_f64(const double *d_values, const int32_t *d_permutation, double *d_values_t,
+                                   int32_t nnz, mspmv_stream_t stream, int debug_sync);
+/* Stateless y = alpha*A^T*x + beta*y: x has `rows` entries, y has `cols`; beta == 0 never reads y.  Transposes into temp storage,
+ * then runs the ordinary CsrMV on the result: bitwise equal to mspmv_csr_transpose_* followed by mspmv_csrmv_axpby_* on its outputs
+ * with that call's queried temp size.  Needs cols + nnz <= 2^31 - 65537 (A^T's rows + nnz; the same int32 path bound as the forward
+ * call).  COST: every call pays the whole conversion, which is several times the SpMV itself; a caller that multiplies by A^T more
+ * than once builds A^T once (mspmv_csr_transpose_*) and calls the forward entry points on it, which run as fast as on any matrix of
+ * that shape.  Reproducibility has that price against a scatter-add transposed SpMV (rocSPARSE's csrmv with the transpose
+ * operation), which is faster on large, evenly spread matrices but adds in arrival order.  Measured (DESIGN.md 4 "Transpose"): C2
+ * fp32 6.9 ms stateless against 0.68 ms through a built A^T and rocSPARSE's 4.8 ms; grid2d 2000 fp64 1.27 ms against 0.041 / 0.126 ms;
+ * on skewed matrices, where the scatter serialises on hot columns, the stateless call is the faster one (C3 stand-in 0.25 against
+ * 3.6 ms). */
+int mspmv_csrmv_transpose_f32(void *d_temp, size_t *temp_bytes, const float *d_values,
+                              const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                              const float *d_x, float *d_y, int32_t rows, int32_t cols, int32_t nnz,
+                              float alpha, float beta, mspmv_stream_t stream, int debug_sync);
+int mspmv_csrmv_transpose_f64(void *d_temp, size_t *temp_bytes, const double *d_values,
+                              const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                              const double *d_x, double *d_y, int32_t rows, int32_t cols, int32_t nnz,
+                              double alpha, double beta, mspmv_stream_t stream, int debug_sync);
 
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */

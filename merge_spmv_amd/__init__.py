@@ -17,7 +17,7 @@ import ctypes
 import os
 from typing import Optional, Tuple
 
-__all__ = ["DeviceSpmv", "csrmv", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "plan_bench_record", "library_path", "load_library", "launch_info",
+__all__ = ["DeviceSpmv", "csrmv", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
 
@@ -150,6 +150,16 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "mspmv_csrmv_plan_apply_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, ctypes.c_size_t, vp, vp, i32, i32, i32, i32, ct, ct, vp, ctypes.c_int]
+    for name, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        fn = getattr(lib, "mspmv_csr_transpose_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, sz_p, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_int]
+        fn = getattr(lib, "mspmv_csr_transpose_values_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, i32, vp, ctypes.c_int]
+        fn = getattr(lib, "mspmv_csrmv_transpose_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, sz_p, vp, vp, vp, vp, vp, i32, i32, i32, ct, ct, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_size.restype = ctypes.c_int
     lib.mspmv_csrmv_hotcols_size.argtypes = [i32, i32, i32, i32, sz_p]
     lib.mspmv_csrmv_hotcols_build.restype = ctypes.c_int
@@ -230,7 +240,7 @@ def _stream_handle(stream) -> ctypes.c_void_p:
 
 
 def _validate(values, row_offsets, column_indices, x, y, rows: int, cols: int, nnz: int, what: str,
-              x_rows: Optional[int] = None) -> None:
+              x_rows: Optional[int] = None, y_rows: Optional[int] = None) -> None:
     """The checks the C ABI cannot make (it sees raw pointers): every csrmv / csrmm / DeviceSpmv.CsrMV
     call goes through here, so a wrong dtype, device, stride or length is an MspmvError instead of
     a reinterpretation of memory.  x / y may be 1-D (CsrMV) or 2-D row-major (SpMM)."""
@@ -252,7 +262,7 @@ def _validate(values, row_offsets, column_indices, x, y, rows: int, cols: int, n
     if nnz > 0:
         if values is None or values.dtype != y.dtype or values.device != dev or not values.is_contiguous() or values.numel() < nnz:
             raise MspmvError(f"{what}: values must be a contiguous {y.dtype} tensor on {dev} with at least {nnz} entries")
-    for t, name, need in ((x, "x", cols if x_rows is None else x_rows), (y, "y", rows)):
+    for t, name, need in ((x, "x", cols if x_rows is None else x_rows), (y, "y", rows if y_rows is None else y_rows)):
         if t is None:
             if need == 0 or (name == "x" and nnz == 0):
                 continue
@@ -357,10 +367,14 @@ class CsrMVWorkspace:
 
 def csrmv(values, row_offsets, column_indices, x, y=None, num_cols: Optional[int] = None,
           workspace: Optional[CsrMVWorkspace] = None, stream=None, alpha=None, beta=None,
-          debug_synchronous: bool = False):
+          debug_synchronous: bool = False, transpose: bool = False):
     """Convenience wrapper: size query + temp allocation + CsrMV.  Tensors must
-    be contiguous CUDA tensors.  Returns y."""
+    be contiguous CUDA tensors.  Returns y.  transpose=True: y = alpha*A^T*x + beta*y through the stateless
+    mspmv_csrmv_transpose_* (x has rows entries, y cols; `workspace` is not used) -- a caller that multiplies by
+    A^T more than once builds it once with CsrTranspose instead."""
     import torch
+    if transpose:
+        return _csrmv_transpose(values, row_offsets, column_indices, x, y, num_cols, stream, alpha, beta, debug_synchronous)
     if not values.is_cuda or not row_offsets.is_cuda or not x.is_cuda:
         raise MspmvError("csrmv needs CUDA (HIP) tensors: the merge-path kernels only run on the GPU")
     if row_offsets.dtype != torch.int32 or column_indices.dtype != torch.int32:
@@ -434,6 +448,105 @@ def csrmm(values, row_offsets, column_indices, X, Y=None, alpha: float = 1.0, be
     size = ctypes.c_size_t(temp.numel())
     _check(call(ctypes.c_void_p(temp.data_ptr()), size), "mspmv_csrmm")
     return Y
+
+
+def _csrmv_transpose(values, row_offsets, column_indices, x, y, num_cols, stream, alpha, beta, debug_synchronous):
+    import torch
+    if not values.is_cuda or not row_offsets.is_cuda or not x.is_cuda:
+        raise MspmvError("csrmv needs CUDA (HIP) tensors: the merge-path kernels only run on the GPU")
+    if row_offsets.dtype != torch.int32 or column_indices.dtype != torch.int32:
+        raise TypeError("row_offsets/column_indices must be int32 (OffsetT=int, gpu_spmv.cu:730,734)")
+    if num_cols is None:
+        raise MspmvError("csrmv(transpose=True) needs num_cols: y has one entry per column of A")
+    rows, cols, nnz = row_offsets.numel() - 1, int(num_cols), values.numel()
+    if y is None:
+        y = torch.empty(cols, dtype=values.dtype, device=values.device)
+    # the checks of the forward call with the roles of rows and cols swapped for the vectors: x has `rows` entries, y has `cols`
+    _validate(values, row_offsets, column_indices, x, y, rows, cols, nnz, "csrmv(transpose=True)", x_rows=rows, y_rows=cols)
+    vb = _value_bytes(values)
+    lib = load_library()
+    fn = lib.mspmv_csrmv_transpose_f32 if vb == 4 else lib.mspmv_csrmv_transpose_f64
+    ct = ctypes.c_float if vb == 4 else ctypes.c_double
+    a, b = ct(1.0 if alpha is None else alpha), ct(0.0 if beta is None else beta)
+    size = ctypes.c_size_t(0)
+    args = (_ptr(values), _ptr(row_offsets), _ptr(column_indices), _ptr(x), _ptr(y), rows, cols, nnz, a, b)
+    _check(fn(ctypes.c_void_p(0), ctypes.byref(size), *args, ctypes.c_void_p(0), 0), "mspmv_csrmv_transpose (size query)")
+    temp = torch.empty(max(int(size.value), 1), dtype=torch.uint8, device=values.device)
+    _check(fn(ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), *args, _stream_handle(stream), int(bool(debug_synchronous))),
+           "mspmv_csrmv_transpose")
+    if stream is not None and hasattr(stream, "cuda_stream"):
+        temp.record_stream(stream)
+    return y
+
+
+def csr_transpose(values, row_offsets, column_indices, num_cols: int, stream=None):
+    """A^T as CSR on the device (mspmv_csr_transpose_*): returns (values_t, row_offsets_t, column_indices_t, permutation) with
+    values_t[j] = values[permutation[j]]; the entries of each row of A^T in their order in A (stable), so the result is canonical.
+    values=None: the structure only (values_t is None).  Asynchronous on `stream`."""
+    import torch
+    if row_offsets is None or not row_offsets.is_cuda or row_offsets.dtype != torch.int32 or not row_offsets.is_contiguous():
+        raise MspmvError("csr_transpose: row_offsets must be a contiguous int32 CUDA tensor")
+    rows, cols = row_offsets.numel() - 1, int(num_cols)
+    nnz = column_indices.numel() if values is None else values.numel()
+    if rows < 0:
+        raise MspmvError("csr_transpose: row_offsets needs rows + 1 entries")
+    dev = row_offsets.device
+    dtype = torch.float32 if values is None else values.dtype
+    probe = torch.empty(0, dtype=dtype, device=dev)
+    if values is None:              # structure only
+        _validate(None, row_offsets, None, None, probe, rows, cols, 0, "csr_transpose", x_rows=0, y_rows=0)
+        if nnz > 0 and (column_indices.dtype != torch.int32 or column_indices.device != dev or not column_indices.is_contiguous()):
+            raise MspmvError(f"csr_transpose: column_indices must be a contiguous int32 tensor on {dev}")
+    else:
+        _validate(values, row_offsets, column_indices, None, probe, rows, cols, nnz, "csr_transpose", x_rows=0, y_rows=0)
+    vb = _value_bytes(probe)
+    lib = load_library()
+    fn = lib.mspmv_csr_transpose_f32 if vb == 4 else lib.mspmv_csr_transpose_f64
+    values_t = None if values is None else torch.empty(nnz, dtype=dtype, device=dev)
+    row_offsets_t = torch.empty(cols + 1, dtype=torch.int32, device=dev)
+    column_indices_t = torch.empty(nnz, dtype=torch.int32, device=dev)
+    permutation = torch.empty(nnz, dtype=torch.int32, device=dev)
+    size = ctypes.c_size_t(0)
+    args = (_ptr(values), _ptr(row_offsets), _ptr(column_indices), rows, cols, nnz, _ptr(values_t), ctypes.c_void_p(row_offsets_t.data_ptr()),
+            _ptr(column_indices_t), _ptr(permutation))
+    _check(fn(ctypes.c_void_p(0), ctypes.byref(size), *args, ctypes.c_void_p(0), 0), "mspmv_csr_transpose (size query)")
+    temp = torch.empty(max(int(size.value), 1), dtype=torch.uint8, device=dev)
+    _check(fn(ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), *args, _stream_handle(stream), 0), "mspmv_csr_transpose")
+    if stream is not None and hasattr(stream, "cuda_stream"):
+        temp.record_stream(stream)        # (the allocator must not hand `temp` out again before the conversion on `stream` has run)
+    return values_t, row_offsets_t, column_indices_t, permutation
+
+
+class CsrTranspose:
+    """A^T built once on the device (csr_transpose) for a caller that multiplies by it many times: holds A^T's tensors, the
+    permutation and a CsrMVWorkspace prepared for A^T.  `t(x, y)` computes y = alpha*A^T*x + beta*y with the ordinary forward call on
+    A^T (x has A's rows entries, y A's cols); `t.matmul(X, Y)` is csrmm on A^T; `t.refresh_values(values)` takes new values on the
+    same pattern."""
+
+    def __init__(self, values, row_offsets, column_indices, num_cols: int, stream=None):
+        self.rows, self.cols, self.nnz = row_offsets.numel() - 1, int(num_cols), values.numel()
+        self.dtype = values.dtype
+        self.values_t, self.row_offsets_t, self.column_indices_t, self.permutation = \
+            csr_transpose(values, row_offsets, column_indices, num_cols, stream=stream)
+        self.workspace = CsrMVWorkspace(self.cols, self.nnz, self.dtype, device=values.device).prepare(self.row_offsets_t, stream=stream)
+
+    def refresh_values(self, values, stream=None):
+        """values_t[j] = values[permutation[j]] (mspmv_csr_transpose_values_*) for new values on A's pattern."""
+        if values.dtype != self.dtype or values.device != self.values_t.device or not values.is_contiguous() or values.numel() != self.nnz:
+            raise MspmvError(f"CsrTranspose.refresh_values: values must be a contiguous {self.dtype} tensor of {self.nnz} entries on "
+                             f"{self.values_t.device}")
+        vb = _value_bytes(values)
+        fn = load_library().mspmv_csr_transpose_values_f32 if vb == 4 else load_library().mspmv_csr_transpose_values_f64
+        _check(fn(_ptr(values), _ptr(self.permutation), _ptr(self.values_t), self.nnz, _stream_handle(stream), 0),
+               "mspmv_csr_transpose_values")
+        return self
+
+    def __call__(self, x, y=None, alpha: float = 1.0, beta: float = 0.0, stream=None):
+        return csrmv(self.values_t, self.row_offsets_t, self.column_indices_t, x, y, num_cols=self.rows, workspace=self.workspace,
+                     stream=stream, alpha=alpha, beta=beta)
+
+    def matmul(self, X, Y=None, alpha: float = 1.0, beta: float = 0.0, stream=None):
+        return csrmm(self.values_t, self.row_offsets_t, self.column_indices_t, X, Y, alpha=alpha, beta=beta, stream=stream)
 
 
 class CsrMVPlan:

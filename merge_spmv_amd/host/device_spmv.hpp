@@ -9,6 +9,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/mspmv.h"
 
 namespace mspmv {
@@ -123,6 +125,54 @@ struct DeviceSpmv {
     {
         return (hipError_t) mspmv_csrmv_plan_apply_f64(d_plan, plan_bytes, d_vector_x, d_vector_y, num_rows, num_cols, num_nonzeros, bands,
                                                        alpha, beta, (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+    }
+
+    // ---- transpose (extension): A^T as CSR on the device, stable (d_values == d_values_t == nullptr: structure only) ...
+    template <typename ValueT>
+    static hipError_t CsrTranspose(void *d_temp_storage, size_t &temp_storage_bytes, const ValueT *d_values, const int *d_row_offsets,
+                                   const int *d_column_indices, int num_rows, int num_cols, int num_nonzeros, ValueT *d_values_t,
+                                   int *d_row_offsets_t, int *d_column_indices_t, int *d_permutation = nullptr, hipStream_t stream = 0,
+                                   bool debug_synchronous = false)
+    {
+        static_assert(std::is_same<ValueT, float>::value || std::is_same<ValueT, double>::value, "float or double");
+        if constexpr (std::is_same<ValueT, float>::value)
+            return (hipError_t) mspmv_csr_transpose_f32(d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices, num_rows,
+                                                        num_cols, num_nonzeros, d_values_t, d_row_offsets_t, d_column_indices_t, d_permutation,
+                                                        (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+        else
+            return (hipError_t) mspmv_csr_transpose_f64(d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices, num_rows,
+                                                        num_cols, num_nonzeros, d_values_t, d_row_offsets_t, d_column_indices_t, d_permutation,
+                                                        (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+    }
+    // ... new values on the same pattern: values_t[j] = values[permutation[j]]
+    template <typename ValueT>
+    static hipError_t CsrTransposeValues(const ValueT *d_values, const int *d_permutation, ValueT *d_values_t, int num_nonzeros,
+                                         hipStream_t stream = 0, bool debug_synchronous = false)
+    {
+        static_assert(std::is_same<ValueT, float>::value || std::is_same<ValueT, double>::value, "float or double");
+        if constexpr (std::is_same<ValueT, float>::value)
+            return (hipError_t) mspmv_csr_transpose_values_f32(d_values, d_permutation, d_values_t, num_nonzeros, (mspmv_stream_t) stream,
+                                                               debug_synchronous ? 1 : 0);
+        else
+            return (hipError_t) mspmv_csr_transpose_values_f64(d_values, d_permutation, d_values_t, num_nonzeros, (mspmv_stream_t) stream,
+                                                               debug_synchronous ? 1 : 0);
+    }
+    // ... stateless y = alpha*A^T*x + beta*y (x: num_rows entries, y: num_cols): transposes into temp storage every call
+    template <typename ValueT>
+    static hipError_t CsrMVTranspose(void *d_temp_storage, size_t &temp_storage_bytes, const ValueT *d_values, const int *d_row_offsets,
+                                     const int *d_column_indices, const ValueT *d_vector_x, ValueT *d_vector_y, int num_rows, int num_cols,
+                                     int num_nonzeros, ValueT alpha = 1, ValueT beta = 0, hipStream_t stream = 0,
+                                     bool debug_synchronous = false)
+    {
+        static_assert(std::is_same<ValueT, float>::value || std::is_same<ValueT, double>::value, "float or double");
+        if constexpr (std::is_same<ValueT, float>::value)
+            return (hipError_t) mspmv_csrmv_transpose_f32(d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices,
+                                                          d_vector_x, d_vector_y, num_rows, num_cols, num_nonzeros, alpha, beta,
+                                                          (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+        else
+            return (hipError_t) mspmv_csrmv_transpose_f64(d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices,
+                                                          d_vector_x, d_vector_y, num_rows, num_cols, num_nonzeros, alpha, beta,
+                                                          (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
     }
 };
 

@@ -9,13 +9,16 @@
 //
 //   gpu_spmv [--device=<id>] [--quiet] [--v] [--v2] [--i=<iterations>] [--fp32]
 //            [--alpha=<a>] [--beta=<b>] [--peak-gbs=<GB/s>] [--no-strict] [--no-vendor] [--no-hyb] [--check]
-//            [--prepared] [--plan[=<bands>]] [--gpus=<G>[,<G2>...]] [--mg-one-device] [--mg-exchange=peer|rccl]
+//            [--prepared] [--plan[=<bands>]] [--transpose] [--gpus=<G>[,<G2>...]] [--mg-one-device] [--mg-exchange=peer|rccl]
 //            --mtx=<file> | --dense=<cols> [--size=<nnz>] | --grid2d=<w> | --grid3d=<w> | --wheel=<spokes>
 //
 // Extra method lines of this project (non-quiet only; the CSV keeps the reference's columns):
 //   --prepared   the stateless call with the tile coordinates found once (mspmv_csrmv_prepare)
 //   --plan       the prepared band-major plan (mspmv_csrmv_plan_*): set-up = the plan build
 //   --hotcols    the hot-column plan (mspmv_csrmv_hotcols_*): set-up = ranking the columns by reference count
+//   --transpose  y = alpha*A^T*x + beta*y: A^T built on the device (mspmv_csr_transpose_*; set-up, checked entry for entry against a
+//                stable transpose on the host), the forward call on it, the stateless mspmv_csrmv_transpose_*, and (with the vendor
+//                lines) rocSPARSE CsrMV with the transpose operation, set-up = rocsparse_csr2csc
 //   --gpus=G     the matrix merge-partitioned over G GPUs of this node through the C multi-GPU operator
 //                (mspmv_mg_plan_*; the reference has a single --device, utils.h:465-474), one line per G;
 //                --mg-one-device runs all parts on --device (a functional run on a 1-GPU box)
@@ -343,10 +346,12 @@ template <typename V> struct Roc;
 template <> struct Roc<float> {
     static constexpr auto analysis = rocsparse_scsrmv_analysis; static constexpr auto csrmv = rocsparse_scsrmv;
     static constexpr auto csr2hyb = rocsparse_scsr2hyb; static constexpr auto hybmv = rocsparse_shybmv;
+    static constexpr auto csr2csc = rocsparse_scsr2csc;
 };
 template <> struct Roc<double> {
     static constexpr auto analysis = rocsparse_dcsrmv_analysis; static constexpr auto csrmv = rocsparse_dcsrmv;
     static constexpr auto csr2hyb = rocsparse_dcsr2hyb; static constexpr auto hybmv = rocsparse_dhybmv;
+    static constexpr auto csr2csc = rocsparse_dcsr2csc;
 };
 
 // rocSPARSE CsrMV, the counterpart of TestCusparseCsrmv (gpu_spmv.cu:262-364); setup = analysis
@@ -410,7 +415,123 @@ float TestRocsparseHybmv(const RunConfig &c, const CsrMatrix<V> &a, const std::v
     return ms;
 }
 
-struct Extras { bool vendor = true, hyb = true, prepared = false, plan = false, hotcols = false, mg_one_device = false; int plan_bands = 0, mg_exchange = MSPMV_MG_EXCHANGE_AUTO; std::vector<int> gpus; };
+// --transpose (extension): A^T as CSR, stable (entries of each column in row order), built on the host for the exact check and the gold
+template <typename V>
+void HostTranspose(const CsrMatrix<V> &a, CsrMatrix<V> &t)
+{
+    t.num_rows = a.num_cols; t.num_cols = a.num_rows; t.num_nonzeros = a.num_nonzeros;
+    t.row_offsets.assign((size_t) a.num_cols + 1, 0);
+    t.column_indices.resize((size_t) a.num_nonzeros); t.values.resize((size_t) a.num_nonzeros);
+    for (int j = 0; j < a.num_nonzeros; ++j) ++t.row_offsets[(size_t) a.column_indices[j] + 1];
+    for (int c = 0; c < a.num_cols; ++c) t.row_offsets[(size_t) c + 1] += t.row_offsets[c];
+    std::vector<int> next(t.row_offsets.begin(), t.row_offsets.end() - 1);
+    for (int r = 0; r < a.num_rows; ++r)
+        for (int j = a.row_offsets[r]; j < a.row_offsets[r + 1]; ++j) {
+            const int k = next[a.column_indices[j]]++;
+            t.column_indices[k] = r; t.values[k] = a.values[j];
+        }
+}
+
+// A^T on the device (mspmv_csr_transpose_*), timed as set-up and checked entry for entry against HostTranspose; `pt` then holds it
+template <typename V>
+float BuildTranspose(const CsrMatrix<V> &at, DeviceProblem<V> &p, DeviceProblem<V> &pt)
+{
+    pt.rows = p.cols; pt.cols = p.rows; pt.nnz = p.nnz;
+    HIP_OK(hipMalloc(&pt.d_values, sizeof(V) * std::max(pt.nnz, 1)));
+    HIP_OK(hipMalloc(&pt.d_row_offsets, sizeof(int) * (pt.rows + 1)));
+    HIP_OK(hipMalloc(&pt.d_cols, sizeof(int) * std::max(pt.nnz, 1)));
+    HIP_OK(hipMalloc(&pt.d_x, sizeof(V) * std::max(pt.cols, 1)));
+    HIP_OK(hipMalloc(&pt.d_y, sizeof(V) * std::max(pt.rows, 1)));
+    size_t bytes = 0;
+    HIP_OK(mspmv::DeviceSpmv::CsrTranspose<V>(nullptr, bytes, p.d_values, p.d_row_offsets, p.d_cols, p.rows, p.cols, p.nnz, pt.d_values,
+                                              pt.d_row_offsets, pt.d_cols));
+    void *d_temp = nullptr;
+    HIP_OK(hipMalloc(&d_temp, bytes));
+    GpuTimer setup; setup.Start();
+    HIP_OK(mspmv::DeviceSpmv::CsrTranspose<V>(d_temp, bytes, p.d_values, p.d_row_offsets, p.d_cols, p.rows, p.cols, p.nnz, pt.d_values,
+                                              pt.d_row_offsets, pt.d_cols));
+    setup.Stop();
+    const float ms = setup.ElapsedMillis();
+    HIP_OK(hipFree(d_temp));
+    std::vector<int> off((size_t) pt.rows + 1), col((size_t) pt.nnz);
+    std::vector<V> val((size_t) pt.nnz);
+    HIP_OK(hipMemcpy(off.data(), pt.d_row_offsets, sizeof(int) * off.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(col.data(), pt.d_cols, sizeof(int) * col.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(val.data(), pt.d_values, sizeof(V) * val.size(), hipMemcpyDeviceToHost));
+    const bool same = off == at.row_offsets && std::equal(col.begin(), col.end(), at.column_indices.begin()) &&
+                      std::memcmp(val.data(), at.values.data(), sizeof(V) * val.size()) == 0;
+    printf("\ttranspose built on the device: %s (row offsets, column indices and values bit for bit the stable transpose)\n",
+           same ? "PASS" : "FAIL");
+    return ms;
+}
+
+// the stateless y = alpha*A^T*x + beta*y (mspmv_csrmv_transpose_*): the conversion inside every call
+template <typename V>
+float TestTransposeStateless(const RunConfig &c, const CsrMatrix<V> &at, const std::vector<V> &xt, const std::vector<V> &yt_in,
+                             const std::vector<V> &gold_t, DeviceProblem<V> &p, DeviceProblem<V> &pt, int iterations)
+{
+    auto call = [&](void *temp, size_t &bytes, bool debug) {
+        return mspmv::DeviceSpmv::CsrMVTranspose<V>(temp, bytes, p.d_values, p.d_row_offsets, p.d_cols, pt.d_x, pt.d_y, p.rows, p.cols, p.nnz,
+                                                    (V) c.alpha, (V) c.beta, (hipStream_t) 0, debug);
+    };
+    size_t bytes = 0;
+    HIP_OK(call(nullptr, bytes, false));
+    void *d_temp = nullptr;
+    HIP_OK(hipMalloc(&d_temp, bytes));
+    HIP_OK(hipMemcpy(pt.d_y, yt_in.data(), sizeof(V) * pt.rows, hipMemcpyHostToDevice));
+    HIP_OK(call(d_temp, bytes, false));
+    Verify(c, at, xt, gold_t, pt.d_y, c.alpha == 1.0f && c.beta == 0.0f);
+    GpuTimer timer; timer.Start();
+    for (int it = 0; it < iterations; ++it) HIP_OK(call(d_temp, bytes, false));
+    timer.Stop();
+    const float ms = timer.ElapsedMillis() / iterations;
+    HIP_OK(hipFree(d_temp));
+    return ms;
+}
+
+// rocSPARSE CsrMV with rocsparse_operation_transpose on A; set-up = rocsparse_csr2csc (what building A^T costs the vendor library)
+template <typename V>
+float TestRocsparseTranspose(const RunConfig &c, const CsrMatrix<V> &at, const std::vector<V> &xt, const std::vector<V> &yt_in,
+                             const std::vector<V> &gold_t, DeviceProblem<V> &p, DeviceProblem<V> &pt, int iterations, float &setup_ms,
+                             rocsparse_handle handle)
+{
+    {   // the conversion, timed apart (its outputs are not used)
+        size_t bytes = 0;
+        ROCSPARSE_OK(rocsparse_csr2csc_buffer_size(handle, p.rows, p.cols, p.nnz, p.d_row_offsets, p.d_cols, rocsparse_action_numeric, &bytes));
+        void *buf = nullptr, *val = nullptr, *row = nullptr, *off = nullptr;
+        HIP_OK(hipMalloc(&buf, std::max<size_t>(bytes, 1))); HIP_OK(hipMalloc(&val, sizeof(V) * std::max(p.nnz, 1)));
+        HIP_OK(hipMalloc(&row, sizeof(int) * std::max(p.nnz, 1))); HIP_OK(hipMalloc(&off, sizeof(int) * (p.cols + 1)));
+        GpuTimer setup; setup.Start();
+        ROCSPARSE_OK(Roc<V>::csr2csc(handle, p.rows, p.cols, p.nnz, p.d_values, p.d_row_offsets, p.d_cols, (V *) val, (int *) row, (int *) off,
+                                     rocsparse_action_numeric, rocsparse_index_base_zero, buf));
+        setup.Stop(); setup_ms = setup.ElapsedMillis();
+        HIP_OK(hipFree(buf)); HIP_OK(hipFree(val)); HIP_OK(hipFree(row)); HIP_OK(hipFree(off));
+    }
+    rocsparse_mat_descr descr; rocsparse_mat_info info;
+    ROCSPARSE_OK(rocsparse_create_mat_descr(&descr));
+    ROCSPARSE_OK(rocsparse_create_mat_info(&info));
+    rocsparse_mat_info use = info;      // (no analysis for the transpose in some releases: then the call runs without one)
+    if (Roc<V>::analysis(handle, rocsparse_operation_transpose, p.rows, p.cols, p.nnz, descr, p.d_values, p.d_row_offsets, p.d_cols, info) !=
+        rocsparse_status_success)
+        use = nullptr;
+    const V alpha = (V) c.alpha, beta = (V) c.beta;
+    auto call = [&]() {
+        ROCSPARSE_OK(Roc<V>::csrmv(handle, rocsparse_operation_transpose, p.rows, p.cols, p.nnz, &alpha, descr, p.d_values, p.d_row_offsets,
+                                   p.d_cols, use, pt.d_x, &beta, pt.d_y));
+    };
+    HIP_OK(hipMemcpy(pt.d_y, yt_in.data(), sizeof(V) * pt.rows, hipMemcpyHostToDevice));
+    call();
+    Verify(c, at, xt, gold_t, pt.d_y, c.alpha == 1.0f && c.beta == 0.0f);
+    GpuTimer timer; timer.Start();
+    for (int it = 0; it < iterations; ++it) call();
+    timer.Stop();
+    const float ms = timer.ElapsedMillis() / iterations;
+    ROCSPARSE_OK(rocsparse_destroy_mat_info(info));
+    ROCSPARSE_OK(rocsparse_destroy_mat_descr(descr));
+    return ms;
+}
+
+struct Extras { bool vendor = true, hyb = true, prepared = false, plan = false, hotcols = false, transpose = false, mg_one_device = false; int plan_bands = 0, mg_exchange = MSPMV_MG_EXCHANGE_AUTO; std::vector<int> gpus; };
 
 template <typename V>
 void Run(const RunConfig &c, const Device &dev, const Extras &ex)
@@ -460,6 +581,30 @@ void Run(const RunConfig &c, const Device &dev, const Extras &ex)
         DisplayPerf(c.quiet, (int) sizeof(V), setup_ms, avg_ms, csr.num_rows, csr.num_nonzeros, dev.giga_bandwidth);
         DisplayRoofline((int) sizeof(V), avg_ms, csr.num_rows, csr.num_cols, csr.num_nonzeros, dev.giga_bandwidth);
     }
+    if (ex.transpose && !c.quiet) {             // extra method lines, never in the CSV: y = alpha*A^T*x + beta*y
+        CsrMatrix<V> at;
+        HostTranspose(csr, at);
+        std::vector<V> xt((size_t) at.num_cols, (V) 1.0), yt_in((size_t) at.num_rows, (V) 1.0), gold_t((size_t) at.num_rows);
+        SpmvGold(at, xt.data(), yt_in.data(), gold_t.data(), (V) c.alpha, (V) c.beta);
+        DeviceProblem<V> pt;
+        printf("\n\nMerge-based CsrMV (transpose: A^T built once on the device), "); fflush(stdout);
+        const float build_ms = BuildTranspose(at, p, pt);
+        HIP_OK(hipMemcpy(pt.d_x, xt.data(), sizeof(V) * pt.cols, hipMemcpyHostToDevice));
+        avg_ms = TestMerge(c, at, xt, yt_in, gold_t, pt, iterations, setup_ms);
+        DisplayPerf(c.quiet, (int) sizeof(V), build_ms, avg_ms, at.num_rows, at.num_nonzeros, dev.giga_bandwidth);
+        DisplayRoofline((int) sizeof(V), avg_ms, at.num_rows, at.num_cols, at.num_nonzeros, dev.giga_bandwidth);
+        printf("\n\nMerge-based CsrMV (transpose: stateless, A^T built inside every call), "); fflush(stdout);
+        avg_ms = TestTransposeStateless(c, at, xt, yt_in, gold_t, p, pt, iterations);
+        DisplayPerf(c.quiet, (int) sizeof(V), 0.0, avg_ms, at.num_rows, at.num_nonzeros, dev.giga_bandwidth);
+        if (vendor) {
+            rocsparse_handle handle;
+            ROCSPARSE_OK(rocsparse_create_handle(&handle));
+            printf("\n\nrocSPARSE CsrMV (transpose), "); fflush(stdout);
+            avg_ms = TestRocsparseTranspose(c, at, xt, yt_in, gold_t, p, pt, iterations, setup_ms, handle);
+            DisplayPerf(c.quiet, (int) sizeof(V), setup_ms, avg_ms, at.num_rows, at.num_nonzeros, dev.giga_bandwidth);
+            ROCSPARSE_OK(rocsparse_destroy_handle(handle));
+        }
+    }
     if (!c.quiet && c.alpha == 1.0f && c.beta == 0.0f)
         for (int parts : ex.gpus) {
             int used = 0;
@@ -497,7 +642,7 @@ int main(int argc, char **argv)
     if (args.CheckCmdLineFlag("help")) {
         printf("%s [--csrmv | --hybmv | --bsrmv ] [--device=<device-id>] [--quiet] [--v] [--i=<timing iterations>] [--fp32] "
                "[--alpha=<alpha scalar (default: 1.0)>] [--beta=<beta scalar (default: 0.0)>] [--peak-gbs=<GB/s>] "
-               "[--no-strict] [--no-vendor] [--no-hyb] [--check] [--cache] [--prepared] [--plan[=<bands>]] [--hotcols] [--gpus=<G>[,<G2>...]] [--mg-one-device] "
+               "[--no-strict] [--no-vendor] [--no-hyb] [--check] [--cache] [--prepared] [--plan[=<bands>]] [--hotcols] [--transpose] [--gpus=<G>[,<G2>...]] [--mg-one-device] "
                "[--mg-exchange=peer|rccl] [--chunk-times=<calls per chunk>]\n"
                "\t--mtx=<matrix market file> \n\t--dense=<cols>\n\t--grid2d=<width>\n\t--grid3d=<width>\n\t--wheel=<spokes>\n",
                argv[0]);
@@ -510,6 +655,7 @@ int main(int argc, char **argv)
     ex.hyb = !args.CheckCmdLineFlag("no-hyb");          // (the CSR -> HYB conversion takes seconds on some small matrices)
     ex.prepared = args.CheckCmdLineFlag("prepared");
     ex.hotcols = args.CheckCmdLineFlag("hotcols");
+    ex.transpose = args.CheckCmdLineFlag("transpose");
     ex.plan = args.CheckCmdLineFlag("plan");
     args.GetCmdLineArgument("plan", ex.plan_bands);
     ex.mg_one_device = args.CheckCmdLineFlag("mg-one-device");
