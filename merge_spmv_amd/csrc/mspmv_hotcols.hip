@@ -77,7 +77,7 @@ __global__ __launch_bounds__(HC_BLOCK) void hot_class_sizes_kernel(const unsigne
     __shared__ unsigned s_n[CLASSES];
     if (threadIdx.x < CLASSES) s_n[threadIdx.x] = 0u;
     __syncthreads();
-    const int c = blockIdx.x * HC_BLOCK + threadIdx.x;
+    const long long c = (long long) blockIdx.x * HC_BLOCK + threadIdx.x;
     if (c < num_cols) atomicAdd(&s_n[hot_class(counts[c])], 1u);
     __syncthreads();
     if (threadIdx.x < CLASSES && s_n[threadIdx.x]) atomicAdd(&sizes[threadIdx.x], s_n[threadIdx.x]);
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(HC_BLOCK) void hot_rank_kernel(unsigned *__restrict
     __shared__ unsigned char s_cls[HC_BLOCK];
     if (threadIdx.x < CLASSES) s_n[threadIdx.x] = 0u;
     __syncthreads();
-    const int c = blockIdx.x * HC_BLOCK + threadIdx.x;
+    const long long c = (long long) blockIdx.x * HC_BLOCK + threadIdx.x;
     const int k = c < num_cols ? hot_class(counts_then_rank[c]) : -1;
     s_cls[threadIdx.x] = (unsigned char) (k < 0 ? 255 : k);
     if (k >= 0) atomicAdd(&s_n[k], 1u);
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(HC_BLOCK) void hot_rank_kernel(unsigned *__restrict
         for (int t = 0; t < (int) threadIdx.x; ++t) before += s_cls[t] == (unsigned char) k ? 1u : 0u;
         const unsigned r = s_base[k] + before;
         counts_then_rank[c] = r;
-        order[r] = c;
+        order[r] = (int) c;
     }
 }
 
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(HC_BLOCK) void hot_relabel_kernel(const int *__rest
 template <typename V>
 __global__ __launch_bounds__(HC_BLOCK) void hot_permute_x_kernel(const V *__restrict__ x, const int *__restrict__ order, V *__restrict__ xp, int num_cols)
 {
-    const int k = blockIdx.x * HC_BLOCK + threadIdx.x;
+    const long long k = (long long) blockIdx.x * HC_BLOCK + threadIdx.x;
     if (k < num_cols) xp[k] = x[order[k]];
 }
 
@@ -160,7 +160,7 @@ int hot_build(void *d_plan, size_t plan_bytes, const int32_t *d_row_offsets, con
     HC_HIP(hipMemsetAsync(counts, 0, (size_t) std::max(cols, 1) * 4, stream));
     HC_HIP(hipMemsetAsync(cls, 0, (size_t) 3 * CLASSES * 4, stream));
     if (cols == 0) return hipSuccess;
-    const unsigned cgrid = (unsigned) ((cols + HC_BLOCK - 1) / HC_BLOCK);
+    const unsigned cgrid = (unsigned) (((long long) cols + HC_BLOCK - 1) / HC_BLOCK);
     const unsigned ngrid = (unsigned) std::min<long long>(((long long) nnz + HC_BLOCK - 1) / HC_BLOCK, 1 << 16);
     if (nnz > 0) {
         hipLaunchKernelGGL(hot_count_kernel, dim3(ngrid), dim3(HC_BLOCK), 0, stream, d_cols, (long long) nnz, counts, cols);
@@ -194,7 +194,7 @@ int hot_permute(const void *d_plan, size_t plan_bytes, const V *d_x, V *d_out, i
     if (!make_layout(rows, cols, nnz, (int) sizeof(V), L) || plan_bytes < L.total || (reinterpret_cast<uintptr_t>(d_plan) & 15)) return hipErrorInvalidValue;
     if (cols == 0) return hipSuccess;
     if (!d_x || !d_out || d_x == d_out) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned) ((cols + HC_BLOCK - 1) / HC_BLOCK);
+    const unsigned grid = (unsigned) (((long long) cols + HC_BLOCK - 1) / HC_BLOCK);
     hipLaunchKernelGGL((hot_permute_x_kernel<V>), dim3(grid), dim3(HC_BLOCK), 0, stream, d_x, reinterpret_cast<const int *>(static_cast<const char *>(d_plan) + L.order_off), d_out, cols);
     return launched(stream, debug_sync, "hot_permute_x_kernel", grid);
 }
@@ -211,7 +211,7 @@ int hot_apply(void *d_plan, size_t plan_bytes, const V *d_values, const int32_t 
     char *base = static_cast<char *>(d_plan);
     const V *xp = x_is_permuted ? d_x : reinterpret_cast<const V *>(base + L.xp_off);
     if (cols > 0 && nnz > 0 && !x_is_permuted) {
-        const unsigned grid = (unsigned) ((cols + HC_BLOCK - 1) / HC_BLOCK);
+        const unsigned grid = (unsigned) (((long long) cols + HC_BLOCK - 1) / HC_BLOCK);
         hipLaunchKernelGGL((hot_permute_x_kernel<V>), dim3(grid), dim3(HC_BLOCK), 0, stream, d_x, reinterpret_cast<const int *>(base + L.order_off), reinterpret_cast<V *>(base + L.xp_off), cols);
         if (int e = launched(stream, debug_sync, "hot_permute_x_kernel", grid)) return e;
     }
