@@ -333,7 +333,8 @@ int mspmv_get_launch_info_cols(int32_t rows, int32_t cols, int32_t nnz, int32_t 
  * They correspond to d_tile_coordinates / d_tile_carry_pairs of
  * dispatch_spmv_orig.cuh:643-646 and are what the parity tests pin against
  * the oracle.  Any output pointer may be NULL.  (Laid out as mspmv_get_launch_info says: not for the calls that pick their
- * tile shape by the column count, mspmv_get_launch_info_cols.) */
+ * tile shape by the column count, mspmv_get_launch_info_cols.)  After a call that took the skinny layout this describes a region that
+ * call did not write: read that call's regions at the offsets of mspmv_get_launch_info_cols instead. */
 int mspmv_debug_read_tiles(const void *d_temp, int32_t rows, int32_t nnz,
                            int32_t value_bytes, int32_t *h_coords,
                            int32_t *h_carry_keys, void *h_carry_values,
@@ -367,7 +368,8 @@ int mspmv_get_band_passes(int32_t rows, int32_t cols, int32_t nnz, int32_t value
  * band (a power of two: 1 MiB of x, widened until 32 bands cover it). */
 int mspmv_get_clocked_bands(int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t *bands, int32_t *band_cols);
 /* The 64 window verdicts (1 = columns look uniformly spread) the last automatic call left in d_temp -> HOST
- * array of 64 int32 (synchronises `stream`); at least 56 ones select the band passes. */
+ * array of 64 int32 (synchronises `stream`); at least 56 ones select the band passes.  After a call that took the skinny layout this
+ * describes a region that call did not write (use the offsets of mspmv_get_launch_info_cols instead). */
 int mspmv_debug_band_windows(const void *d_temp, int32_t rows, int32_t nnz, int32_t value_bytes,
                              int32_t *h_verdicts, mspmv_stream_t stream);
 

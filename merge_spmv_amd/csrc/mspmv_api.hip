@@ -14,6 +14,7 @@
 #include <cstring>
 #include <mutex>
 #include <random>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mspmv.h"
@@ -207,34 +208,44 @@ static Layout make_layout(int rows, int nnz, int value_bytes, const Tune &tune, 
     return L;
 }
 
-// What the column-band policy is derived from: the L2 a gather can hit in -- one XCD's, as the runtime reports it -- and
-// how many of them the device has; queried once per device (never on the hot path again).  Dev library only: MSPMV_FAKE_L2_MIB /
-// MSPMV_FAKE_XCDS in the environment override the query (read once: tests of the policy).
-struct DeviceCaches { long long l2_bytes; int xcds; };
-static DeviceCaches device_caches()
+// What the dispatcher knows about the current device, queried once per device (never on the hot path again):
+//  * what the column-band policy is derived from: the L2 a gather can hit in -- one XCD's, as the runtime reports it -- and how many
+//    of them the device has.  Dev library only: MSPMV_FAKE_L2_MIB / MSPMV_FAKE_XCDS in the environment override the query (read once:
+//    tests of the policy);
+//  * its CU count;
+//  * ticks per microsecond of the counter s_memrealtime reads (hipDeviceAttributeWallClockRate, kHz; 100 MHz on MI300 / MI355X): the
+//    slots of the clock-scheduled column bands are lengths of time, not tick counts.
+// `slot` indexes the per-device caches kept elsewhere (resident_blocks).
+struct DeviceInfo { long long l2_bytes; int xcds, cus, slot; double ticks_per_us; };
+static DeviceInfo device_info()
 {
     // (lock-free after the first call per device: this sits on the path of every large-problem call.  Two threads racing through
     //  the first call compute the same values.)
     static std::atomic<long long> cached_l2[64];
-    static std::atomic<int> cached_xcds[64];
+    static std::atomic<int> cached_xcds[64], cached_cus[64], cached_khz[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void) hipGetLastError(); dev = 0; }
-    DeviceCaches c; c.l2_bytes = cached_l2[dev].load(std::memory_order_acquire); c.xcds = cached_xcds[dev].load(std::memory_order_relaxed);
+    DeviceInfo c; c.slot = dev; c.l2_bytes = cached_l2[dev].load(std::memory_order_acquire);
     if (c.l2_bytes == 0) {
-        c.l2_bytes = 4LL << 20; c.xcds = 8;                                      // MI355X in SPX mode: 8 XCDs x 4 MiB
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeNumberOfXccs, dev) == hipSuccess && v > 0) c.xcds = v; else (void) hipGetLastError();
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeL2CacheSize, dev) == hipSuccess && v > 0) {
-            // (the runtime reports one XCD's L2 on this part; a figure of 16 MiB or more can only be an aggregate)
-            c.l2_bytes = v >= (16 << 20) && c.xcds > 1 ? (long long) v / c.xcds : (long long) v;
-        } else (void) hipGetLastError();
+        int attr[4] = {8, 4 << 20, 256, 100000};                                 // MI355X in SPX mode: 8 XCDs x 4 MiB, 256 CUs, a 100 MHz wall clock
+        const hipDeviceAttribute_t which[4] = {hipDeviceAttributeNumberOfXccs, hipDeviceAttributeL2CacheSize, hipDeviceAttributeMultiprocessorCount, hipDeviceAttributeWallClockRate};
+        for (int i = 0; i < 4; ++i) {
+            int v = 0;
+            if (hipDeviceGetAttribute(&v, which[i], dev) == hipSuccess && v > 0) attr[i] = v; else (void) hipGetLastError();
+        }
+        // (the runtime reports one XCD's L2 on this part; a figure of 16 MiB or more can only be an aggregate)
+        c.l2_bytes = attr[1] >= (16 << 20) && attr[0] > 1 ? (long long) attr[1] / attr[0] : (long long) attr[1];
 #ifdef MSPMV_TUNING
         if (const char *e = getenv("MSPMV_FAKE_L2_MIB")) { const double m = atof(e); if (m > 0) c.l2_bytes = (long long) (m * 1048576.0); }
-        if (const char *e = getenv("MSPMV_FAKE_XCDS")) { const int n = atoi(e); if (n > 0) c.xcds = n; }
+        if (const char *e = getenv("MSPMV_FAKE_XCDS")) { const int n = atoi(e); if (n > 0) attr[0] = n; }
 #endif
-        cached_xcds[dev].store(c.xcds, std::memory_order_relaxed);
+        cached_xcds[dev].store(attr[0], std::memory_order_relaxed);
+        cached_cus[dev].store(attr[2], std::memory_order_relaxed);
+        cached_khz[dev].store(attr[3], std::memory_order_relaxed);
         cached_l2[dev].store(c.l2_bytes, std::memory_order_release);
     }
+    c.xcds = cached_xcds[dev].load(std::memory_order_relaxed); c.cus = cached_cus[dev].load(std::memory_order_relaxed);
+    c.ticks_per_us = cached_khz[dev].load(std::memory_order_relaxed) * 1e-3;
     return c;
 }
 
@@ -259,7 +270,7 @@ static DeviceCaches device_caches()
 // columns are in fact spread is decided on the device.  Below 256 MB of stream the passes use ordinary loads like the
 // one-sweep kernel (the matrix then stays in the Infinity Cache from pass to pass: 24 M uniformly spread nonzeros over
 // 7.6 / 11.4 MiB of x: 242 -> 174 us, 301 -> 214 us).
-static int band_passes_for(const Layout &L, long long x_bytes, int value_bytes, int rows, int nnz, const CallExtra &ex, int *force)
+static int band_passes_for(const Layout &L, long long x_bytes, int value_bytes, int rows, int nnz, unsigned long long stream_bytes, const CallExtra &ex, int *force)
 {
     *force = 0;
     if (ex.no_bands || ex.tile_map != 0 || !band_shape(L.shape.block, L.shape.ipt, value_bytes)) return 0;
@@ -268,8 +279,7 @@ static int band_passes_for(const Layout &L, long long x_bytes, int value_bytes, 
     if (policy < 0) return 0;
     if (policy >= 2) { *force = 1; return x_bytes / value_bytes >= policy ? policy : 0; }
     if ((long long) nnz < 8LL * rows) return 0;
-    const DeviceCaches dc = device_caches();
-    const unsigned long long stream_bytes = (unsigned long long) nnz * (value_bytes + 4) + 4ull * rows;
+    const DeviceInfo dc = device_info();
     if (stream_bytes < 5ull * (unsigned long long) dc.xcds * (unsigned long long) dc.l2_bytes) return 0;
     const double r = (double) x_bytes / (double) dc.l2_bytes;
     // (The clock-scheduled one-pass form that serves the offered calls since round 6, mspmv_tdm.hpp, would still win beyond 10 / 9 L2 --
@@ -289,35 +299,6 @@ static int tdm_shift_for(long long cols, int value_bytes, int band_passes, const
     while (shift < TDM_SLOT_SHIFT && ((cols + (1LL << shift) - 1) >> shift) > TDM_MAX_BANDS) ++shift;
     if (((cols + (1LL << shift) - 1) >> shift) > TDM_MAX_BANDS || shift > TDM_SLOT_SHIFT) return 0;
     return shift;
-}
-
-// CU count of the current device, queried once per device (never on the hot path again).
-static int device_cus()
-{
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int v = cached[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cached[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-
-// ticks per microsecond of the counter s_memrealtime reads (hipDeviceAttributeWallClockRate, kHz; 100 MHz on MI300 / MI355X), queried
-// once per device: the slots of the clock-scheduled column bands are lengths of time, not tick counts
-static double device_wall_clock_ticks_per_us()
-{
-    static std::atomic<int> cached[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 100.0;
-    int khz = cached[dev].load(std::memory_order_relaxed);
-    if (khz == 0) {
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) { (void) hipGetLastError(); khz = 100000; }
-        cached[dev].store(khz, std::memory_order_relaxed);
-    }
-    return khz * 1e-3;
 }
 
 // opt-in per-kernel event timing (mspmv_profile_begin/_end).  Process-global and meant for ONE
@@ -378,22 +359,39 @@ static hipError_t after_launch(hipStream_t stream, int debug_sync, const char *n
     return e;
 }
 
-// Resident blocks of a kernel on the current device (blocks per CU from the occupancy calculator x CUs), computed once per
-// kernel instantiation and device: what bounds the waits between workgroups of the one-launch kernels.
+// Blocks of a kernel one CU holds at once: what the occupancy calculator says (at most 2048 threads' worth), `fallback` if it
+// cannot say; asked once per `cache`, i.e. once per kernel instantiation.
 template <typename K>
-static int resident_blocks(K kernel, int block, std::atomic<int> (&cache)[64])
+static int blocks_per_cu(K kernel, int block, int fallback, std::atomic<int> &cache)
 {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    int v = cache[dev].load(std::memory_order_relaxed);
+    int v = cache.load(std::memory_order_relaxed);
     if (v == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, 0) != hipSuccess || n < 1) { (void) hipGetLastError(); n = 2; }
-        v = std::min(n, 2048 / block) * device_cus();
-        cache[dev].store(v, std::memory_order_relaxed);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, 0) != hipSuccess || n < 1) { (void) hipGetLastError(); n = fallback; }
+        v = std::min(n, 2048 / block);
+        cache.store(v, std::memory_order_relaxed);
     }
     return v;
 }
+// Resident blocks of a kernel on the current device (blocks per CU x CUs), computed once per kernel instantiation and device:
+// what bounds the waits between workgroups of the one-launch kernels.
+template <typename K>
+static int resident_blocks(K kernel, int block, std::atomic<int> (&cache)[64])
+{
+    const DeviceInfo di = device_info();
+    return blocks_per_cu(kernel, block, 2, cache[di.slot]) * di.cus;
+}
+// Runtime bools -> template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a generic
+// lambda can name the kernel instantiation its flags select.  Every combination of the bools is instantiated, none else.
+template <typename F>
+static inline auto with_bools(F &&f) { return f(); }
+template <typename F, typename... Rest>
+static inline auto with_bools(F &&f, bool first, Rest... rest)
+{
+    if (first) return with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+    return with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+static inline BandArgs no_bands() { return BandArgs{nullptr, nullptr, nullptr, 0, 0, 0, 0, TdmArgs{0, 0, 0.f, 0}}; }
 // Largest run length 2^k (<= the wanted one) of the XCD-chunked block -> tile mapping under which a tile that waits for a
 // lower-numbered TILE's record always finds that tile's block dispatched: inside a group of 8 * 2^k blocks a predecessor
 // can sit on a block up to 8 * 2^k - 1 later, and workgroups are dispatched in order, so one group must fit the resident
@@ -424,313 +422,385 @@ static bool launch_dev_variant(const Layout &L, const Params<V> &p, bool axpby, 
     const bool remap = !axpby && (L.flags & 1) != 0;
     const int ablate = axpby ? 0 : (L.flags >> 16) & 7;
     if (!(tpb_flag || forced || remap || ablate)) return false;
-#define MSPMV_LAUNCH_P(...)                                                                                        \
-    do {                                                                                                   \
-        auto kernel = tile_kernel_vec<V, BLOCK, IPT, __VA_ARGS__>;                                          \
-        static std::atomic<int> resident{0};      /* one per kernel variant */                              \
-        int per_cu = forced ? forced : resident.load(std::memory_order_relaxed);                            \
-        if (per_cu == 0) {                                                                                 \
-            int n = 0;                                                                                     \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, BLOCK, 0) != hipSuccess || n < 1) n = 4; \
-            per_cu = std::min(n, 2048 / BLOCK);                                                            \
-            resident.store(per_cu, std::memory_order_relaxed);                                             \
-        }                                                                                                  \
-        long long want = (long long) per_cu * device_cus();                                                \
-        if (!forced) want = std::max<long long>(want, (L.num_tiles + tpb - 1) / tpb);                      \
-        const unsigned pgrid = (unsigned) std::min<long long>(L.num_tiles, want);                          \
-        hipLaunchKernelGGL(kernel, dim3(pgrid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), stream, p, coords, carries, L.num_tiles, chunk_log2, BandArgs{nullptr, nullptr, nullptr, 0, 0, 0, 0, TdmArgs{0, 0, 0.f, 0}});   \
-    } while (0)
-    if (ablate == 1) MSPMV_LAUNCH_P(false, false, true, 1, true);
-    else if (ablate == 6) MSPMV_LAUNCH_P(false, false, true, 6, true);
-    else if (ablate == 7) MSPMV_LAUNCH_P(false, false, true, 7, true);
-    else if (remap) { if (nt) MSPMV_LAUNCH_P(false, true, true, 0, true); else MSPMV_LAUNCH_P(false, true, false, 0, true); }
-    else if (axpby) { if (nt) MSPMV_LAUNCH_P(true, false, true, 0, true); else MSPMV_LAUNCH_P(true, false, false, 0, true); }
-    else if (nt) MSPMV_LAUNCH_P(false, false, true, 0, true);
-    else MSPMV_LAUNCH_P(false, false, false, 0, true);
-#undef MSPMV_LAUNCH_P
+    auto launch = [&](auto ax, auto rm, auto ntf, auto abl) {
+        auto kernel = tile_kernel_vec<V, BLOCK, IPT, ax.value, rm.value, ntf.value, abl.value, true>;
+        static std::atomic<int> resident{0};      /* one per kernel variant */
+        const int per_cu = forced ? forced : blocks_per_cu(kernel, BLOCK, 4, resident);
+        long long want = (long long) per_cu * device_info().cus;
+        if (!forced) want = std::max<long long>(want, (L.num_tiles + tpb - 1) / tpb);
+        const unsigned pgrid = (unsigned) std::min<long long>(L.num_tiles, want);
+        hipLaunchKernelGGL(kernel, dim3(pgrid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), stream, p, coords, carries, L.num_tiles, chunk_log2, no_bands());
+    };
+    constexpr std::false_type no{}; constexpr std::true_type yes{};
+    if (ablate == 1) launch(no, no, yes, std::integral_constant<int, 1>{});
+    else if (ablate == 6) launch(no, no, yes, std::integral_constant<int, 6>{});
+    else if (ablate == 7) launch(no, no, yes, std::integral_constant<int, 7>{});
+    else if (remap) with_bools([&](auto ntf) { launch(no, yes, ntf, std::integral_constant<int, 0>{}); }, nt);
+    else with_bools([&](auto ax, auto ntf) { launch(ax, no, ntf, std::integral_constant<int, 0>{}); }, axpby, nt);
     return true;
 }
 #endif
 
-template <typename V, int BLOCK, int IPT>
-static hipError_t run_shape(const Layout &L, void *d_temp, const Params<V> &p, bool axpby, hipStream_t stream,
-                            int debug_sync, const CallExtra &ex)
+// LARGE fp64 MATRICES OF SHORT ROWS OVER A TINY x (the reference's --dense=<cols> inputs: cpu_spmv.cpp:581-587 is --dense=5, BASELINE config 1's
+// matrix) take the SMALL tile shape behind the compact front end at any size that still streams with ordinary loads (<= 256 MB): every
+// tile of such a matrix is a closed lean tile, and the fast lane's 234 instructions per wave beat the large shape's general kernel --
+// --dense=5 at full size (16.8 M nonzeros, 11 235 tiles instead of 7 150) 35.8 -> 34.1 us per call (rocSPARSE: 35.5), 5-point grids of
+// 16 M nonzeros 39.8 -> 39.3 (tools/compact_other_matrices.py, profiles/r05_compact_other_matrices.txt).  Judged on what the host knows:
+// 8-byte values, the default tuning, a size that would take the large shape, x within the 4 KB that otherwise go to LDS, at most 8
+// nonzeros per row on average.  (Matrices with long rows among the short ones lose in the small shape's general body at these sizes --
+// R-MAT, 3400 tiles: +6...16 % -- and the host cannot tell them from grids unless x is tiny: a row over x of <= 512 entries is short.)
+// Rows of closed lean tiles are summed left to right whatever the tile shape: their y does not change by a bit; a long row among them is
+// associated as the shape's tiles cut it, like under any other choice of shape (tools/fuzz.py compares against the general kernel of the shape run).
+static bool skinny_rule(int rows, int cols, int nnz, int value_bytes, const Tune &t, const Layout &L, unsigned long long stream_bytes)
 {
-    char *base = static_cast<char *>(d_temp);
-    Coord *coords = reinterpret_cast<Coord *>(base + L.coords_off);
-    Carry<V> *carries = reinterpret_cast<Carry<V> *>(base + L.carries_off);
-    const int tile_items = BLOCK * IPT;
-    int phase = ex.phase;
+    return value_bytes == 8 && t.block == 0 && t.flags == 0 && t.compact_tiles == 0 && compact_max_tiles(8) > 0 && L.snap && L.shape.ipt != COMPACT_IPT &&
+           cols > 0 && (size_t) cols * 8u <= (size_t) X_LDS_MAX_BYTES && (long long) nnz <= 8LL * rows &&
+           stream_bytes <= (256ull << 20);      // (the dispatcher's `nt` threshold: ordinary loads)
+}
 
+// ---- ONE RESOLVED DESCRIPTION OF A CALL ----
+// Everything about a CsrMV call that is a function of its sizes, the caller's request (CallExtra), the temp storage offered and the
+// alignment of the arrays: decided once, by resolve_call, and read by the launches (run_shape and its stages), the size query and the
+// introspection entry points alike.
+enum { COORDS_SEARCH, COORDS_INTERP, COORDS_SCATTER };      // how the coordinate pass finds the tile boundaries
+constexpr int COLS_UNKNOWN = -1;       // resolve_call without a column count (mspmv_get_launch_info, the debug readers, csrmv_temp_bytes)
+struct CallPlan {
+    Layout L;                    // the layout that runs ...
+    uint64_t base;               // ... and where it starts in temp storage: 0, or the default layout's size for the skinny layout behind it
+    uint64_t query_bytes;        // what a size query answers
+    int phase;
+    bool skinny;                 // the small tile shape for a large fp64 matrix of short rows over a tiny x (skinny_rule)
+    bool vec;                    // 16-byte streams: tile_kernel_snap / tile_kernel_vec; else the dword-per-lane tile_kernel
+    bool nt;                     // CSR streams through non-temporal loads
+    bool one_launch;             // tile_kernel_snap alone; else the classic coordinate pass | tiles | fix-up
+    bool compact;                // ... behind its compact front end, for at most compact_cap tiles
+    int compact_cap;
+    unsigned long long stream_bytes;     // the CSR arrays, read once per SpMV
+    int x_lds;                   // > 0: x has this many entries and is gathered from LDS
+    int num_cols, band_passes, band_cols, band_force;    // column-band passes (band_passes_for): > 1 = the BAND variant of tile_kernel_vec may serve the call
+    int tdm_shift, tdm_bands;    // > 0: the clock-scheduled one-pass form serves the call when the windows say "spread" (mspmv_tdm.hpp)
+    int tdm_lookahead; double tdm_slot_scale;
+    int tile_map, chunk_log2;    // the caller's block -> tile map (CallExtra), and the map of the classic tile launch (the one launch bounds its run length: safe_chunk_log2)
+    int coords;                  // COORDS_*
+    int max_polls, lean_avg;     // of the one-launch kernel: LookBack::max_polls, consume_tile_rows
+};
+
+static CallPlan resolve_call(int rows, int cols, int nnz, int value_bytes, const CallExtra &ex, uint64_t temp_offered, bool aligned)
+{
+    const Tune &t = ex.tune;
+    CallPlan pl;
+    pl.phase = ex.phase; pl.tile_map = ex.tile_map; pl.num_cols = cols;
+    pl.stream_bytes = (unsigned long long) nnz * (value_bytes + 4) + 4ull * rows;
+    pl.L = make_layout(rows, nnz, value_bytes, t);
+    pl.base = 0; pl.query_bytes = pl.L.total; pl.skinny = false;
     // 16-byte streaming needs 16-byte aligned array bases (hipMalloc gives 256) and at
     // least one full 4-element chunk in each array
-    const bool vec = !(L.flags & MSPMV_TUNE_NO_VEC) && p.nnz >= 4 && p.rows >= 3 &&
-                     ((reinterpret_cast<uintptr_t>(p.values) | reinterpret_cast<uintptr_t>(p.cols) |
-                       reinterpret_cast<uintptr_t>(p.row_end - 1)) & 15) == 0;
-    // a profiler slot is taken only by calls that run all the passes it brackets
-    const int slot = phase == PHASE_COORDS_ONLY ? -1 : prof_take_slot();
+    const bool streams16 = aligned && nnz >= 4 && rows >= 3;
+    // (without a column count: the default layout, and a size large enough for the small shape if the rule holds for SOME column count)
+    if (ex.allow_skinny && skinny_rule(rows, cols == COLS_UNKNOWN ? 1 : cols, nnz, value_bytes, t, pl.L, pl.stream_bytes)) {
+        // The small-shape layout lives BEHIND the default one in temp storage, so a call that takes it never touches the default
+        // layout's coordinates (what mspmv_csrmv_prepare stored, what the classic pipeline of a prepared call trusts): the size query
+        // asks for both; a caller that sized its storage without the column count (mspmv_get_launch_info) and brings less runs the
+        // default shape.  Taken only when the arrays are 16-byte aligned, i.e. when the ONE-LAUNCH kernel will run (its hints are
+        // verified, whatever the region held before).
+        const Layout S = make_layout(rows, nnz, value_bytes, t, true);
+        pl.query_bytes = pl.L.total + S.total;
+        if (cols != COLS_UNKNOWN && temp_offered >= pl.query_bytes && streams16 && S.snap) { pl.base = pl.L.total; pl.L = S; pl.skinny = true; }
+    }
+    const Layout &L = pl.L;
+    pl.vec = streams16 && !(L.flags & MSPMV_TUNE_NO_VEC);
+    // CSR streams: ordinary loads while the matrix fits the 256 MB Infinity Cache (it then stays there
+    // between the SpMVs of a solver: 214 MB dense5 fp64 0.039 vs 0.053 ms, 208 MB grid2d 0.0438 vs
+    // 0.0447), non-temporal loads beyond (they keep x in L2: C2 -2 %, band5 -7 %, C4 -14 %, dense32 -7 %;
+    // only the 0.7-1.1 GB grids prefer ordinary loads, by 2-5 %; profiles/r02_stream_policy.txt)
+    pl.nt = (L.flags & MSPMV_TUNE_FORCE_NT) || (!(L.flags & MSPMV_TUNE_FORCE_TEMPORAL) && pl.stream_bytes > (256ull << 20));
+    // a tiny x is gathered from LDS by the vectorised tile kernels (dynamic shared memory of the launch)
+    pl.x_lds = (cols > 0 && (size_t) cols * (size_t) value_bytes <= (size_t) X_LDS_MAX_BYTES && !(L.flags & MSPMV_TUNE_NO_XLDS)) ? cols : 0;
+    pl.band_passes = band_passes_for(L, (long long) cols * value_bytes, value_bytes, rows, nnz, pl.stream_bytes, ex, &pl.band_force);
+    pl.band_cols = pl.band_passes > 1 ? (cols + pl.band_passes - 1) / pl.band_passes : 0;
+    pl.tdm_shift = tdm_shift_for(cols, value_bytes, pl.band_passes, ex);
+    pl.tdm_bands = pl.tdm_shift > 0 ? (int) (((long long) cols + (1LL << pl.tdm_shift) - 1) >> pl.tdm_shift) : 0;
+    pl.tdm_lookahead = t.tdm_lookahead > 0 ? t.tdm_lookahead - 1 : std::max(1, pl.tdm_bands / 8);      // (an eighth of x ahead of the clock: 1 of 12 bands, 3 of 24)
+    pl.tdm_slot_scale = t.tdm_slot_permille > 0 ? t.tdm_slot_permille * 1e-3 : 1.0;
     // (the band-major plan's contiguous tile ranges, ex.tile_map: through the one-launch kernel in fp64 -- C2 plan 0.669 -> 0.640 ms --,
     //  through the classic launches in fp32, where the one-launch form measured 3 % slower: 0.508 -> 0.523)
-    if (L.snap && vec && (ex.tile_map == 0 || sizeof(V) == 8) && ex.band_passes <= 1) {
-        // ---- ONE launch: row-snapped tiles on verified coordinate hints (tile_kernel_snap) ----
-        int *rstart = reinterpret_cast<int *>(base + L.rstart_off);
-        if (phase == PHASE_COORDS_ONLY) {
-            // mspmv_csrmv_prepare: fill in the hints (what the first call would otherwise find tile by tile)
-            BoundaryOut bo; bo.coords = coords; bo.rstart = rstart;
-            const bool interp = (L.flags & MSPMV_TUNE_INTERP_COORDS) || (!(L.flags & MSPMV_TUNE_SCATTER_COORDS) && p.rows >= INTERP_MIN_ROWS);
-            const unsigned cgrid = interp ? (unsigned) ((L.num_tiles + 1 + SEARCH_BLOCK - 1) / SEARCH_BLOCK)
-                                          : (unsigned) ((((long long) p.rows + 1 + 3) / 4 + SEARCH_BLOCK - 1) / SEARCH_BLOCK);
-            if (interp) hipLaunchKernelGGL((coords_interp_kernel<SEARCH_BLOCK>), dim3(cgrid), dim3(SEARCH_BLOCK), 0, stream, p.row_end, p.rows, p.nnz, tile_items, L.num_tiles, bo);
-            else hipLaunchKernelGGL((coords_scatter_kernel<SEARCH_BLOCK, BLOCK * IPT, true>), dim3(cgrid), dim3(SEARCH_BLOCK), 0, stream, p.row_end - 1, p.rows, p.nnz, L.num_tiles, bo, BandDetectArgs{});
-            return after_launch(stream, debug_sync, interp ? "coords_interp_kernel" : "coords_scatter_kernel", cgrid, SEARCH_BLOCK);
+    pl.one_launch = L.snap && pl.vec && (ex.tile_map == 0 || value_bytes == 8) && pl.band_passes <= 1;
+    // small problems (compact_max_tiles), and the skinny layout whatever its tile count: the one-launch kernel behind its compact front
+    // end (kernels: compact_front) -- bit for bit the same y
+    pl.compact_cap = pl.skinny ? 0x7fffffff : t.compact_tiles > 0 ? t.compact_tiles : t.compact_tiles < 0 ? 0 : compact_max_tiles(value_bytes);
+    pl.compact = L.shape.block == COMPACT_BLOCK && L.shape.ipt == COMPACT_IPT && !pl.nt && ex.tile_map == 0 && L.num_tiles > 1 && L.num_tiles <= pl.compact_cap &&
+                 (unsigned long long) cols * value_bytes < (1ull << 32) && (unsigned long long) nnz * value_bytes < (1ull << 32) &&
+                 (unsigned long long) rows * 4ull < (1ull << 32) - 8;      // (32-bit byte offsets in the fast lane: every array < 4 GB)
+    // XCD-chunked block -> tile mapping: runs of 2^6 consecutive tiles per XCD.  Measured against
+    // plain round-robin: grid2d -19 %, C4 -7 %, dense32 -5 %, band5 -3 %, nothing slower (16 and
+    // 256 are within 1-2 % of 64).  Tuning bits 24-27: 0 = default, 15 = off, else log2 of the
+    // run length.  Prepared band-major plans ask for one contiguous tile range per XCD instead.
+    const int chunk_flag = (L.flags >> 24) & 0xf;
+    pl.chunk_log2 = ex.tile_map ? ex.tile_map : chunk_flag == 0 ? 6 : chunk_flag == 15 ? 0 : chunk_flag;
+    // from 10 M rows up: one thread per boundary, interpolation search (latency-bound: <= 17 us whatever the row
+    // count, 2-8 us on regular matrices) instead of reading all of row_offsets (20-23 us at 16.8 M rows)
+    pl.coords = (L.flags & MSPMV_TUNE_BINARY_SEARCH) ? COORDS_SEARCH
+              : (L.flags & MSPMV_TUNE_INTERP_COORDS) || (!(L.flags & MSPMV_TUNE_SCATTER_COORDS) && rows >= INTERP_MIN_ROWS) ? COORDS_INTERP : COORDS_SCATTER;
+    pl.max_polls = t.record_polls > 0 ? t.record_polls : t.record_polls < 0 ? 0 : REC_MAX_POLLS;
+    pl.lean_avg = (L.flags & MSPMV_TUNE_NO_LEAN) ? 0 : lean_avg_default();
+    return pl;
+}
+
+// ---- THE STAGES OF A CALL (run_shape puts them together) ----
+// what they share: the resolved plan, the kernels' parameters, and the call's regions of temp storage (`base` = where the layout starts)
+template <typename V> struct Stage {
+    const CallPlan &pl; const Params<V> &p;
+    char *base; Coord *coords; Carry<V> *carries; int *rstart;
+    bool axpby; hipStream_t stream; int debug_sync;
+};
+
+// Tile boundary coordinates (also the row start of every boundary: a later prepared call may run tile_kernel_snap on them) --
+// the first of the classic launches, and all that mspmv_csrmv_prepare runs.  `band`: the call is a candidate for column bands, so
+// 64 sampled windows of column indices decide, on the device, whether the tile kernel (its BAND variant) runs its ordinary body or
+// the bands.
+template <typename V, int BLOCK, int IPT>
+static hipError_t coords_stage(const Stage<V> &c, bool band, const BandDetectArgs &da)
+{
+    const CallPlan &pl = c.pl; const Params<V> &p = c.p; const int num_tiles = pl.L.num_tiles;
+    BoundaryOut bo; bo.coords = c.coords; bo.rstart = c.rstart;
+    bool band_sampled = false;
+    if (pl.phase == PHASE_SKIP_COORDS) {
+        // already in d_temp
+    } else if (pl.coords == COORDS_SEARCH) {
+        const unsigned grid = (unsigned) ((num_tiles + 1 + (SEARCH_BLOCK / WAVE) - 1) / (SEARCH_BLOCK / WAVE));
+        hipLaunchKernelGGL((search_kernel<SEARCH_BLOCK>), dim3(grid), dim3(SEARCH_BLOCK), 0, c.stream, p.row_end, p.rows,
+                           p.nnz, BLOCK * IPT, num_tiles, bo);
+        MSPMV_CHECK(after_launch(c.stream, c.debug_sync, "search_kernel", grid, SEARCH_BLOCK));
+    } else if (pl.coords == COORDS_INTERP) {
+        const unsigned grid = (unsigned) ((num_tiles + 1 + SEARCH_BLOCK - 1) / SEARCH_BLOCK);
+        hipLaunchKernelGGL((coords_interp_kernel<SEARCH_BLOCK>), dim3(grid), dim3(SEARCH_BLOCK), 0, c.stream, p.row_end, p.rows, p.nnz,
+                           BLOCK * IPT, num_tiles, bo);
+        MSPMV_CHECK(after_launch(c.stream, c.debug_sync, "coords_interp_kernel", grid, SEARCH_BLOCK));
+    } else {
+        const long long threads = ((long long) p.rows + 1 + 3) / 4;       // 4 row indices per thread
+        // + BAND_WINDOWS blocks that sample the column windows: no launch of their own
+        const unsigned grid = (unsigned) ((threads + SEARCH_BLOCK - 1) / SEARCH_BLOCK) + (band ? BAND_WINDOWS : 0);
+        const int *row_offsets = p.row_end - 1;
+        with_bools([&](auto aligned, auto sample) {
+            hipLaunchKernelGGL((coords_scatter_kernel<SEARCH_BLOCK, BLOCK * IPT, aligned.value, sample.value>), dim3(grid), dim3(SEARCH_BLOCK), 0,
+                               c.stream, row_offsets, p.rows, p.nnz, num_tiles, bo, da);
+        }, (reinterpret_cast<uintptr_t>(row_offsets) & 15) == 0, band);
+        band_sampled = band;
+        MSPMV_CHECK(after_launch(c.stream, c.debug_sync, "coords_scatter_kernel", grid, SEARCH_BLOCK));
+    }
+    if (band && !band_sampled && pl.phase != PHASE_COORDS_ONLY) {             // (prepared calls, the other coordinate passes)
+        hipLaunchKernelGGL((band_detect_kernel<SEARCH_BLOCK>), dim3(BAND_WINDOWS), dim3(SEARCH_BLOCK), 0, c.stream, da);
+        MSPMV_CHECK(after_launch(c.stream, c.debug_sync, "band_detect_kernel", BAND_WINDOWS, SEARCH_BLOCK));
+    }
+    return hipSuccess;
+}
+
+// ---- ONE launch: row-snapped tiles on verified coordinate hints (tile_kernel_snap) ----
+template <typename V, int BLOCK, int IPT>
+static hipError_t one_launch_stage(const Stage<V> &c)
+{
+    const CallPlan &pl = c.pl; const Params<V> &p = c.p; const Layout &L = pl.L;
+    const unsigned long long tag = next_call_tag();
+    LookBack lb; lb.rec = reinterpret_cast<unsigned long long *>(c.base + L.pub_off);
+    lb.tag_a = (unsigned) (tag >> 32) | 1u; lb.tag_b = (unsigned) tag; lb.error = reinterpret_cast<int *>(c.base + L.err_off);
+    lb.group_base = L.num_tiles;
+    lb.call_tag = lb.tag_a; lb.max_polls = pl.max_polls;
+    const unsigned grid = (unsigned) L.num_tiles;
+    // (every launch below is ONE call into the HIP runtime -- launch_exact: hipLaunchKernel with its status -- and the compact
+    //  variant needs nothing else from it: the reference's timing loop is bound by the enqueueing thread for small problems)
+    hipError_t launched = hipSuccess;
+    bool compact = false;
+    if constexpr (BLOCK == COMPACT_BLOCK && IPT == COMPACT_IPT) {
+        compact = pl.compact;
+        if (compact) {
+            // (a tiny x is gathered from memory here, not from an LDS copy: the copy pays on matrices that stream from HBM, a problem of
+            //  this size has x in its caches anyway -- 3.5 -> 2.8 us per call on a 900-row grid -- and the result is the same
+            //  bit for bit, tests/test_gpu_parity.py::test_tiny_x_is_gathered_from_lds)
+            Params<V> pc = p; pc.x_lds = 0;
+            launched = launch_snap_compact<V>(c.axpby, grid, 0, c.stream, c.coords, c.rstart, L.num_tiles, pc, c.carries, lb, pl.lean_avg, compact_tile_map());
         }
+    }
+    if (!compact) {
+        static std::atomic<int> snap_cache[64];
+        // (pl.tile_map: the band-major plan's one contiguous tile range per XCD -- inside a range a lower-numbered tile sits on an
+        //  earlier block of the same XCD, so a tile that waits for records waits for blocks dispatched before it -- EXCEPT the first
+        //  tiles of XCD k's range, which wait for the LAST tiles of XCD k - 1's range: few waiters, a bounded poll, then the sum
+        //  recomputed from the matrix; correct, and slow only for a row longer than HEAD_MAX that crosses a range boundary)
+        // (dev library: MSPMV_SNAP_MAP in the environment, read once: 30 = one contiguous tile range per XCD for every one-launch call, 0 .. 8 = that run length)
+        static const int env_map = env_int("MSPMV_SNAP_MAP", -1);
+        const int chunk_log2 = pl.tile_map ? pl.tile_map : env_map == TILE_MAP_CONTIGUOUS_CODE ? env_map
+                             : safe_chunk_log2(env_map >= 0 && env_map <= 8 ? env_map : pl.chunk_log2, resident_blocks(tile_kernel_snap<V, BLOCK, IPT, true, true>, BLOCK, snap_cache));
+        launched = with_bools([&](auto ax, auto ntf) {
+            return launch_exact(tile_kernel_snap<V, BLOCK, IPT, ax.value, ntf.value>, dim3(grid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), c.stream,
+                                c.coords, c.rstart, L.num_tiles, chunk_log2, p, c.carries, lb, pl.lean_avg);
+        }, c.axpby, pl.nt);
+    }
+    MSPMV_CHECK(launched);
+    if (c.debug_sync) MSPMV_CHECK(after_launch(c.stream, c.debug_sync, compact ? "tile_kernel_snap (compact front end)" : "tile_kernel_snap", grid, BLOCK, lb.error, lb.tag_a));
+    return hipSuccess;
+}
+
+// Band set-up of a classic call that is a candidate for column bands (plan: band_passes > 1): which blocks of the tile launch run
+// them, and the slot of the clock-scheduled form.  grid == 0 (no_bands): the call runs without.
+template <typename V, int BLOCK, int IPT>
+static BandArgs band_setup(const Stage<V> &c)
+{
+    BandArgs ba = no_bands();
+    if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V))) {
+        const CallPlan &pl = c.pl; const Params<V> &p = c.p; const Layout &L = pl.L;
+        if (!pl.vec || pl.band_passes <= 1 || pl.phase == PHASE_COORDS_ONLY) return ba;
+        // the passes are run by 4 (fp64: 5) blocks per CU, or as many as are resident at once if that is fewer: the gathers
+        // of a pass hit L2, so the passes are not short of waves in flight, and with all 8 slots of a CU taken the
+        // ~35 000 blocks of the launch that only return would queue up behind the work instead of draining beside it
+        // (C2 fp32, blocks per CU 8 / 6 / 4 / 3: 0.857 / 0.842 / 0.832 / 0.843 ms; fp64, 5 / 4.4 / 3.1 / 2.5: 1.297 / 1.296 / 1.36 / 1.50)
+        static std::atomic<int> resident{0};
+        const int band_resident_per_cu = blocks_per_cu(tile_kernel_vec<V, BLOCK, IPT, true, false, true, 0, false, true>, BLOCK, 4, resident);
+        const DeviceInfo di = device_info();
+        const int band_per_cu = std::min(band_resident_per_cu, sizeof(V) == 4 ? 4 : 5);
+        long long want = std::min<long long>(L.num_tiles, (long long) band_per_cu * di.cus);
+        if (want >= 8) want &= ~7LL;                                   // (8 interleaved tile sequences, one per XCD)
+        if (want < 8 && want != L.num_tiles) return ba;
+        // the BAND variant: the same kernel, whose first band_grid blocks run the column-band passes instead
+        // when the verdicts (or mspmv_set_band_passes) say so
+        int *band_verdict = reinterpret_cast<int *>(c.base + L.band_off);
+        ba.verdict = band_verdict; ba.counters = band_verdict + BAND_WINDOWS; ba.grid = (int) want;
+        ba.next = reinterpret_cast<int *>(c.base + L.band_next_off);
+        ba.bands = pl.band_passes; ba.band_cols = pl.band_cols; ba.force = pl.band_force;
+        if (pl.tdm_shift > 0) {
+            // clock-scheduled column bands instead of the passes (mspmv_tdm.hpp): every block of the launch stages its one tile
+            // band by band.  Blocks resident per CU: what the kernel's occupancy says (LDS, registers).
+            const int per_cu = std::max(1, (int) std::min<long long>((L.num_tiles + di.cus - 1) / di.cus, band_resident_per_cu));
+            ba.tdm.band_shift = pl.tdm_shift; ba.tdm.bands = pl.tdm_bands;
+            ba.tdm.lookahead = pl.tdm_lookahead;
+            // A band stays on air for as long as the resident blocks need for their gathers of it at the L2 gather rate
+            // (1.02 G gathers/s per CU: 262 G/s over 256 CUs, profiles/r02_hw_ceilings.txt) and a sixth more -- or, if
+            // that is longer, for as long as every XCD needs to fetch the band over the fabric (7.8 TB/s for all of them):
+            // C2 fp32 2.13 us (12 bands of 1 MiB, 8 blocks per CU), fp64 1.08 us (24 bands, 5 blocks per CU); both
+            // constants read off sweeps of the slot length (tools/tdm_check.py sweep: the minimum is sharp, +-10 % of the
+            // slot cost 3-5 % -- a block that misses a band's slot waits for the next rotation).  In ticks of the wall clock (10 ns here).
+            // (a tile's BLOCK * IPT path items are nonzeros and row ends: rows of 8 leave 2503 gathers per tile, and the optimum moves with them)
+            const double nz_share = (double) p.nnz / ((double) p.nnz + (double) p.rows);
+            const double gather_us = 1.16 * nz_share * (double) per_cu * BLOCK * IPT / pl.tdm_bands / 1.02e3;
+            const double fabric_us = (double) sizeof(V) * (double) (1u << pl.tdm_shift) * di.xcds / 7.8e6;
+            const double ticks = std::max(8.0, std::max(gather_us, fabric_us) * di.ticks_per_us * pl.tdm_slot_scale);
+            ba.tdm.inv_slot = (float) (1.0 / ticks);
+        }
+    }
+    return ba;
+}
+
+// The classic tile launch: tile_kernel_vec (plain; its BAND variant when band_setup found blocks for the bands, TDM: the clocked
+// form), or the dword-per-lane tile_kernel for arrays that cannot be streamed 16 bytes at a time.
+template <typename V, int BLOCK, int IPT>
+static hipError_t classic_tiles_stage(const Stage<V> &c, const BandArgs &ba)
+{
+    const CallPlan &pl = c.pl; const Params<V> &p = c.p; const Layout &L = pl.L;
+    const unsigned grid = (unsigned) L.num_tiles;
+    if (!pl.vec) {
+        with_bools([&](auto ax) {
+            hipLaunchKernelGGL((tile_kernel<V, BLOCK, IPT, ax.value>), dim3(grid), dim3(BLOCK), 0, c.stream, p, c.coords, c.carries, L.num_tiles);
+        }, c.axpby);
+        return after_launch(c.stream, c.debug_sync, "tile_kernel", grid, BLOCK);
+    }
+    // One tile per block: the hardware's block scheduler balances the load and de-phases the
+    // blocks of a CU.  (A persistent, software-prefetching form of the same kernel exists in
+    // the -DMSPMV_DEV build; with the flag/segmented-scan reduction it measured 7-10 % slower
+    // on streaming matrices)
+    const size_t xl = (size_t) p.x_lds * sizeof(V);
+    bool launched = false;
+#ifdef MSPMV_DEV
+    launched = launch_dev_variant<V, BLOCK, IPT>(L, p, c.axpby, pl.nt, c.coords, c.carries, pl.chunk_log2, c.stream);
+#endif
+    if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V))) {
+        if (ba.grid > 0 && !launched) {
+            with_bools([&](auto ax, auto ntf, auto td) {
+                hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, ax.value, false, ntf.value, 0, false, true, td.value>), dim3(grid), dim3(BLOCK), xl, c.stream,
+                                   p, c.coords, c.carries, L.num_tiles, pl.chunk_log2, ba);
+            }, c.axpby, pl.nt, pl.tdm_shift > 0);
+            launched = true;
+        }
+    }
+    if (!launched)
+        with_bools([&](auto ax, auto ntf) {
+            hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, ax.value, false, ntf.value, 0, false>), dim3(grid), dim3(BLOCK), xl, c.stream,
+                               p, c.coords, c.carries, L.num_tiles, pl.chunk_log2, ba);
+        }, c.axpby, pl.nt);
+    return after_launch(c.stream, c.debug_sync, "tile_kernel_vec", grid, BLOCK);
+}
+
+// Carry fix-up (not needed for a single tile: its carry is the (rows, 0) pair; nor when the self-searching
+// tiles of a small problem have added the carries themselves)
+template <typename V>
+static hipError_t fixup_stage(const Stage<V> &c)
+{
+    const Params<V> &p = c.p; const Layout &L = c.pl.L;
+    if (L.num_tiles <= 1) return hipSuccess;
+    if (L.flags & MSPMV_TUNE_ATOMIC_FIX) {
+        const unsigned grid = (unsigned) ((L.num_tiles + FIX_BLOCK - 1) / FIX_BLOCK);
+        hipLaunchKernelGGL((fixup_atomic_kernel<V, FIX_BLOCK>), dim3(grid), dim3(FIX_BLOCK), 0, c.stream, c.carries,
+                           L.num_tiles, p.y, p.rows, p.alpha);
+        return after_launch(c.stream, c.debug_sync, "fixup_atomic_kernel", grid, FIX_BLOCK);
+    }
+    if (!(L.flags & MSPMV_TUNE_MULTILEVEL_FIX)) {
+        const unsigned grid = (unsigned) ((L.num_tiles + FIX_CHUNK - 1) / FIX_CHUNK);
+        hipLaunchKernelGGL((fixup_onepass_kernel<V, FIX_BLOCK, FIX_IPT>), dim3(grid), dim3(FIX_BLOCK), 0, c.stream, c.carries,
+                           L.num_tiles, p.y, p.rows, p.alpha);
+        return after_launch(c.stream, c.debug_sync, "fixup_onepass_kernel", grid, FIX_BLOCK);
+    }
+    const Carry<V> *in = c.carries;
+    for (int lvl = 0; lvl < L.fix_levels; ++lvl) {
+        const int n = L.fix_n[lvl];
+        const unsigned grid = (unsigned) ((n + FIX_CHUNK - 1) / FIX_CHUNK);
+        Carry<V> *out = grid > 1 ? reinterpret_cast<Carry<V> *>(c.base + L.fix_off[lvl]) : nullptr;
+        hipLaunchKernelGGL((fixup_kernel<V, FIX_BLOCK, FIX_IPT>), dim3(grid), dim3(FIX_BLOCK), 0, c.stream, in, n,
+                           out, p.y, p.rows, p.alpha);
+        MSPMV_CHECK(after_launch(c.stream, c.debug_sync, "fixup_kernel", grid, FIX_BLOCK));
+        in = out;
+    }
+    return hipSuccess;
+}
+
+// One call in tile shape BLOCK x IPT: the one launch, or the classic three; the profiler's marks bracket search | tiles | fix-up
+template <typename V, int BLOCK, int IPT>
+static hipError_t run_shape(const CallPlan &pl, char *base, const Params<V> &p, bool axpby, hipStream_t stream, int debug_sync)
+{
+    const Layout &L = pl.L;
+    const Stage<V> c{pl, p, base, reinterpret_cast<Coord *>(base + L.coords_off), reinterpret_cast<Carry<V> *>(base + L.carries_off),
+                     reinterpret_cast<int *>(base + L.rstart_off), axpby, stream, debug_sync};
+    // a profiler slot is taken only by calls that run all the passes it brackets
+    const int slot = pl.phase == PHASE_COORDS_ONLY ? -1 : prof_take_slot();
+    if (pl.one_launch) {
+        // mspmv_csrmv_prepare: fill in the hints (what the first call would otherwise find tile by tile)
+        if (pl.phase == PHASE_COORDS_ONLY) return coords_stage<V, BLOCK, IPT>(c, false, BandDetectArgs{});
         prof_mark(stream, slot, 0);
         prof_mark(stream, slot, 1);
-        const unsigned long long tag = next_call_tag();
-        LookBack lb; lb.rec = reinterpret_cast<unsigned long long *>(base + L.pub_off);
-        lb.tag_a = (unsigned) (tag >> 32) | 1u; lb.tag_b = (unsigned) tag; lb.error = reinterpret_cast<int *>(base + L.err_off);
-        lb.group_base = L.num_tiles;
-        lb.call_tag = lb.tag_a; lb.max_polls = ex.tune.record_polls > 0 ? ex.tune.record_polls : ex.tune.record_polls < 0 ? 0 : REC_MAX_POLLS;
-        const unsigned long long stream_bytes = (unsigned long long) p.nnz * (sizeof(V) + 4) + 4ull * p.rows;
-        const bool nt = (L.flags & MSPMV_TUNE_FORCE_NT) || (!(L.flags & MSPMV_TUNE_FORCE_TEMPORAL) && stream_bytes > (256ull << 20));
-        const unsigned grid = (unsigned) L.num_tiles;
-        const size_t xl = (size_t) p.x_lds * sizeof(V);
-        const int lean_avg = (L.flags & MSPMV_TUNE_NO_LEAN) ? 0 : lean_avg_default();
-        // (every launch below is ONE call into the HIP runtime -- launch_exact: hipLaunchKernel with its status -- and the compact
-        //  variant needs nothing else from it: the reference's timing loop is bound by the enqueueing thread for small problems)
-        hipError_t launched = hipSuccess;
-        // small problems (compact_max_tiles): the same kernel behind its compact front end (kernels: compact_front) -- bit for bit the same y
-        bool compact = false;
-        if constexpr (BLOCK == COMPACT_BLOCK && IPT == COMPACT_IPT) {
-            compact = !nt && ex.tile_map == 0 && L.num_tiles > 1 && L.num_tiles <= (ex.tune.compact_tiles > 0 ? ex.tune.compact_tiles : ex.tune.compact_tiles < 0 ? 0 : compact_max_tiles((int) sizeof(V))) &&
-                      (unsigned long long) ex.num_cols * sizeof(V) < (1ull << 32) && (unsigned long long) p.nnz * sizeof(V) < (1ull << 32) &&
-                      (unsigned long long) p.rows * 4ull < (1ull << 32) - 8;      // (32-bit byte offsets in the fast lane: every array < 4 GB)
-            if (compact) {
-                // (a tiny x is gathered from memory here, not from an LDS copy: the copy pays on matrices that stream from HBM, a problem of
-                //  this size has x in its caches anyway -- 3.5 -> 2.8 us per call on a 900-row grid -- and the result is the same
-                //  bit for bit, tests/test_gpu_parity.py::test_tiny_x_is_gathered_from_lds)
-                Params<V> pc = p; pc.x_lds = 0;
-                launched = launch_snap_compact<V>(axpby, grid, 0, stream, coords, rstart, L.num_tiles, pc, carries, lb, lean_avg, compact_tile_map());
-            }
-        }
-        if (!compact) {
-            static std::atomic<int> snap_cache[64];
-            const int chunk_flag = (L.flags >> 24) & 0xf;
-            const int wanted = chunk_flag == 0 ? 6 : chunk_flag == 15 ? 0 : chunk_flag;
-            // (ex.tile_map: the band-major plan's one contiguous tile range per XCD -- inside a range a lower-numbered tile sits on an
-            //  earlier block of the same XCD, so a tile that waits for records waits for blocks dispatched before it -- EXCEPT the first
-            //  tiles of XCD k's range, which wait for the LAST tiles of XCD k - 1's range: few waiters, a bounded poll, then the sum
-            //  recomputed from the matrix; correct, and slow only for a row longer than HEAD_MAX that crosses a range boundary)
-            // (dev library: MSPMV_SNAP_MAP in the environment, read once: 30 = one contiguous tile range per XCD for every one-launch call, 0 .. 8 = that run length)
-            static const int env_map = env_int("MSPMV_SNAP_MAP", -1);
-            const int chunk_log2 = ex.tile_map ? ex.tile_map : env_map == TILE_MAP_CONTIGUOUS_CODE ? env_map
-                                 : safe_chunk_log2(env_map >= 0 && env_map <= 8 ? env_map : wanted, resident_blocks(tile_kernel_snap<V, BLOCK, IPT, true, true>, BLOCK, snap_cache));
-#define MSPMV_LAUNCH_SNAP(AX, NTF) launched = launch_exact(tile_kernel_snap<V, BLOCK, IPT, AX, NTF>, dim3(grid), dim3(BLOCK), xl, stream, coords, rstart, L.num_tiles, chunk_log2, p, carries, lb, lean_avg)
-            if (axpby) { if (nt) MSPMV_LAUNCH_SNAP(true, true); else MSPMV_LAUNCH_SNAP(true, false); }
-            else if (nt) MSPMV_LAUNCH_SNAP(false, true);
-            else MSPMV_LAUNCH_SNAP(false, false);
-#undef MSPMV_LAUNCH_SNAP
-        }
-        MSPMV_CHECK(launched);
-        if (debug_sync) MSPMV_CHECK(after_launch(stream, debug_sync, compact ? "tile_kernel_snap (compact front end)" : "tile_kernel_snap", grid, BLOCK, lb.error, lb.tag_a));
+        MSPMV_CHECK((one_launch_stage<V, BLOCK, IPT>(c)));
         prof_mark(stream, slot, 2);
         prof_mark(stream, slot, 3);
         return hipSuccess;
-    } else {
-    // column-band passes (band_passes_for): 64 sampled windows of column indices decide, on the device, whether the
-    // tile kernel (its BAND variant) runs its ordinary body or the passes
-    bool band = false, band_sampled = false;
-    unsigned band_grid = 0;
-    int band_resident_per_cu = 4;
-    if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V))) {
-        if (vec && ex.band_passes > 1 && phase != PHASE_COORDS_ONLY) {
-            // the passes are run by 4 (fp64: 5) blocks per CU, or as many as are resident at once if that is fewer: the gathers
-            // of a pass hit L2, so the passes are not short of waves in flight, and with all 8 slots of a CU taken the
-            // ~35 000 blocks of the launch that only return would queue up behind the work instead of draining beside it
-            // (C2 fp32, blocks per CU 8 / 6 / 4 / 3: 0.857 / 0.842 / 0.832 / 0.843 ms; fp64, 5 / 4.4 / 3.1 / 2.5: 1.297 / 1.296 / 1.36 / 1.50)
-            static std::atomic<int> resident{0};
-            int per_cu = resident.load(std::memory_order_relaxed);
-            if (per_cu == 0) {
-                int n = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, tile_kernel_vec<V, BLOCK, IPT, true, false, true, 0, false, true>, BLOCK, 0) != hipSuccess || n < 1) { (void) hipGetLastError(); n = 4; }
-                per_cu = std::min(n, 2048 / BLOCK);
-                resident.store(per_cu, std::memory_order_relaxed);
-            }
-            band_resident_per_cu = per_cu;
-            const int band_per_cu = std::min(per_cu, sizeof(V) == 4 ? 4 : 5);
-            long long want = std::min<long long>(L.num_tiles, (long long) band_per_cu * device_cus());
-            if (want >= 8) want &= ~7LL;                                   // (8 interleaved tile sequences, one per XCD)
-            band_grid = (unsigned) want;
-            band = want >= 8 || want == L.num_tiles;
-        }
     }
-    int *band_verdict = reinterpret_cast<int *>(base + L.band_off);
-    BandDetectArgs da; da.cols = p.cols; da.nnz = p.nnz; da.num_cols = ex.num_cols; da.line_shift = sizeof(V) == 4 ? 5 : 4;
-    da.verdict = band_verdict;
-    // 1. tile boundary coordinates (also the row start of every boundary: a later prepared call may run tile_kernel_snap on them)
-    BoundaryOut bo; bo.coords = coords; bo.rstart = reinterpret_cast<int *>(base + L.rstart_off);
+    const BandArgs ba = band_setup<V, BLOCK, IPT>(c);
+    BandDetectArgs da; da.cols = p.cols; da.nnz = p.nnz; da.num_cols = pl.num_cols; da.line_shift = sizeof(V) == 4 ? 5 : 4;
+    da.verdict = reinterpret_cast<int *>(base + L.band_off);
     prof_mark(stream, slot, 0);
-    if (phase == PHASE_SKIP_COORDS) {
-        // already in d_temp
-    } else if (L.flags & MSPMV_TUNE_BINARY_SEARCH) {
-        const unsigned grid = (unsigned) ((L.num_tiles + 1 + (SEARCH_BLOCK / WAVE) - 1) / (SEARCH_BLOCK / WAVE));
-        hipLaunchKernelGGL((search_kernel<SEARCH_BLOCK>), dim3(grid), dim3(SEARCH_BLOCK), 0, stream, p.row_end, p.rows,
-                           p.nnz, tile_items, L.num_tiles, bo);
-        MSPMV_CHECK(after_launch(stream, debug_sync, "search_kernel", grid, SEARCH_BLOCK));
-    } else if ((L.flags & MSPMV_TUNE_INTERP_COORDS) || (!(L.flags & MSPMV_TUNE_SCATTER_COORDS) && p.rows >= INTERP_MIN_ROWS)) {
-        // from 10 M rows up: one thread per boundary, interpolation search (latency-bound: <= 17 us whatever the row
-        // count, 2-8 us on regular matrices) instead of reading all of row_offsets (20-23 us at 16.8 M rows)
-        const unsigned grid = (unsigned) ((L.num_tiles + 1 + SEARCH_BLOCK - 1) / SEARCH_BLOCK);
-        hipLaunchKernelGGL((coords_interp_kernel<SEARCH_BLOCK>), dim3(grid), dim3(SEARCH_BLOCK), 0, stream, p.row_end, p.rows, p.nnz,
-                           tile_items, L.num_tiles, bo);
-        MSPMV_CHECK(after_launch(stream, debug_sync, "coords_interp_kernel", grid, SEARCH_BLOCK));
-    } else {
-        const long long threads = ((long long) p.rows + 1 + 3) / 4;       // 4 row indices per thread
-        const unsigned grid = (unsigned) ((threads + SEARCH_BLOCK - 1) / SEARCH_BLOCK);
-        const int *row_offsets = p.row_end - 1;
-        const bool aligned = (reinterpret_cast<uintptr_t>(row_offsets) & 15) == 0;
-        if (band) {
-            // + BAND_WINDOWS blocks that sample the column windows: no launch of their own
-            const unsigned dgrid = grid + BAND_WINDOWS;
-            if (aligned) hipLaunchKernelGGL((coords_scatter_kernel<SEARCH_BLOCK, BLOCK * IPT, true, true>), dim3(dgrid), dim3(SEARCH_BLOCK), 0,
-                                            stream, row_offsets, p.rows, p.nnz, L.num_tiles, bo, da);
-            else hipLaunchKernelGGL((coords_scatter_kernel<SEARCH_BLOCK, BLOCK * IPT, false, true>), dim3(dgrid), dim3(SEARCH_BLOCK), 0,
-                                    stream, row_offsets, p.rows, p.nnz, L.num_tiles, bo, da);
-            band_sampled = true;
-        } else if (aligned)
-            hipLaunchKernelGGL((coords_scatter_kernel<SEARCH_BLOCK, BLOCK * IPT, true>), dim3(grid), dim3(SEARCH_BLOCK), 0,
-                               stream, row_offsets, p.rows, p.nnz, L.num_tiles, bo, da);
-        else
-            hipLaunchKernelGGL((coords_scatter_kernel<SEARCH_BLOCK, BLOCK * IPT, false>), dim3(grid), dim3(SEARCH_BLOCK), 0,
-                               stream, row_offsets, p.rows, p.nnz, L.num_tiles, bo, da);
-        MSPMV_CHECK(after_launch(stream, debug_sync, "coords_scatter_kernel", band ? grid + BAND_WINDOWS : grid, SEARCH_BLOCK));
-    }
-    if (phase == PHASE_COORDS_ONLY) return hipSuccess;
-    if (band && !band_sampled) {             // (prepared calls, the other coordinate passes)
-        hipLaunchKernelGGL((band_detect_kernel<SEARCH_BLOCK>), dim3(BAND_WINDOWS), dim3(SEARCH_BLOCK), 0, stream, da);
-        MSPMV_CHECK(after_launch(stream, debug_sync, "band_detect_kernel", BAND_WINDOWS, SEARCH_BLOCK));
-    }
-    // 2. tiles
+    MSPMV_CHECK((coords_stage<V, BLOCK, IPT>(c, ba.grid > 0, da)));
+    if (pl.phase == PHASE_COORDS_ONLY) return hipSuccess;
     prof_mark(stream, slot, 1);
-    {
-        const unsigned grid = (unsigned) L.num_tiles;
-        if (vec) {
-            // One tile per block: the hardware's block scheduler balances the load and de-phases the
-            // blocks of a CU.  (A persistent, software-prefetching form of the same kernel exists in
-            // the -DMSPMV_DEV build; with the flag/segmented-scan reduction it measured 7-10 % slower
-            // on streaming matrices)
-            // XCD-chunked block -> tile mapping: runs of 2^6 consecutive tiles per XCD.  Measured against
-            // plain round-robin: grid2d -19 %, C4 -7 %, dense32 -5 %, band5 -3 %, nothing slower (16 and
-            // 256 are within 1-2 % of 64).  Tuning bits 24-27: 0 = default, 15 = off, else log2 of the
-            // run length.  Prepared band-major plans ask for one contiguous tile range per XCD instead.
-            const int chunk_flag = (L.flags >> 24) & 0xf;
-            const int chunk_log2 = ex.tile_map ? ex.tile_map : chunk_flag == 0 ? 6 : chunk_flag == 15 ? 0 : chunk_flag;
-            // CSR streams: ordinary loads while the matrix fits the 256 MB Infinity Cache (it then stays there
-            // between the SpMVs of a solver: 214 MB dense5 fp64 0.039 vs 0.053 ms, 208 MB grid2d 0.0438 vs
-            // 0.0447), non-temporal loads beyond (they keep x in L2: C2 -2 %, band5 -7 %, C4 -14 %, dense32 -7 %;
-            // only the 0.7-1.1 GB grids prefer ordinary loads, by 2-5 %; profiles/r02_stream_policy.txt)
-            const unsigned long long stream_bytes = (unsigned long long) p.nnz * (sizeof(V) + 4) + 4ull * p.rows;
-            const bool nt = (L.flags & MSPMV_TUNE_FORCE_NT) || (!(L.flags & MSPMV_TUNE_FORCE_TEMPORAL) && stream_bytes > (256ull << 20));
-            bool launched = false;
-#ifdef MSPMV_DEV
-            launched = launch_dev_variant<V, BLOCK, IPT>(L, p, axpby, nt, coords, carries, chunk_log2, stream);
-#endif
-            BandArgs ba; ba.verdict = nullptr; ba.counters = nullptr; ba.next = nullptr; ba.grid = 0; ba.bands = 0; ba.band_cols = 0; ba.force = 0; ba.tdm = TdmArgs{0, 0, 0.f, 0};
-            if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V))) {
-                if (band && !launched) {
-                    // the BAND variant: the same kernel, whose first band_grid blocks run the column-band passes instead
-                    // when the verdicts (or mspmv_set_band_passes) say so
-                    ba.verdict = band_verdict; ba.counters = band_verdict + BAND_WINDOWS; ba.grid = (int) band_grid;
-                    ba.next = reinterpret_cast<int *>(base + L.band_next_off);
-                    ba.bands = ex.band_passes; ba.band_cols = ex.band_cols; ba.force = ex.band_force;
-                    if (ex.tdm_shift > 0) {
-                        // clock-scheduled column bands instead of the passes (mspmv_tdm.hpp): every block of the launch stages its one tile
-                        // band by band.  Blocks resident per CU: what the kernel's occupancy says (LDS, registers).
-                        const int per_cu = std::max(1, (int) std::min<long long>((L.num_tiles + device_cus() - 1) / device_cus(), band_resident_per_cu));
-                        ba.tdm.band_shift = ex.tdm_shift; ba.tdm.bands = ex.tdm_bands;
-                        ba.tdm.lookahead = ex.tune.tdm_lookahead > 0 ? ex.tune.tdm_lookahead - 1 : std::max(1, ex.tdm_bands / 8);      // (an eighth of x ahead of the clock: 1 of 12 bands, 3 of 24)
-                        // A band stays on air for as long as the resident blocks need for their gathers of it at the L2 gather rate
-                        // (1.02 G gathers/s per CU: 262 G/s over 256 CUs, profiles/r02_hw_ceilings.txt) and a sixth more -- or, if
-                        // that is longer, for as long as every XCD needs to fetch the band over the fabric (7.8 TB/s for all of them):
-                        // C2 fp32 2.13 us (12 bands of 1 MiB, 8 blocks per CU), fp64 1.08 us (24 bands, 5 blocks per CU); both
-                        // constants read off sweeps of the slot length (tools/tdm_check.py sweep: the minimum is sharp, +-10 % of the
-                        // slot cost 3-5 % -- a block that misses a band's slot waits for the next rotation).  In ticks of the wall clock (10 ns here).
-                        // (a tile's BLOCK * IPT path items are nonzeros and row ends: rows of 8 leave 2503 gathers per tile, and the optimum moves with them)
-                        const double nz_share = (double) p.nnz / ((double) p.nnz + (double) p.rows);
-                        const double gather_us = 1.16 * nz_share * (double) per_cu * BLOCK * IPT / ex.tdm_bands / 1.02e3;
-                        const double fabric_us = (double) sizeof(V) * (double) (1u << ex.tdm_shift) * device_caches().xcds / 7.8e6;
-                        const double ticks = std::max(8.0, std::max(gather_us, fabric_us) * device_wall_clock_ticks_per_us() * (ex.tune.tdm_slot_permille > 0 ? ex.tune.tdm_slot_permille * 1e-3 : 1.0));
-                        ba.tdm.inv_slot = (float) (1.0 / ticks);
-                    }
-#define MSPMV_LAUNCH_BAND(AX, NTF, TD) hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, AX, false, NTF, 0, false, true, TD>), dim3(grid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), stream, p, coords, carries, L.num_tiles, chunk_log2, ba)
-                    if (ex.tdm_shift > 0) {
-                        if (axpby) { if (nt) MSPMV_LAUNCH_BAND(true, true, true); else MSPMV_LAUNCH_BAND(true, false, true); }
-                        else if (nt) MSPMV_LAUNCH_BAND(false, true, true);
-                        else MSPMV_LAUNCH_BAND(false, false, true);
-                    } else {
-                        if (axpby) { if (nt) MSPMV_LAUNCH_BAND(true, true, false); else MSPMV_LAUNCH_BAND(true, false, false); }
-                        else if (nt) MSPMV_LAUNCH_BAND(false, true, false);
-                        else MSPMV_LAUNCH_BAND(false, false, false);
-                    }
-#undef MSPMV_LAUNCH_BAND
-                    launched = true;
-                }
-            }
-#define MSPMV_LAUNCH(AX, NTF) hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, AX, false, NTF, 0, false>), dim3(grid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), stream, p, coords, carries, L.num_tiles, chunk_log2, ba)
-            if (!launched) {
-                if (axpby) { if (nt) MSPMV_LAUNCH(true, true); else MSPMV_LAUNCH(true, false); }
-                else if (nt) MSPMV_LAUNCH(false, true);
-                else MSPMV_LAUNCH(false, false);
-            }
-#undef MSPMV_LAUNCH
-        } else {
-            if (axpby) hipLaunchKernelGGL((tile_kernel<V, BLOCK, IPT, true>), dim3(grid), dim3(BLOCK), 0, stream, p, coords, carries, L.num_tiles);
-            else       hipLaunchKernelGGL((tile_kernel<V, BLOCK, IPT, false>), dim3(grid), dim3(BLOCK), 0, stream, p, coords, carries, L.num_tiles);
-        }
-        MSPMV_CHECK(after_launch(stream, debug_sync, vec ? "tile_kernel_vec" : "tile_kernel", grid, BLOCK));
-    }
-    }
-    // 3. carry fix-up (not needed for a single tile: its carry is the (rows, 0) pair; nor when the self-searching
-    //    tiles of a small problem have added the carries themselves)
+    MSPMV_CHECK((classic_tiles_stage<V, BLOCK, IPT>(c, ba)));
     prof_mark(stream, slot, 2);
-    if (L.num_tiles > 1) {
-        if (L.flags & MSPMV_TUNE_ATOMIC_FIX) {
-            const unsigned grid = (unsigned) ((L.num_tiles + FIX_BLOCK - 1) / FIX_BLOCK);
-            hipLaunchKernelGGL((fixup_atomic_kernel<V, FIX_BLOCK>), dim3(grid), dim3(FIX_BLOCK), 0, stream, carries,
-                               L.num_tiles, p.y, p.rows, p.alpha);
-            MSPMV_CHECK(after_launch(stream, debug_sync, "fixup_atomic_kernel", grid, FIX_BLOCK));
-        } else if (!(L.flags & MSPMV_TUNE_MULTILEVEL_FIX)) {
-            const unsigned grid = (unsigned) ((L.num_tiles + FIX_CHUNK - 1) / FIX_CHUNK);
-            hipLaunchKernelGGL((fixup_onepass_kernel<V, FIX_BLOCK, FIX_IPT>), dim3(grid), dim3(FIX_BLOCK), 0, stream, carries,
-                               L.num_tiles, p.y, p.rows, p.alpha);
-            MSPMV_CHECK(after_launch(stream, debug_sync, "fixup_onepass_kernel", grid, FIX_BLOCK));
-        } else {
-            const Carry<V> *in = carries;
-            for (int lvl = 0; lvl < L.fix_levels; ++lvl) {
-                const int n = L.fix_n[lvl];
-                const unsigned grid = (unsigned) ((n + FIX_CHUNK - 1) / FIX_CHUNK);
-                Carry<V> *out = grid > 1 ? reinterpret_cast<Carry<V> *>(base + L.fix_off[lvl]) : nullptr;
-                hipLaunchKernelGGL((fixup_kernel<V, FIX_BLOCK, FIX_IPT>), dim3(grid), dim3(FIX_BLOCK), 0, stream, in, n,
-                                   out, p.y, p.rows, p.alpha);
-                MSPMV_CHECK(after_launch(stream, debug_sync, "fixup_kernel", grid, FIX_BLOCK));
-                in = out;
-            }
-        }
-    }
+    MSPMV_CHECK(fixup_stage<V>(c));
     prof_mark(stream, slot, 3);
     return hipSuccess;
 }
 
 template <typename V>
-static hipError_t dispatch_shape(const Layout &L, void *d_temp, const Params<V> &p, bool axpby, hipStream_t stream,
-                                 int debug_sync, const CallExtra &ex);
+static hipError_t dispatch_shape(const CallPlan &pl, char *base, const Params<V> &p, bool axpby, hipStream_t stream, int debug_sync);
 
 #define MSPMV_SHAPE_CASE(V, B, I) \
-    if (L.shape.block == B && L.shape.ipt == I) return run_shape<V, B, I>(L, d_temp, p, axpby, stream, debug_sync, ex);
+    if (pl.L.shape.block == B && pl.L.shape.ipt == I) return run_shape<V, B, I>(pl, base, p, axpby, stream, debug_sync);
 
 template <>
-hipError_t dispatch_shape<float>(const Layout &L, void *d_temp, const Params<float> &p, bool axpby, hipStream_t stream,
-                                 int debug_sync, const CallExtra &ex)
+hipError_t dispatch_shape<float>(const CallPlan &pl, char *base, const Params<float> &p, bool axpby, hipStream_t stream, int debug_sync)
 {
     MSPMV_SHAPE_CASE(float, 256, 7)
     MSPMV_SHAPE_CASE(float, 256, 11)
@@ -745,8 +815,7 @@ hipError_t dispatch_shape<float>(const Layout &L, void *d_temp, const Params<flo
 }
 
 template <>
-hipError_t dispatch_shape<double>(const Layout &L, void *d_temp, const Params<double> &p, bool axpby,
-                                  hipStream_t stream, int debug_sync, const CallExtra &ex)
+hipError_t dispatch_shape<double>(const CallPlan &pl, char *base, const Params<double> &p, bool axpby, hipStream_t stream, int debug_sync)
 {
     MSPMV_SHAPE_CASE(double, 256, 7)
     MSPMV_SHAPE_CASE(double, 256, 11)
@@ -760,23 +829,6 @@ hipError_t dispatch_shape<double>(const Layout &L, void *d_temp, const Params<do
     return hipErrorInvalidValue;
 }
 
-// LARGE fp64 MATRICES OF SHORT ROWS OVER A TINY x (the reference's --dense=<cols> inputs: cpu_spmv.cpp:581-587 is --dense=5, BASELINE config 1's
-// matrix) take the SMALL tile shape behind the compact front end at any size that still streams with ordinary loads (<= 256 MB): every
-// tile of such a matrix is a closed lean tile, and the fast lane's 234 instructions per wave beat the large shape's general kernel --
-// --dense=5 at full size (16.8 M nonzeros, 11 235 tiles instead of 7 150) 35.8 -> 34.1 us per call (rocSPARSE: 35.5), 5-point grids of
-// 16 M nonzeros 39.8 -> 39.3 (tools/compact_other_matrices.py, profiles/r05_compact_other_matrices.txt).  Judged on what the host knows:
-// 8-byte values, the default tuning, a size that would take the large shape, x within the 4 KB that otherwise go to LDS, at most 8
-// nonzeros per row on average.  (Matrices with long rows among the short ones lose in the small shape's general body at these sizes --
-// R-MAT, 3400 tiles: +6...16 % -- and the host cannot tell them from grids unless x is tiny: a row over x of <= 512 entries is short.)
-// Rows of closed lean tiles are summed left to right whatever the tile shape: their y does not change by a bit; a long row among them is
-// associated as the shape's tiles cut it, like under any other choice of shape (tools/fuzz.py compares against the general kernel of the shape run).
-static bool skinny_rule(int rows, int cols, int nnz, int value_bytes, const Tune &t, const Layout &L)
-{
-    return value_bytes == 8 && t.block == 0 && t.flags == 0 && t.compact_tiles == 0 && compact_max_tiles(8) > 0 && L.snap && L.shape.ipt != COMPACT_IPT &&
-           cols > 0 && (size_t) cols * 8u <= (size_t) X_LDS_MAX_BYTES && (long long) nnz <= 8LL * rows &&
-           (unsigned long long) nnz * 12ull + 4ull * (unsigned long long) rows <= (256ull << 20);      // (the dispatcher's `nt` threshold: ordinary loads)
-}
-
 template <typename V>
 int csrmv_call(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_t *d_row_offsets, const int32_t *d_cols,
                const V *d_x, V *d_y, int32_t rows, int32_t cols, int32_t nnz, V alpha, V beta, bool axpby,
@@ -784,27 +836,13 @@ int csrmv_call(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_
 {
     if (!temp_bytes || rows < 0 || cols < 0 || nnz < 0) return hipErrorInvalidValue;
     if ((long long) rows + nnz > MAX_ITEMS) return hipErrorInvalidValue;
-    Layout L = make_layout(rows, nnz, (int) sizeof(V), ex.tune);
-    bool skinny = false;
-    if (ex.allow_skinny && skinny_rule(rows, cols, nnz, (int) sizeof(V), ex.tune, L)) {
-        // The small-shape layout lives BEHIND the default one in temp storage, so a call that takes it never touches the default
-        // layout's coordinates (what mspmv_csrmv_prepare stored, what the classic pipeline of a prepared call trusts): the size query
-        // asks for both; a caller that sized its storage without the column count (mspmv_get_launch_info) and brings less runs the
-        // default shape.  Taken only when the arrays are 16-byte aligned, i.e. when the ONE-LAUNCH kernel will run (its hints are
-        // verified, whatever the region held before).
-        const Layout S = make_layout(rows, nnz, (int) sizeof(V), ex.tune, true);
-        const uint64_t both = L.total + S.total;
-        if (d_temp == nullptr) { *temp_bytes = (size_t) both; return hipSuccess; }
-        const bool aligned = nnz >= 4 && rows >= 3 &&
-                             ((reinterpret_cast<uintptr_t>(d_values) | reinterpret_cast<uintptr_t>(d_cols) | reinterpret_cast<uintptr_t>(d_row_offsets) |
-                               reinterpret_cast<uintptr_t>(d_temp)) & 15) == 0;
-        if (*temp_bytes >= both && aligned && S.snap) { d_temp = static_cast<char *>(d_temp) + L.total; L = S; skinny = true; }
-    }
+    const bool aligned = ((reinterpret_cast<uintptr_t>(d_values) | reinterpret_cast<uintptr_t>(d_cols) | reinterpret_cast<uintptr_t>(d_row_offsets)) & 15) == 0;
+    const CallPlan pl = resolve_call(rows, cols, nnz, (int) sizeof(V), ex, d_temp ? (uint64_t) *temp_bytes : 0, aligned);
     if (d_temp == nullptr) {                      // size query (dispatch_spmv_orig.cuh:651-655)
-        *temp_bytes = (size_t) L.total;
+        *temp_bytes = (size_t) pl.query_bytes;
         return hipSuccess;
     }
-    if (!skinny && *temp_bytes < L.total) return hipErrorInvalidValue;   // util_device.cuh:90-93
+    if (!pl.skinny && *temp_bytes < pl.L.total) return hipErrorInvalidValue;   // util_device.cuh:90-93
     // (the temp storage holds 64-bit records updated atomically and is read with scalar loads: 16-byte alignment, which any
     //  device allocation has, is required rather than silently compensated for)
     if (reinterpret_cast<uintptr_t>(d_temp) & 15) return hipErrorInvalidValue;
@@ -814,24 +852,16 @@ int csrmv_call(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_
     Params<V> p;
     p.values = d_values; p.row_end = d_row_offsets + 1; p.cols = d_cols; p.x = d_x; p.y = d_y;
     p.rows = rows; p.nnz = nnz; p.alpha = alpha; p.beta = beta;
-    // a tiny x is gathered from LDS by the vectorised tile kernels (dynamic shared memory of the launch)
-    p.x_lds = (cols > 0 && (size_t) cols * sizeof(V) <= (size_t) X_LDS_MAX_BYTES && !(L.flags & MSPMV_TUNE_NO_XLDS)) ? cols : 0;
+    p.x_lds = pl.x_lds;
     p.band_lo = 0; p.band_len = 0; p.band_pass = 0;
-    CallExtra ex2 = ex;
-    if (skinny) ex2.tune.compact_tiles = 0x7fffffff;          // (the compact front end whatever the tile count)
-    ex2.band_passes = band_passes_for(L, (long long) cols * (long long) sizeof(V), (int) sizeof(V), rows, nnz, ex, &ex2.band_force);
-    ex2.band_cols = ex2.band_passes > 1 ? (cols + ex2.band_passes - 1) / ex2.band_passes : 0;
-    ex2.num_cols = cols;
-    ex2.tdm_shift = tdm_shift_for(cols, (int) sizeof(V), ex2.band_passes, ex);
-    ex2.tdm_bands = ex2.tdm_shift > 0 ? (int) (((long long) cols + (1LL << ex2.tdm_shift) - 1) >> ex2.tdm_shift) : 0;
-    return (int) dispatch_shape<V>(L, d_temp, p, axpby, stream, debug_sync, ex2);
+    return (int) dispatch_shape<V>(pl, static_cast<char *>(d_temp) + pl.base, p, axpby, stream, debug_sync);
 }
 template int csrmv_call<float>(void *, size_t *, const float *, const int32_t *, const int32_t *, const float *, float *, int32_t,
                                int32_t, int32_t, float, float, bool, hipStream_t, int, const CallExtra &);
 template int csrmv_call<double>(void *, size_t *, const double *, const int32_t *, const int32_t *, const double *, double *,
                                 int32_t, int32_t, int32_t, double, double, bool, hipStream_t, int, const CallExtra &);
 
-uint64_t csrmv_temp_bytes(int32_t rows, int32_t nnz, int32_t value_bytes) { return make_layout(rows, nnz, value_bytes, Tune{}).total; }
+uint64_t csrmv_temp_bytes(int32_t rows, int32_t nnz, int32_t value_bytes) { return resolve_call(rows, COLS_UNKNOWN, nnz, value_bytes, CallExtra{}, 0, true).query_bytes; }
 
 template <typename V>
 static int csrmv_impl(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_t *d_row_offsets,
@@ -948,16 +978,15 @@ static hipError_t run_mm_group(const MMLayout &L, char *base, MMParams<T> p, int
     const unsigned grid = (unsigned) num_tiles;
     constexpr int mm_chunk = MM_CHUNK_LOG2;
     if constexpr (LANE) {
-#define MSPMV_MM_LAUNCH(AX, NTF) hipLaunchKernelGGL((spmm_lane_kernel<T, K, mm_lane_vec<T, K>(), MM_LANE_BLOCK, 256 * MM_LANE_IPT / MM_LANE_BLOCK, AX, NTF>), dim3(grid), dim3(MM_LANE_BLOCK), 0, stream, p, coords, carries, num_tiles, groups, mm_chunk)
-        if (axpby) { if (nt) MSPMV_MM_LAUNCH(true, true); else MSPMV_MM_LAUNCH(true, false); }
-        else { if (nt) MSPMV_MM_LAUNCH(false, true); else MSPMV_MM_LAUNCH(false, false); }
-#undef MSPMV_MM_LAUNCH
+        with_bools([&](auto ax, auto ntf) {
+            hipLaunchKernelGGL((spmm_lane_kernel<T, K, mm_lane_vec<T, K>(), MM_LANE_BLOCK, 256 * MM_LANE_IPT / MM_LANE_BLOCK, ax.value, ntf.value>), dim3(grid), dim3(MM_LANE_BLOCK), 0, stream,
+                               p, coords, carries, num_tiles, groups, mm_chunk);
+        }, axpby, nt);
         MSPMV_CHECK(after_launch(stream, debug_sync, "spmm_lane_kernel", grid, MM_LANE_BLOCK));
     } else {
-#define MSPMV_MM_LAUNCH(AX, NTF) hipLaunchKernelGGL((spmm_tile_kernel<T, K, S::BLOCK, S::IPT, AX, NTF>), dim3(grid), dim3(S::BLOCK), 0, stream, p, coords, carries, num_tiles, groups, mm_chunk)
-        if (axpby) { if (nt) MSPMV_MM_LAUNCH(true, true); else MSPMV_MM_LAUNCH(true, false); }
-        else { if (nt) MSPMV_MM_LAUNCH(false, true); else MSPMV_MM_LAUNCH(false, false); }
-#undef MSPMV_MM_LAUNCH
+        with_bools([&](auto ax, auto ntf) {
+            hipLaunchKernelGGL((spmm_tile_kernel<T, K, S::BLOCK, S::IPT, ax.value, ntf.value>), dim3(grid), dim3(S::BLOCK), 0, stream, p, coords, carries, num_tiles, groups, mm_chunk);
+        }, axpby, nt);
         MSPMV_CHECK(after_launch(stream, debug_sync, "spmm_tile_kernel", grid, S::BLOCK));
     }
     if (num_tiles > 1) {
@@ -1145,25 +1174,26 @@ int mspmv_csrmm_f64(void *d_temp, size_t *temp_bytes, const double *d_values, co
                               alpha, beta, stream, debug_sync);
 }
 
+// what a call of this host thread resolves to when all that is known are its sizes (the aligned, vectorised path is assumed)
+static CallPlan resolve_sizes(int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, bool allow_skinny = false)
+{
+    CallExtra ex; ex.tune = thread_tune(value_bytes); ex.allow_skinny = allow_skinny;
+    return resolve_call(rows, cols, nnz, value_bytes, ex, ~uint64_t(0), true);
+}
+// the layout at the start of temp storage: what mspmv_csrmv_prepare fills and every call but one that took the skinny layout runs on
+static Layout default_layout(int32_t rows, int32_t nnz, int32_t value_bytes) { return resolve_sizes(rows, COLS_UNKNOWN, nnz, value_bytes).L; }
+
 static int launch_info_impl(int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, mspmv_launch_info_t *info)
 {
     if (!info || (value_bytes != 4 && value_bytes != 8) || rows < 0 || nnz < 0 ||
         (long long) rows + nnz > MAX_ITEMS)
         return hipErrorInvalidValue;
-    const Tune &tune = thread_tune(value_bytes);
-    Layout L = make_layout(rows, nnz, value_bytes, tune);
     // cols < 0 (mspmv_get_launch_info: the column count is not known): the default layout, with temp_bytes large enough for the small
     // shape a large fp64 matrix of short rows over a tiny x takes (skinny_rule) -- a buffer sized from here serves either;
     // cols >= 0 (mspmv_get_launch_info_cols): the layout a stateless call of exactly these sizes runs
-    uint64_t temp_bytes = L.total, base = 0;
-    if (cols < 0) {
-        if (skinny_rule(rows, 1, nnz, value_bytes, tune, L))      // (the rule holds for SOME column count)
-            temp_bytes = L.total + make_layout(rows, nnz, value_bytes, tune, true).total;
-    } else if (skinny_rule(rows, cols, nnz, value_bytes, tune, L)) {
-        base = L.total;                                           // (the small-shape layout sits behind the default one: csrmv_call)
-        L = make_layout(rows, nnz, value_bytes, tune, true);
-        temp_bytes = base + L.total;
-    }
+    const CallPlan pl = resolve_sizes(rows, cols < 0 ? COLS_UNKNOWN : cols, nnz, value_bytes, true);
+    const Layout &L = pl.L;
+    const uint64_t temp_bytes = pl.query_bytes, base = pl.base;
     memset(info, 0, sizeof(*info));
     info->block_threads = L.shape.block;
     info->items_per_thread = L.shape.ipt;
@@ -1190,7 +1220,7 @@ int mspmv_debug_read_tiles(const void *d_temp, int32_t rows, int32_t nnz, int32_
                            int32_t *h_carry_keys, void *h_carry_values, mspmv_stream_t stream_)
 {
     if (!d_temp || (value_bytes != 4 && value_bytes != 8) || rows < 0 || nnz < 0 || (long long) rows + nnz > MAX_ITEMS) return hipErrorInvalidValue;
-    const Layout L = make_layout(rows, nnz, value_bytes, thread_tune(value_bytes));
+    const Layout L = default_layout(rows, nnz, value_bytes);
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     MSPMV_CHECK(hipStreamSynchronize(stream));
     const char *base = static_cast<const char *>(d_temp);
@@ -1254,10 +1284,10 @@ int mspmv_set_tdm(int32_t value_bytes, int32_t policy, int32_t slot_permille, in
 
 int mspmv_get_device_caches(int64_t *l2_bytes_per_xcd, int32_t *xcds, int32_t *cus)
 {
-    const DeviceCaches dc = device_caches();
-    if (l2_bytes_per_xcd) *l2_bytes_per_xcd = dc.l2_bytes;
-    if (xcds) *xcds = dc.xcds;
-    if (cus) *cus = device_cus();
+    const DeviceInfo di = device_info();
+    if (l2_bytes_per_xcd) *l2_bytes_per_xcd = di.l2_bytes;
+    if (xcds) *xcds = di.xcds;
+    if (cus) *cus = di.cus;
     return hipSuccess;
 }
 
@@ -1291,22 +1321,17 @@ int mspmv_get_band_passes(int32_t rows, int32_t cols, int32_t nnz, int32_t value
 {
     if (!passes || rows < 0 || cols < 0 || nnz < 0 || (value_bytes != 4 && value_bytes != 8) || (long long) rows + nnz > MAX_ITEMS)
         return hipErrorInvalidValue;
-    const Layout L = make_layout(rows, nnz, value_bytes, thread_tune(value_bytes));
-    CallExtra ex; ex.tune = thread_tune(value_bytes); int force = 0;
-    *passes = band_passes_for(L, (long long) cols * value_bytes, value_bytes, rows, nnz, ex, &force);
+    *passes = resolve_sizes(rows, cols, nnz, value_bytes).band_passes;
     return hipSuccess;
 }
 
 int mspmv_get_clocked_bands(int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t *bands, int32_t *band_cols)
 {
-    int32_t passes = 0;
     if (!bands || !band_cols) return hipErrorInvalidValue;
-    const int st = mspmv_get_band_passes(rows, cols, nnz, value_bytes, &passes);
-    if (st != hipSuccess) return st;
-    CallExtra ex; ex.tune = thread_tune(value_bytes);
-    const int shift = tdm_shift_for(cols, value_bytes, passes, ex);
-    *bands = shift > 0 ? (int32_t) (((long long) cols + (1LL << shift) - 1) >> shift) : 0;
-    *band_cols = shift > 0 ? (int32_t) (1 << shift) : 0;
+    if (rows < 0 || cols < 0 || nnz < 0 || (value_bytes != 4 && value_bytes != 8) || (long long) rows + nnz > MAX_ITEMS) return hipErrorInvalidValue;
+    const CallPlan pl = resolve_sizes(rows, cols, nnz, value_bytes);
+    *bands = pl.tdm_bands;
+    *band_cols = pl.tdm_shift > 0 ? (int32_t) (1 << pl.tdm_shift) : 0;
     return hipSuccess;
 }
 
@@ -1315,7 +1340,7 @@ int mspmv_debug_band_windows(const void *d_temp, int32_t rows, int32_t nnz, int3
 {
     if (!d_temp || !h_verdicts || (value_bytes != 4 && value_bytes != 8) || rows < 0 || nnz < 0 || (long long) rows + nnz > MAX_ITEMS)
         return hipErrorInvalidValue;
-    const Layout L = make_layout(rows, nnz, value_bytes, thread_tune(value_bytes));
+    const Layout L = default_layout(rows, nnz, value_bytes);
     MSPMV_CHECK(hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream_)));
     return (int) hipMemcpy(h_verdicts, static_cast<const char *>(d_temp) + L.band_off, sizeof(int32_t) * BAND_WINDOWS, hipMemcpyDeviceToHost);
 }

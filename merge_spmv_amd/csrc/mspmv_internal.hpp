@@ -29,14 +29,12 @@ struct Tune {
     int tdm = 0, tdm_slot_permille = 0, tdm_lookahead = 0, tdm_band_shift = 0;
 };
 
+// What the caller of csrmv_call asks for beyond the arrays and sizes; what the dispatcher derives from it stays in mspmv_api.hip (CallPlan).
 struct CallExtra {
     int phase = PHASE_ALL;
     Tune tune;
     int tile_map = 0;       // 0: library default (XCD-chunked runs of 64 tiles); else the chunk_log2 code of
                             // xcd_chunked_tile (TILE_MAP_CONTIGUOUS_CODE: one contiguous tile range per XCD)
-    // column-band passes (filled in by csrmv_call, see band_passes_for): > 1 = tile_kernel_band may serve the call
-    int band_passes = 0, band_cols = 0, band_force = 0, num_cols = 0;
-    int tdm_shift = 0, tdm_bands = 0;   // > 0: the clock-scheduled one-pass form serves the call when the windows say "spread" (mspmv_tdm.hpp)
     bool no_bands = false;  // callers that must not take them (the band-major plan: its stacked matrix is banded already)
     bool allow_skinny = false;   // the stateless public calls only: a large fp64 matrix of short rows over a tiny x may take the small tile shape (mspmv_api.hip: skinny_rule)
 };
