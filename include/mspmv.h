@@ -55,7 +55,7 @@ extern "C" {
  * no HIP headers (NULL = the default stream). */
 typedef void *mspmv_stream_t;
 
-#define MSPMV_VERSION 102 /* (the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
+#define MSPMV_VERSION 102 /* (the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
 int mspmv_version(void);
 
 /* hipGetErrorString for codes returned by this library. */
@@ -286,6 +286,66 @@ int mspmv_csrmv_transpose_f64(void *d_temp, size_t *temp_bytes, const double *d_
                               const int32_t *d_row_offsets, const int32_t *d_column_indices,
                               const double *d_x, double *d_y, int32_t rows, int32_t cols, int32_t nnz,
                               double alpha, double beta, mspmv_stream_t stream, int debug_sync);
+
+/* ---- extension: CSR FROM UNSORTED COO, built on the device (csrc/mspmv_coo.hip).  The result is the entries sorted STABLY by
+ * (row, column) -- the reference's CsrMatrix(coo), sparse_matrix.h:636-643: output entry j is input entry permutation[j],
+ * permutation is the unique stable order, duplicates are KEPT, next to each other in input order; row_offsets is right for empty
+ * rows anywhere.  The sort is the transpose's radix sort over a two-part key: ceil(bits(cols - 1) / 8) passes over the column
+ * digits, then ceil(bits(rows - 1) / 8) over the row digits (a 1-column or 1-row matrix skips that half; C2's 3.1 M x 3.1 M runs
+ * 3 + 3), each pass reading and writing (column, row, position, value) as sequential traffic; the first reads the caller's arrays,
+ * the last writes them.  No atomics on global memory, no workgroup waits on another, the host launches the same kernels whatever
+ * the data and never reads device memory: the result is a function of the input alone and the call can be captured in a graph.
+ * d_values == NULL and d_values_csr == NULL: structure (+ permutation) only, for either precision.  Inputs are not modified and
+ * must not alias the outputs.  Indices outside [0, rows) x [0, cols) are the caller's error, as for CSR input (not checked).
+ * nnz == 0 gives all-zero offsets; rows == 0 or cols == 0 with nnz > 0 is refused; rows + nnz <= 2^31 - 65537 (the forward call's
+ * bound, so whatever this builds can be multiplied).  Same two-phase temp storage, 16-byte alignment, ownership, stream,
+ * debug_sync and error conventions as mspmv_csr_transpose_*.  Temp storage: about 2 x nnz x (12 + value bytes) + 4 x nnz bytes
+ * for three passes and more.  Measured on MI355X (profiles/coo_bench.txt): C2's 100 M shuffled triples 10.5 ms fp32 / 11.6 ms fp64
+ * (3 + 3 passes) against 18.1 / 18.4 ms through a stable torch.sort of the 64-bit key and 10.2 / 10.3 ms for rocSPARSE's
+ * coosort_by_row + coo2csr + gthr; an R-MAT edge list of 117 M edges 10.6 ms against 26.7 and 14.4 ms. ---- */
+int mspmv_coo_to_csr_f32(void *d_temp, size_t *temp_bytes,
+                         const float *d_values /* [nnz] or NULL */, const int32_t *d_row_indices, const int32_t *d_column_indices,
+                         int32_t rows, int32_t cols, int32_t nnz,
+                         int32_t *d_row_offsets /* [rows + 1] */, int32_t *d_column_indices_csr, float *d_values_csr,
+                         int32_t *d_permutation /* may be NULL */, mspmv_stream_t stream, int debug_sync);
+int mspmv_coo_to_csr_f64(void *d_temp, size_t *temp_bytes,
+                         const double *d_values /* [nnz] or NULL */, const int32_t *d_row_indices, const int32_t *d_column_indices,
+                         int32_t rows, int32_t cols, int32_t nnz,
+                         int32_t *d_row_offsets /* [rows + 1] */, int32_t *d_column_indices_csr, double *d_values_csr,
+                         int32_t *d_permutation /* may be NULL */, mspmv_stream_t stream, int debug_sync);
+/* New values on the same pattern: values_csr[j] = values[permutation[j]]. */
+int mspmv_coo_to_csr_values_f32(const float *d_values, const int32_t *d_permutation, float *d_values_csr,
+                                int32_t nnz, mspmv_stream_t stream, int debug_sync);
+int mspmv_coo_to_csr_values_f64(const double *d_values, const int32_t *d_permutation, double *d_values_csr,
+                                int32_t nnz, mspmv_stream_t stream, int debug_sync);
+/* Merges duplicates.  Input: a CSR whose rows are sorted by column (what mspmv_coo_to_csr_* writes).  Output: every run of equal
+ * (row, column) replaced by one entry whose value is the run's values added LEFT TO RIGHT in the value type (defined bit for bit;
+ * one thread adds one run, so a run of length L costs L serial adds -- meant for the short runs of assembly and edge lists),
+ * row_offsets_out[rows + 1], and the new count in *d_nnz_out (one int32 on the device: the host does not learn it inside the
+ * call).  The output arrays are sized for nnz; entries past the count are left untouched.  d_values == NULL and
+ * d_values_out == NULL: structure only.  Output must not alias input.  Conventions as above. */
+int mspmv_csr_sum_duplicates_f32(void *d_temp, size_t *temp_bytes,
+                                 const float *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                                 int32_t rows, int32_t cols, int32_t nnz,
+                                 float *d_values_out, int32_t *d_row_offsets_out, int32_t *d_column_indices_out,
+                                 int32_t *d_nnz_out, mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_sum_duplicates_f64(void *d_temp, size_t *temp_bytes,
+                                 const double *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                                 int32_t rows, int32_t cols, int32_t nnz,
+                                 double *d_values_out, int32_t *d_row_offsets_out, int32_t *d_column_indices_out,
+                                 int32_t *d_nnz_out, mspmv_stream_t stream, int debug_sync);
+/* Stateless y = alpha*A*x + beta*y from unsorted COO: builds the CSR into temp storage (mspmv_coo_to_csr_*), then runs the ordinary
+ * CsrMV on it -- bitwise equal to mspmv_coo_to_csr_* followed by mspmv_csrmv_axpby_* on its outputs with that call's queried temp
+ * size.  Duplicates add, because they are kept.  COST: every call pays the whole build, many times the SpMV itself; a caller that
+ * multiplies more than once builds the CSR once. */
+int mspmv_coomv_f32(void *d_temp, size_t *temp_bytes, const float *d_values,
+                    const int32_t *d_row_indices, const int32_t *d_column_indices,
+                    const float *d_x, float *d_y, int32_t rows, int32_t cols, int32_t nnz,
+                    float alpha, float beta, mspmv_stream_t stream, int debug_sync);
+int mspmv_coomv_f64(void *d_temp, size_t *temp_bytes, const double *d_values,
+                    const int32_t *d_row_indices, const int32_t *d_column_indices,
+                    const double *d_x, double *d_y, int32_t rows, int32_t cols, int32_t nnz,
+                    double alpha, double beta, mspmv_stream_t stream, int debug_sync);
 
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */

@@ -17,7 +17,8 @@ import ctypes
 import os
 from typing import Optional, Tuple
 
-__all__ = ["DeviceSpmv", "csrmv", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "plan_bench_record", "library_path", "load_library", "launch_info",
+__all__ = ["DeviceSpmv", "csrmv", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
+           "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
 
@@ -129,6 +130,8 @@ def load_library() -> ctypes.CDLL:
         lib.mspmv_set_record_polls.argtypes = [ctypes.c_int32]
         lib.mspmv_set_compact_tiles.restype = ctypes.c_int
         lib.mspmv_set_compact_tiles.argtypes = [ctypes.c_int32]
+        lib.mspmv_set_tdm.restype = ctypes.c_int
+        lib.mspmv_set_tdm.argtypes = [i32, i32, i32, i32, i32]
     lib.mspmv_get_band_passes.restype = ctypes.c_int
     lib.mspmv_get_band_passes.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]
     lib.mspmv_debug_band_windows.restype = ctypes.c_int
@@ -158,6 +161,19 @@ def load_library() -> ctypes.CDLL:
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, vp, i32, vp, ctypes.c_int]
         fn = getattr(lib, "mspmv_csrmv_transpose_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, sz_p, vp, vp, vp, vp, vp, i32, i32, i32, ct, ct, vp, ctypes.c_int]
+    for name, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        fn = getattr(lib, "mspmv_coo_to_csr_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, sz_p, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_int]
+        fn = getattr(lib, "mspmv_coo_to_csr_values_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, i32, vp, ctypes.c_int]
+        fn = getattr(lib, "mspmv_csr_sum_duplicates_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, sz_p, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_int]
+        fn = getattr(lib, "mspmv_coomv_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, sz_p, vp, vp, vp, vp, vp, i32, i32, i32, ct, ct, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_size.restype = ctypes.c_int
@@ -547,6 +563,172 @@ class CsrTranspose:
 
     def matmul(self, X, Y=None, alpha: float = 1.0, beta: float = 0.0, stream=None):
         return csrmm(self.values_t, self.row_offsets_t, self.column_indices_t, X, Y, alpha=alpha, beta=beta, stream=stream)
+
+
+def _coo_check(values, row_indices, column_indices, what: str):
+    """the checks the C ABI cannot make for COO input; returns (device, value dtype, nnz)"""
+    import torch
+    for t, name in ((row_indices, "row_indices"), (column_indices, "column_indices")):
+        if t is None or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+            raise MspmvError(f"{what}: {name} must be a contiguous 1-D int32 CUDA tensor")
+    dev, nnz = row_indices.device, row_indices.numel()
+    if column_indices.device != dev or column_indices.numel() != nnz:
+        raise MspmvError(f"{what}: column_indices must have row_indices' {nnz} entries on {dev}")
+    if values is not None:
+        if values.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{what} is instantiated for float32 and float64 only, got {values.dtype}")
+        if values.device != dev or not values.is_contiguous() or values.dim() != 1 or values.numel() != nnz:
+            raise MspmvError(f"{what}: values must be a contiguous 1-D tensor of {nnz} entries on {dev}")
+    return dev, (torch.float32 if values is None else values.dtype), nnz
+
+
+def _two_phase(fn, what, dev, stream, args, temp=None):
+    """size query, temp allocation (or `temp` when it is large enough), the call on `stream`; returns the temp tensor"""
+    import torch
+    size = ctypes.c_size_t(0)
+    _check(fn(ctypes.c_void_p(0), ctypes.byref(size), *args, ctypes.c_void_p(0), 0), what + " (size query)")
+    fresh = temp is None or temp.numel() < size.value
+    if fresh:
+        temp = torch.empty(max(int(size.value), 1), dtype=torch.uint8, device=dev)
+    size = ctypes.c_size_t(temp.numel())
+    _check(fn(ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), *args, _stream_handle(stream), 0), what)
+    if fresh and stream is not None and hasattr(stream, "cuda_stream"):
+        temp.record_stream(stream)        # (the allocator must not hand `temp` out again before the work on `stream` has run)
+    return temp
+
+
+def csr_sum_duplicates(values, row_offsets, column_indices, num_cols: int, stream=None):
+    """Merges the duplicate entries of a CSR whose rows are sorted by column (mspmv_csr_sum_duplicates_*): each run of equal (row,
+    column) becomes one entry, its values added left to right in the value type.  Returns (values_out, row_offsets_out,
+    column_indices_out, count): the arrays keep nnz entries, of which the first `count` (a one-element int32 CUDA tensor) are
+    written.  values=None: structure only.  Asynchronous on `stream`; nothing is read back."""
+    import torch
+    if row_offsets is None or not row_offsets.is_cuda or row_offsets.dtype != torch.int32 or not row_offsets.is_contiguous():
+        raise MspmvError("csr_sum_duplicates: row_offsets must be a contiguous int32 CUDA tensor")
+    rows, cols, nnz = row_offsets.numel() - 1, int(num_cols), column_indices.numel()
+    dev = row_offsets.device
+    if rows < 0 or column_indices.dtype != torch.int32 or column_indices.device != dev or not column_indices.is_contiguous():
+        raise MspmvError(f"csr_sum_duplicates: column_indices must be a contiguous int32 tensor on {dev}, row_offsets needs rows + 1 entries")
+    if values is not None and (values.dtype not in (torch.float32, torch.float64) or values.device != dev or not values.is_contiguous()
+                               or values.numel() != nnz):
+        raise MspmvError(f"csr_sum_duplicates: values must be a contiguous float32 / float64 tensor of {nnz} entries on {dev}")
+    dtype = torch.float32 if values is None else values.dtype
+    lib = load_library()
+    fn = lib.mspmv_csr_sum_duplicates_f32 if dtype == torch.float32 else lib.mspmv_csr_sum_duplicates_f64
+    values_out = None if values is None else torch.empty(nnz, dtype=dtype, device=dev)
+    row_offsets_out = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    column_indices_out = torch.empty(nnz, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    args = (_ptr(values), ctypes.c_void_p(row_offsets.data_ptr()), _ptr(column_indices), rows, cols, nnz, _ptr(values_out),
+            ctypes.c_void_p(row_offsets_out.data_ptr()), _ptr(column_indices_out), ctypes.c_void_p(count.data_ptr()))
+    _two_phase(fn, "mspmv_csr_sum_duplicates", dev, stream, args)
+    return values_out, row_offsets_out, column_indices_out, count
+
+
+def coo_to_csr(values, row_indices, column_indices, num_rows: int, num_cols: int, stream=None, sum_duplicates: bool = False,
+               return_permutation: bool = False, _temp=None):
+    """CSR from unsorted COO triples on the device (mspmv_coo_to_csr_*): the entries sorted stably by (row, column), duplicates kept
+    next to each other in input order -- a generators.DeviceCsr (values=None: structure only, .values is None).  With
+    return_permutation=True returns (csr, permutation): csr entry j is input entry permutation[j].  Asynchronous on `stream`.
+    sum_duplicates=True also merges equal (row, column) entries, adding left to right (mspmv_csr_sum_duplicates_*), reads the new
+    count back -- the ONLY synchronising step -- and narrows the arrays to it; the permutation still describes the build before merging."""
+    import torch
+    from .generators import DeviceCsr
+    dev, dtype, nnz = _coo_check(values, row_indices, column_indices, "coo_to_csr")
+    rows, cols = int(num_rows), int(num_cols)
+    lib = load_library()
+    fn = lib.mspmv_coo_to_csr_f32 if dtype == torch.float32 else lib.mspmv_coo_to_csr_f64
+    row_offsets = torch.empty(max(rows, 0) + 1, dtype=torch.int32, device=dev)
+    cols_csr = torch.empty(nnz, dtype=torch.int32, device=dev)
+    values_csr = None if values is None else torch.empty(nnz, dtype=dtype, device=dev)
+    permutation = torch.empty(nnz, dtype=torch.int32, device=dev) if return_permutation else None
+    args = (_ptr(values), _ptr(row_indices), _ptr(column_indices), rows, cols, nnz, ctypes.c_void_p(row_offsets.data_ptr()), _ptr(cols_csr),
+            _ptr(values_csr), _ptr(permutation))
+    _two_phase(fn, "mspmv_coo_to_csr", dev, stream, args, temp=_temp)
+    if sum_duplicates:
+        v, o, c, count = csr_sum_duplicates(values_csr, row_offsets, cols_csr, cols, stream=stream)
+        if stream is not None and hasattr(stream, "synchronize"):
+            stream.synchronize()
+        n = int(count.item())
+        values_csr, row_offsets, cols_csr = (None if v is None else v[:n]), o, c[:n]
+    csr = DeviceCsr(rows, cols, row_offsets, cols_csr, values_csr)
+    return (csr, permutation) if return_permutation else csr
+
+
+class CooToCsr:
+    """A CSR built once from COO triples (coo_to_csr) for a caller whose values change on a fixed pattern: holds the CSR's tensors,
+    the permutation and the build's temp storage.  `b.refresh_values(values)` takes new values in the triples' order
+    (mspmv_coo_to_csr_values_*); `b.rebuild(values, row_indices, column_indices)` runs the build again for new triples of the same
+    count into the same tensors; `b(x, y)` computes y = alpha*A*x + beta*y with the forward call."""
+
+    def __init__(self, values, row_indices, column_indices, num_rows: int, num_cols: int, stream=None):
+        import torch
+        dev, self.dtype, self.nnz = _coo_check(values, row_indices, column_indices, "CooToCsr")
+        if values is None:
+            raise MspmvError("CooToCsr needs values (coo_to_csr builds the structure alone)")
+        self.rows, self.cols = int(num_rows), int(num_cols)
+        lib = load_library()
+        self._fn = lib.mspmv_coo_to_csr_f32 if self.dtype == torch.float32 else lib.mspmv_coo_to_csr_f64
+        self.row_offsets = torch.empty(self.rows + 1, dtype=torch.int32, device=dev)
+        self.column_indices = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+        self.values = torch.empty(self.nnz, dtype=self.dtype, device=dev)
+        self.permutation = torch.empty(self.nnz, dtype=torch.int32, device=dev)
+        self.temp = None
+        self.rebuild(values, row_indices, column_indices, stream=stream)
+
+    def rebuild(self, values, row_indices, column_indices, stream=None):
+        dev, dtype, nnz = _coo_check(values, row_indices, column_indices, "CooToCsr.rebuild")
+        if values is None or dtype != self.dtype or nnz != self.nnz or dev != self.values.device:
+            raise MspmvError(f"CooToCsr.rebuild: needs {self.nnz} triples with {self.dtype} values on {self.values.device}")
+        args = (_ptr(values), _ptr(row_indices), _ptr(column_indices), self.rows, self.cols, self.nnz,
+                ctypes.c_void_p(self.row_offsets.data_ptr()), _ptr(self.column_indices), _ptr(self.values), _ptr(self.permutation))
+        self.temp = _two_phase(self._fn, "mspmv_coo_to_csr", dev, stream, args, temp=self.temp)
+        return self
+
+    def refresh_values(self, values, stream=None):
+        """values_csr[j] = values[permutation[j]] (mspmv_coo_to_csr_values_*) for new values on the same triples."""
+        if values.dtype != self.dtype or values.device != self.values.device or not values.is_contiguous() or values.numel() != self.nnz:
+            raise MspmvError(f"CooToCsr.refresh_values: values must be a contiguous {self.dtype} tensor of {self.nnz} entries on "
+                             f"{self.values.device}")
+        vb = _value_bytes(values)
+        fn = load_library().mspmv_coo_to_csr_values_f32 if vb == 4 else load_library().mspmv_coo_to_csr_values_f64
+        _check(fn(_ptr(values), _ptr(self.permutation), _ptr(self.values), self.nnz, _stream_handle(stream), 0), "mspmv_coo_to_csr_values")
+        return self
+
+    def __call__(self, x, y=None, alpha: float = 1.0, beta: float = 0.0, stream=None):
+        return csrmv(self.values, self.row_offsets, self.column_indices, x, y, num_cols=self.cols, stream=stream, alpha=alpha, beta=beta)
+
+
+def coomv(values, row_indices, column_indices, x, y=None, num_rows: Optional[int] = None, num_cols: Optional[int] = None, stream=None,
+          alpha=None, beta=None, debug_synchronous: bool = False):
+    """y = alpha*A*x + beta*y from unsorted COO triples through the stateless mspmv_coomv_* (duplicates add): the CSR is built inside
+    every call -- a caller that multiplies more than once builds it once (coo_to_csr / CooToCsr).  num_rows defaults to y's length,
+    num_cols to x's.  Returns y."""
+    import torch
+    dev, dtype, nnz = _coo_check(values, row_indices, column_indices, "coomv")
+    if values is None:
+        raise MspmvError("coomv needs values")
+    if num_rows is None and y is None:
+        raise MspmvError("coomv needs num_rows or y")
+    rows = int(num_rows) if num_rows is not None else y.numel()
+    cols = int(num_cols) if num_cols is not None else x.numel()
+    if y is None:
+        y = torch.empty(rows, dtype=dtype, device=dev)
+    for t, name, need in ((x, "x", cols), (y, "y", rows)):
+        if t is None or t.dtype != dtype or t.device != dev or not t.is_contiguous() or t.dim() != 1 or t.numel() < need:
+            raise MspmvError(f"coomv: {name} must be a contiguous 1-D {dtype} tensor of at least {need} entries on {dev}")
+    lib = load_library()
+    fn = lib.mspmv_coomv_f32 if dtype == torch.float32 else lib.mspmv_coomv_f64
+    ct = ctypes.c_float if dtype == torch.float32 else ctypes.c_double
+    args = (_ptr(values), _ptr(row_indices), _ptr(column_indices), _ptr(x), _ptr(y), rows, cols, nnz, ct(1.0 if alpha is None else alpha),
+            ct(0.0 if beta is None else beta))
+    size = ctypes.c_size_t(0)
+    _check(fn(ctypes.c_void_p(0), ctypes.byref(size), *args, ctypes.c_void_p(0), 0), "mspmv_coomv (size query)")
+    temp = torch.empty(max(int(size.value), 1), dtype=torch.uint8, device=dev)
+    _check(fn(ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), *args, _stream_handle(stream), int(bool(debug_synchronous))), "mspmv_coomv")
+    if stream is not None and hasattr(stream, "cuda_stream"):
+        temp.record_stream(stream)
+    return y
 
 
 class CsrMVPlan:

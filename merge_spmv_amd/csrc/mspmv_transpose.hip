@@ -19,9 +19,6 @@
 // Deterministic by construction: every position is a function of the input alone, so the output is the canonical stable transpose.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdio>
-
 #include "../../include/mspmv.h"
 #include "mspmv_internal.hpp"
 
@@ -31,24 +28,7 @@ using namespace mspmv;
 
 #include "mspmv_scan.hpp"      // row_of, block_row_range, the three scan kernels
 
-constexpr int TR_BLOCK = 256, TR_WAVES = TR_BLOCK / 64, TR_IPT = 8, TR_TILE = TR_BLOCK * TR_IPT;
-constexpr int TR_BITS = 8, TR_DIGITS = 1 << TR_BITS;
-constexpr int TR_WAVE_ITEMS = TR_TILE / TR_WAVES;     // a wave's contiguous share of a tile: TR_IPT rounds of 64 items
-
-static int key_bits(int cols)                           // bits of the largest column index, cols - 1
-{
-    int b = 0;
-    for (unsigned v = cols > 1 ? (unsigned) (cols - 1) : 0u; v; v >>= 1) ++b;
-    return b;
-}
-static int radix_passes(int cols) { return std::max(1, (key_bits(cols) + TR_BITS - 1) / TR_BITS); }
-
-// (the set's size with the alignment of its four arrays)
-static uint64_t set_bytes(int nnz, int value_bytes)
-{
-    const uint64_t n = (uint64_t) std::max(nnz, 1);
-    return 3 * align256(n * 4) + align256(n * value_bytes);
-}
+#include "mspmv_radix.hpp"     // the pass kernels (upsweep, downsweep), the offsets / fill / gather kernels, Items, launched, grid_for
 
 struct TrLayout {
     int passes, sets;
@@ -78,147 +58,6 @@ static TrLayout tr_layout(int cols, int nnz, int value_bytes)
     return L;
 }
 
-template <typename V>
-struct Items {                                          // one set of arrays of the sort (n entries each)
-    int *key, *row, *k; V *val;
-};
-template <typename V>
-static Items<V> items_at(char *base, uint64_t off, int nnz)
-{
-    const uint64_t n = (uint64_t) std::max(nnz, 1);
-    Items<V> s;
-    s.key = reinterpret_cast<int *>(base + off);
-    s.row = reinterpret_cast<int *>(base + off + align256(n * 4));
-    s.k = reinterpret_cast<int *>(base + off + 2 * align256(n * 4));
-    s.val = reinterpret_cast<V *>(base + off + 3 * align256(n * 4));
-    return s;
-}
-// ---- upsweep: digit histogram of one tile ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(TR_BLOCK) void tr_upsweep_kernel(const int *__restrict__ keys, int nnz, int shift, long long tiles,
-                                                              int *__restrict__ counts)
-{
-    __shared__ int s_hist[TR_DIGITS];
-    s_hist[threadIdx.x] = 0;
-    __syncthreads();
-    const long long base = (long long) blockIdx.x * TR_TILE;
-    for (int i = 0; i < TR_IPT; ++i) {
-        const long long j = base + i * TR_BLOCK + threadIdx.x;
-        if (j < nnz) atomicAdd(&s_hist[(keys[j] >> shift) & (TR_DIGITS - 1)], 1);
-    }
-    __syncthreads();
-    counts[(long long) threadIdx.x * tiles + blockIdx.x] = s_hist[threadIdx.x];
-}
-
-// ---- downsweep: stable rank by ballots, staged in LDS, contiguous runs per digit ---------------------------------------------
-// FIRST: the items come from the CSR arrays (key = column, row by search, k = position); else from `in`.  VALS: values travel.
-template <typename V, bool FIRST, bool VALS>
-__global__ __launch_bounds__(TR_BLOCK) void tr_downsweep_kernel(const int *__restrict__ off, const int *__restrict__ csr_cols,
-                                                                const V *__restrict__ csr_vals, int rows, Items<V> in, int nnz,
-                                                                int shift, long long tiles, const int *__restrict__ digit_offs,
-                                                                int *__restrict__ out_key, int *__restrict__ out_row,
-                                                                int *__restrict__ out_k, V *__restrict__ out_val)
-{
-    __shared__ int s_wc[TR_WAVES][TR_DIGITS];           // per wave: running count of each digit, then the wave's offset in the digit
-    __shared__ int s_goff[TR_DIGITS], s_lstart[TR_DIGITS];
-    __shared__ int s_key[TR_TILE], s_row[TR_TILE], s_k[TR_TILE];
-    __shared__ V s_val[VALS ? TR_TILE : 1];
-    __shared__ int s_range[2], s_tmp[TR_WAVES];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long tile_base = (long long) blockIdx.x * TR_TILE;
-    const int tile_n = (int) std::min<long long>(TR_TILE, nnz - tile_base);
-    for (int w = 0; w < TR_WAVES; ++w) s_wc[w][threadIdx.x] = 0;
-    s_goff[threadIdx.x] = digit_offs[(long long) threadIdx.x * tiles + blockIdx.x];
-    int r_lo = 0, r_hi = 0;
-    if constexpr (FIRST) {
-        block_row_range(off, rows, (int) tile_base, (int) tile_base + tile_n - 1, s_range);     // (syncs)
-        r_lo = s_range[0]; r_hi = s_range[1];
-    } else {
-        __syncthreads();
-    }
-    const unsigned long long lt = lane ? (~0ull >> (64 - lane)) : 0ull;      // lanes below this one
-    int key[TR_IPT], row[TR_IPT], kk[TR_IPT], rank[TR_IPT];
-    V val[TR_IPT];
-    for (int i = 0; i < TR_IPT; ++i) {
-        const int t = wave * TR_WAVE_ITEMS + i * 64 + lane;                   // item index inside the tile (item order = input order)
-        const bool valid = t < tile_n;
-        const int j = (int) tile_base + t;
-        key[i] = 0; row[i] = 0; kk[i] = j; val[i] = (V) 0;
-        if (valid) {
-            if constexpr (FIRST) {
-                key[i] = csr_cols[j];
-                row[i] = row_of(off, r_lo, r_hi, j);
-                if constexpr (VALS) val[i] = csr_vals[j];
-            } else {
-                key[i] = in.key[j]; row[i] = in.row[j]; kk[i] = in.k[j];
-                if constexpr (VALS) val[i] = in.val[j];
-            }
-        }
-        const int d = (key[i] >> shift) & (TR_DIGITS - 1);
-        unsigned long long peers = __ballot(valid);
-        for (int b = 0; b < TR_BITS; ++b) {
-            const unsigned long long m = __ballot((d >> b) & 1);
-            peers &= ((d >> b) & 1) ? m : ~m;
-        }
-        // the wave's count of digit d so far; the lowest lane of the group adds the group (all lanes read before it writes)
-        const int before = valid ? s_wc[wave][d] : 0;
-        __builtin_amdgcn_wave_barrier();
-        if (valid && (peers & lt) == 0) s_wc[wave][d] = before + __popcll(peers);
-        __builtin_amdgcn_wave_barrier();
-        rank[i] = before + __popcll(peers & lt);
-    }
-    __syncthreads();
-    {   // per digit (thread = digit): the waves' offsets inside the digit's run, and the run's start in the tile
-        const int d = threadIdx.x;
-        int sum = 0;
-        for (int w = 0; w < TR_WAVES; ++w) { const int c = s_wc[w][d]; s_wc[w][d] = sum; sum += c; }
-        const int incl = block_inclusive_scan(sum, s_tmp);                    // (syncs)
-        s_lstart[d] = incl - sum;
-    }
-    __syncthreads();
-    for (int i = 0; i < TR_IPT; ++i) {
-        const int t = wave * TR_WAVE_ITEMS + i * 64 + lane;
-        if (t < tile_n) {
-            const int d = (key[i] >> shift) & (TR_DIGITS - 1);
-            const int p = s_lstart[d] + s_wc[wave][d] + rank[i];
-            s_key[p] = key[i]; s_row[p] = row[i]; s_k[p] = kk[i];
-            if constexpr (VALS) s_val[p] = val[i];
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < tile_n; t += TR_BLOCK) {
-        const int k = s_key[t];
-        const int d = (k >> shift) & (TR_DIGITS - 1);
-        const int p = s_goff[d] + (t - s_lstart[d]);
-        out_key[p] = k; out_row[p] = s_row[t];
-        if (out_k) out_k[p] = s_k[t];
-        if constexpr (VALS) out_val[p] = s_val[t];
-    }
-}
-
-// ---- finishing: row_offsets_t[c] = the number of entries with key < c, by boundary detection ---------------------------------
-// Entry j (0 <= j <= nnz, key[-1] = -1, key[nnz] = cols) writes j at columns key[j-1]+1 .. key[j].  A span longer than a wave is
-// written by the whole wave (lanes taking turns by ballot) so that a long run of empty columns costs no single lane a long loop.
-__global__ __launch_bounds__(256) void tr_offsets_kernel(const int *__restrict__ keys, int nnz, int cols, int *__restrict__ offsets_t)
-{
-    const long long j = (long long) blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    int lo = 0, hi = -1;
-    if (j <= nnz) {
-        lo = j == 0 ? 0 : keys[j - 1] + 1;
-        hi = j == nnz ? cols : keys[j];
-    }
-    const bool longspan = hi - lo >= 64;
-    if (!longspan) for (int c = lo; c <= hi; ++c) offsets_t[c] = (int) j;
-    unsigned long long todo = __ballot(longspan);
-    while (todo) {
-        const int src = __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int slo = __shfl(lo, src, 64), shi = __shfl(hi, src, 64);
-        const int sj = __shfl((int) j, src, 64);
-        for (long long c = (long long) slo + lane; c <= shi; c += 64) offsets_t[c] = sj;
-    }
-}
-
 // cols == 1: A's order is already sorted by column -- column_indices_t = the rows, values_t = the values, permutation = identity
 template <typename V, bool VALS>
 __global__ __launch_bounds__(256) void tr_identity_kernel(const int *__restrict__ off, const V *__restrict__ vals, int rows, int nnz,
@@ -234,32 +73,6 @@ __global__ __launch_bounds__(256) void tr_identity_kernel(const int *__restrict_
         if (perm) perm[j] = j;
     }
 }
-
-__global__ __launch_bounds__(256) void tr_fill_kernel(int *__restrict__ out, long long n, int v)
-{
-    const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = v;
-}
-
-template <typename V>
-__global__ __launch_bounds__(256) void tr_values_kernel(const V *__restrict__ vals, const int *__restrict__ perm, V *__restrict__ vals_t,
-                                                        int nnz)
-{
-    const long long j = (long long) blockIdx.x * 256 + threadIdx.x;
-    if (j < nnz) vals_t[j] = vals[perm[j]];
-}
-
-#define TR_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int) e_; } while (0)
-
-static int launched(hipStream_t stream, int debug_sync, const char *name, unsigned grid)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int) e;
-    if (debug_sync) { printf("mspmv: %s<<<%u, 256>>>\n", name, grid); fflush(stdout); e = hipStreamSynchronize(stream); }
-    return (int) e;
-}
-
-static unsigned grid_for(long long n, int per_block) { return (unsigned) std::max<long long>(1, (n + per_block - 1) / per_block); }
 
 template <typename V, bool VALS>
 int transpose_run(char *base, const TrLayout &L, const V *d_values, const int32_t *d_off, const int32_t *d_cols, int32_t rows,
@@ -284,26 +97,20 @@ int transpose_run(char *base, const TrLayout &L, const V *d_values, const int32_
     int *keys = reinterpret_cast<int *>(base + L.keys_off);
     Items<V> set[2] = {items_at<V>(base, L.set_off[0], nnz), items_at<V>(base, L.set_off[1], nnz)};
     const unsigned tgrid = (unsigned) L.tiles;
-    const unsigned sblocks = grid_for(L.table, SCAN_CHUNK);
     for (int p = 0; p < L.passes; ++p) {
         const int shift = p * TR_BITS;
         const bool last = p == L.passes - 1;
         const Items<V> &src = set[(p + 1) & 1];          // pass p reads what pass p - 1 wrote (set (p - 1) % 2)
         hipLaunchKernelGGL(tr_upsweep_kernel, dim3(tgrid), dim3(TR_BLOCK), 0, stream, p == 0 ? d_cols : src.key, nnz, shift, L.tiles, counts);
         if (int e = launched(stream, debug_sync, "tr_upsweep_kernel", tgrid)) return e;
-        hipLaunchKernelGGL(scan_reduce_kernel, dim3(sblocks), dim3(SCAN_BLOCK), 0, stream, counts, L.table, bsum);
-        if (int e = launched(stream, debug_sync, "scan_reduce_kernel", sblocks)) return e;
-        hipLaunchKernelGGL(scan_blocksums_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, bsum, (int) sblocks);
-        if (int e = launched(stream, debug_sync, "scan_blocksums_kernel", 1)) return e;
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(sblocks), dim3(SCAN_BLOCK), 0, stream, counts, L.table, bsum, offs);
-        if (int e = launched(stream, debug_sync, "scan_apply_kernel", sblocks)) return e;
+        if (int e = scan_table(counts, L.table, bsum, offs, stream, debug_sync)) return e;
         int *ok = last ? keys : set[p & 1].key, *orow = last ? d_cols_t : set[p & 1].row, *okk = last ? d_perm : set[p & 1].k;
         V *oval = last ? d_values_t : set[p & 1].val;
         if (p == 0)
-            hipLaunchKernelGGL((tr_downsweep_kernel<V, true, VALS>), dim3(tgrid), dim3(TR_BLOCK), 0, stream, d_off, d_cols, d_values, rows, src,
+            hipLaunchKernelGGL((tr_downsweep_kernel<V, SRC_CSR, VALS>), dim3(tgrid), dim3(TR_BLOCK), 0, stream, d_off, d_cols, d_values, rows, src,
                                nnz, shift, L.tiles, offs, ok, orow, okk, oval);
         else
-            hipLaunchKernelGGL((tr_downsweep_kernel<V, false, VALS>), dim3(tgrid), dim3(TR_BLOCK), 0, stream, d_off, d_cols, d_values, rows,
+            hipLaunchKernelGGL((tr_downsweep_kernel<V, SRC_ITEMS, VALS>), dim3(tgrid), dim3(TR_BLOCK), 0, stream, d_off, d_cols, d_values, rows,
                                src, nnz, shift, L.tiles, offs, ok, orow, okk, oval);
         if (int e = launched(stream, debug_sync, "tr_downsweep_kernel", tgrid)) return e;
     }

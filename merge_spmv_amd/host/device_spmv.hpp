@@ -174,6 +174,73 @@ struct DeviceSpmv {
                                                           d_vector_x, d_vector_y, num_rows, num_cols, num_nonzeros, alpha, beta,
                                                           (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
     }
+
+    // ---- COO (extension): CSR built on the device from unsorted triples -- the entries sorted stably by (row, column), duplicates kept
+    // (d_values == d_values_csr == nullptr: structure only) ...
+    template <typename ValueT>
+    static hipError_t CooToCsr(void *d_temp_storage, size_t &temp_storage_bytes, const ValueT *d_values, const int *d_row_indices,
+                               const int *d_column_indices, int num_rows, int num_cols, int num_nonzeros, int *d_row_offsets,
+                               int *d_column_indices_csr, ValueT *d_values_csr, int *d_permutation = nullptr, hipStream_t stream = 0,
+                               bool debug_synchronous = false)
+    {
+        static_assert(std::is_same<ValueT, float>::value || std::is_same<ValueT, double>::value, "float or double");
+        if constexpr (std::is_same<ValueT, float>::value)
+            return (hipError_t) mspmv_coo_to_csr_f32(d_temp_storage, &temp_storage_bytes, d_values, d_row_indices, d_column_indices, num_rows,
+                                                     num_cols, num_nonzeros, d_row_offsets, d_column_indices_csr, d_values_csr, d_permutation,
+                                                     (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+        else
+            return (hipError_t) mspmv_coo_to_csr_f64(d_temp_storage, &temp_storage_bytes, d_values, d_row_indices, d_column_indices, num_rows,
+                                                     num_cols, num_nonzeros, d_row_offsets, d_column_indices_csr, d_values_csr, d_permutation,
+                                                     (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+    }
+    // ... new values on the same pattern: values_csr[j] = values[permutation[j]]
+    template <typename ValueT>
+    static hipError_t CooToCsrValues(const ValueT *d_values, const int *d_permutation, ValueT *d_values_csr, int num_nonzeros,
+                                     hipStream_t stream = 0, bool debug_synchronous = false)
+    {
+        static_assert(std::is_same<ValueT, float>::value || std::is_same<ValueT, double>::value, "float or double");
+        if constexpr (std::is_same<ValueT, float>::value)
+            return (hipError_t) mspmv_coo_to_csr_values_f32(d_values, d_permutation, d_values_csr, num_nonzeros, (mspmv_stream_t) stream,
+                                                            debug_synchronous ? 1 : 0);
+        else
+            return (hipError_t) mspmv_coo_to_csr_values_f64(d_values, d_permutation, d_values_csr, num_nonzeros, (mspmv_stream_t) stream,
+                                                            debug_synchronous ? 1 : 0);
+    }
+    // ... duplicates of a CSR with sorted rows merged, each run added left to right; the new count goes to *d_num_nonzeros_out (device)
+    template <typename ValueT>
+    static hipError_t CsrSumDuplicates(void *d_temp_storage, size_t &temp_storage_bytes, const ValueT *d_values, const int *d_row_offsets,
+                                       const int *d_column_indices, int num_rows, int num_cols, int num_nonzeros, ValueT *d_values_out,
+                                       int *d_row_offsets_out, int *d_column_indices_out, int *d_num_nonzeros_out, hipStream_t stream = 0,
+                                       bool debug_synchronous = false)
+    {
+        static_assert(std::is_same<ValueT, float>::value || std::is_same<ValueT, double>::value, "float or double");
+        if constexpr (std::is_same<ValueT, float>::value)
+            return (hipError_t) mspmv_csr_sum_duplicates_f32(d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices,
+                                                             num_rows, num_cols, num_nonzeros, d_values_out, d_row_offsets_out,
+                                                             d_column_indices_out, d_num_nonzeros_out, (mspmv_stream_t) stream,
+                                                             debug_synchronous ? 1 : 0);
+        else
+            return (hipError_t) mspmv_csr_sum_duplicates_f64(d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices,
+                                                             num_rows, num_cols, num_nonzeros, d_values_out, d_row_offsets_out,
+                                                             d_column_indices_out, d_num_nonzeros_out, (mspmv_stream_t) stream,
+                                                             debug_synchronous ? 1 : 0);
+    }
+    // ... stateless y = alpha*A*x + beta*y from unsorted triples: builds the CSR into temp storage every call
+    template <typename ValueT>
+    static hipError_t CooMV(void *d_temp_storage, size_t &temp_storage_bytes, const ValueT *d_values, const int *d_row_indices,
+                            const int *d_column_indices, const ValueT *d_vector_x, ValueT *d_vector_y, int num_rows, int num_cols,
+                            int num_nonzeros, ValueT alpha = 1, ValueT beta = 0, hipStream_t stream = 0, bool debug_synchronous = false)
+    {
+        static_assert(std::is_same<ValueT, float>::value || std::is_same<ValueT, double>::value, "float or double");
+        if constexpr (std::is_same<ValueT, float>::value)
+            return (hipError_t) mspmv_coomv_f32(d_temp_storage, &temp_storage_bytes, d_values, d_row_indices, d_column_indices, d_vector_x,
+                                                d_vector_y, num_rows, num_cols, num_nonzeros, alpha, beta, (mspmv_stream_t) stream,
+                                                debug_synchronous ? 1 : 0);
+        else
+            return (hipError_t) mspmv_coomv_f64(d_temp_storage, &temp_storage_bytes, d_values, d_row_indices, d_column_indices, d_vector_x,
+                                                d_vector_y, num_rows, num_cols, num_nonzeros, alpha, beta, (mspmv_stream_t) stream,
+                                                debug_synchronous ? 1 : 0);
+    }
 };
 
 }  // namespace mspmv

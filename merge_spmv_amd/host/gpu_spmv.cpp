@@ -9,7 +9,7 @@
 //
 //   gpu_spmv [--device=<id>] [--quiet] [--v] [--v2] [--i=<iterations>] [--fp32]
 //            [--alpha=<a>] [--beta=<b>] [--peak-gbs=<GB/s>] [--no-strict] [--no-vendor] [--no-hyb] [--check]
-//            [--prepared] [--plan[=<bands>]] [--transpose] [--gpus=<G>[,<G2>...]] [--mg-one-device] [--mg-exchange=peer|rccl]
+//            [--prepared] [--plan[=<bands>]] [--transpose] [--coo] [--gpus=<G>[,<G2>...]] [--mg-one-device] [--mg-exchange=peer|rccl]
 //            --mtx=<file> | --dense=<cols> [--size=<nnz>] | --grid2d=<w> | --grid3d=<w> | --wheel=<spokes>
 //
 // Extra method lines of this project (non-quiet only; the CSV keeps the reference's columns):
@@ -19,6 +19,9 @@
 //   --transpose  y = alpha*A^T*x + beta*y: A^T built on the device (mspmv_csr_transpose_*; set-up, checked entry for entry against a
 //                stable transpose on the host), the forward call on it, the stateless mspmv_csrmv_transpose_*, and (with the vendor
 //                lines) rocSPARSE CsrMV with the transpose operation, set-up = rocsparse_csr2csc
+//   --coo        the matrix's triples uploaded in a fixed shuffled order (a seeded permutation): the CSR built from them on the device
+//                (mspmv_coo_to_csr_*; set-up, checked entry for entry against a stable sort on the host), the forward call on it, the
+//                stateless mspmv_coomv_*, and (with the vendor lines) the time of rocSPARSE's coosort_by_row + coo2csr + gthr
 //   --gpus=G     the matrix merge-partitioned over G GPUs of this node through the C multi-GPU operator
 //                (mspmv_mg_plan_*; the reference has a single --device, utils.h:465-474), one line per G;
 //                --mg-one-device runs all parts on --device (a functional run on a 1-GPU box)
@@ -29,7 +32,10 @@
 #include <hip/hip_runtime.h>
 #include <rocsparse/rocsparse.h>
 
+#include <algorithm>
 #include <cstring>
+#include <numeric>
+#include <random>
 #include <vector>
 
 #include "device_spmv.hpp"
@@ -531,7 +537,138 @@ float TestRocsparseTranspose(const RunConfig &c, const CsrMatrix<V> &at, const s
     return ms;
 }
 
-struct Extras { bool vendor = true, hyb = true, prepared = false, plan = false, hotcols = false, transpose = false, mg_one_device = false; int plan_bands = 0, mg_exchange = MSPMV_MG_EXCHANGE_AUTO; std::vector<int> gpus; };
+// --coo (extension): the matrix as triples in a fixed shuffled order, on the host and on the device; `sorted` is what a stable sort of
+// them by (row, column) gives -- the CSR the device build must reproduce entry for entry
+template <typename V>
+struct CooProblem {
+    std::vector<int> row, col;
+    std::vector<V> val;
+    CsrMatrix<V> sorted;
+    int *d_row = nullptr, *d_col = nullptr;
+    V *d_val = nullptr;
+    explicit CooProblem(const CsrMatrix<V> &a)
+    {
+        const size_t n = (size_t) a.num_nonzeros;
+        std::vector<int> order(n), rows_of(n);
+        for (int r = 0; r < a.num_rows; ++r)
+            for (int j = a.row_offsets[r]; j < a.row_offsets[r + 1]; ++j) rows_of[j] = r;
+        std::iota(order.begin(), order.end(), 0);
+        std::mt19937_64 gen(12345);                              // (Fisher-Yates by hand: std::shuffle's draws differ between libraries)
+        for (size_t i = n; i > 1; --i) std::swap(order[i - 1], order[(size_t) (gen() % i)]);
+        row.resize(n); col.resize(n); val.resize(n);
+        for (size_t i = 0; i < n; ++i) { row[i] = rows_of[order[i]]; col[i] = a.column_indices[order[i]]; val[i] = a.values[order[i]]; }
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return row[x] != row[y] ? row[x] < row[y] : col[x] < col[y]; });
+        sorted.num_rows = a.num_rows; sorted.num_cols = a.num_cols; sorted.num_nonzeros = a.num_nonzeros;
+        sorted.row_offsets.assign((size_t) a.num_rows + 1, 0);
+        sorted.column_indices.resize(n); sorted.values.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            ++sorted.row_offsets[(size_t) row[order[i]] + 1];
+            sorted.column_indices[i] = col[order[i]]; sorted.values[i] = val[order[i]];
+        }
+        for (int r = 0; r < a.num_rows; ++r) sorted.row_offsets[(size_t) r + 1] += sorted.row_offsets[r];
+        HIP_OK(hipMalloc(&d_row, sizeof(int) * std::max<size_t>(n, 1))); HIP_OK(hipMalloc(&d_col, sizeof(int) * std::max<size_t>(n, 1)));
+        HIP_OK(hipMalloc(&d_val, sizeof(V) * std::max<size_t>(n, 1)));
+        HIP_OK(hipMemcpy(d_row, row.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_col, col.data(), sizeof(int) * n, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_val, val.data(), sizeof(V) * n, hipMemcpyHostToDevice));
+    }
+    ~CooProblem() { (void) hipFree(d_row); (void) hipFree(d_col); (void) hipFree(d_val); }
+};
+
+// the CSR on the device (mspmv_coo_to_csr_*), timed as set-up and checked entry for entry against the host's stable sort; `pc` then holds it
+template <typename V>
+float BuildFromCoo(const CooProblem<V> &coo, const std::vector<V> &x, DeviceProblem<V> &pc)
+{
+    const CsrMatrix<V> &a = coo.sorted;
+    pc.rows = a.num_rows; pc.cols = a.num_cols; pc.nnz = a.num_nonzeros;
+    HIP_OK(hipMalloc(&pc.d_values, sizeof(V) * std::max(pc.nnz, 1)));
+    HIP_OK(hipMalloc(&pc.d_row_offsets, sizeof(int) * (pc.rows + 1)));
+    HIP_OK(hipMalloc(&pc.d_cols, sizeof(int) * std::max(pc.nnz, 1)));
+    HIP_OK(hipMalloc(&pc.d_x, sizeof(V) * std::max(pc.cols, 1)));
+    HIP_OK(hipMalloc(&pc.d_y, sizeof(V) * std::max(pc.rows, 1)));
+    HIP_OK(hipMemcpy(pc.d_x, x.data(), sizeof(V) * pc.cols, hipMemcpyHostToDevice));
+    size_t bytes = 0;
+    HIP_OK(mspmv::DeviceSpmv::CooToCsr<V>(nullptr, bytes, coo.d_val, coo.d_row, coo.d_col, pc.rows, pc.cols, pc.nnz, pc.d_row_offsets, pc.d_cols,
+                                          pc.d_values));
+    void *d_temp = nullptr;
+    HIP_OK(hipMalloc(&d_temp, bytes));
+    GpuTimer setup; setup.Start();
+    HIP_OK(mspmv::DeviceSpmv::CooToCsr<V>(d_temp, bytes, coo.d_val, coo.d_row, coo.d_col, pc.rows, pc.cols, pc.nnz, pc.d_row_offsets, pc.d_cols,
+                                          pc.d_values));
+    setup.Stop();
+    const float ms = setup.ElapsedMillis();
+    HIP_OK(hipFree(d_temp));
+    std::vector<int> off((size_t) pc.rows + 1), col((size_t) pc.nnz);
+    std::vector<V> val((size_t) pc.nnz);
+    HIP_OK(hipMemcpy(off.data(), pc.d_row_offsets, sizeof(int) * off.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(col.data(), pc.d_cols, sizeof(int) * col.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(val.data(), pc.d_values, sizeof(V) * val.size(), hipMemcpyDeviceToHost));
+    const bool same = off == a.row_offsets && std::equal(col.begin(), col.end(), a.column_indices.begin()) &&
+                      std::memcmp(val.data(), a.values.data(), sizeof(V) * val.size()) == 0;
+    printf("\tCSR built on the device from shuffled COO: %s (row offsets, column indices and values bit for bit the stable sort)\n",
+           same ? "PASS" : "FAIL");
+    return ms;
+}
+
+// the stateless y = alpha*A*x + beta*y from the shuffled triples (mspmv_coomv_*): the build inside every call
+template <typename V>
+float TestCooStateless(const RunConfig &c, const CooProblem<V> &coo, const std::vector<V> &x, const std::vector<V> &y_in,
+                       const std::vector<V> &gold, DeviceProblem<V> &pc, int iterations)
+{
+    auto call = [&](void *temp, size_t &bytes) {
+        return mspmv::DeviceSpmv::CooMV<V>(temp, bytes, coo.d_val, coo.d_row, coo.d_col, pc.d_x, pc.d_y, pc.rows, pc.cols, pc.nnz, (V) c.alpha,
+                                           (V) c.beta, (hipStream_t) 0, false);
+    };
+    size_t bytes = 0;
+    HIP_OK(call(nullptr, bytes));
+    void *d_temp = nullptr;
+    HIP_OK(hipMalloc(&d_temp, bytes));
+    HIP_OK(hipMemcpy(pc.d_y, y_in.data(), sizeof(V) * pc.rows, hipMemcpyHostToDevice));
+    HIP_OK(call(d_temp, bytes));
+    Verify(c, coo.sorted, x, gold, pc.d_y, c.alpha == 1.0f && c.beta == 0.0f);
+    GpuTimer timer; timer.Start();
+    for (int it = 0; it < iterations; ++it) HIP_OK(call(d_temp, bytes));
+    timer.Stop();
+    const float ms = timer.ElapsedMillis() / iterations;
+    HIP_OK(hipFree(d_temp));
+    return ms;
+}
+
+// what the same build costs the vendor library: rocsparse_coosort_by_row on a copy of the indices (with a permutation), coo2csr for the
+// offsets and gthr for the values; the copy is not timed.  (Its order among duplicates is not specified, so only the offsets are compared.)
+template <typename V>
+float TimeRocsparseCooBuild(const CooProblem<V> &coo, rocsparse_handle handle)
+{
+    const CsrMatrix<V> &a = coo.sorted;
+    const int rows = a.num_rows, cols = a.num_cols, nnz = a.num_nonzeros;
+    const size_t n = (size_t) std::max(nnz, 1);
+    int *row = nullptr, *col = nullptr, *perm = nullptr, *off = nullptr; V *val = nullptr; void *buf = nullptr;
+    HIP_OK(hipMalloc(&row, sizeof(int) * n)); HIP_OK(hipMalloc(&col, sizeof(int) * n)); HIP_OK(hipMalloc(&perm, sizeof(int) * n));
+    HIP_OK(hipMalloc(&off, sizeof(int) * ((size_t) rows + 1))); HIP_OK(hipMalloc(&val, sizeof(V) * n));
+    size_t bytes = 0;
+    ROCSPARSE_OK(rocsparse_coosort_buffer_size(handle, rows, cols, nnz, coo.d_row, coo.d_col, &bytes));
+    HIP_OK(hipMalloc(&buf, std::max<size_t>(bytes, 1)));
+    float ms = 0;
+    for (int rep = 0; rep < 2; ++rep) {                           // (the first run warms the library up)
+        HIP_OK(hipMemcpy(row, coo.d_row, sizeof(int) * nnz, hipMemcpyDeviceToDevice));
+        HIP_OK(hipMemcpy(col, coo.d_col, sizeof(int) * nnz, hipMemcpyDeviceToDevice));
+        GpuTimer t; t.Start();
+        ROCSPARSE_OK(rocsparse_create_identity_permutation(handle, nnz, perm));
+        ROCSPARSE_OK(rocsparse_coosort_by_row(handle, rows, cols, nnz, row, col, perm, buf));
+        ROCSPARSE_OK(rocsparse_coo2csr(handle, row, nnz, rows, off, rocsparse_index_base_zero));
+        if constexpr (sizeof(V) == 4) ROCSPARSE_OK(rocsparse_sgthr(handle, nnz, coo.d_val, val, perm, rocsparse_index_base_zero));
+        else ROCSPARSE_OK(rocsparse_dgthr(handle, nnz, coo.d_val, val, perm, rocsparse_index_base_zero));
+        t.Stop(); ms = t.ElapsedMillis();
+    }
+    std::vector<int> h((size_t) rows + 1);
+    HIP_OK(hipMemcpy(h.data(), off, sizeof(int) * h.size(), hipMemcpyDeviceToHost));
+    printf("\trocSPARSE coosort_by_row + coo2csr + gthr: %.4f ms, row offsets %s\n", ms, h == a.row_offsets ? "agree" : "DIFFER");
+    HIP_OK(hipFree(row)); HIP_OK(hipFree(col)); HIP_OK(hipFree(perm)); HIP_OK(hipFree(off)); HIP_OK(hipFree(val)); HIP_OK(hipFree(buf));
+    return ms;
+}
+
+struct Extras { bool vendor = true, hyb = true, prepared = false, plan = false, hotcols = false, transpose = false, coo = false, mg_one_device = false; int plan_bands = 0, mg_exchange = MSPMV_MG_EXCHANGE_AUTO; std::vector<int> gpus; };
 
 template <typename V>
 void Run(const RunConfig &c, const Device &dev, const Extras &ex)
@@ -605,6 +742,26 @@ void Run(const RunConfig &c, const Device &dev, const Extras &ex)
             ROCSPARSE_OK(rocsparse_destroy_handle(handle));
         }
     }
+    if (ex.coo && !c.quiet) {                   // extra method lines, never in the CSV: the matrix arrives as shuffled triples
+        CooProblem<V> coo(csr);
+        std::vector<V> gold_c((size_t) csr.num_rows);
+        SpmvGold(coo.sorted, x.data(), y_in.data(), gold_c.data(), (V) c.alpha, (V) c.beta);
+        DeviceProblem<V> pc;
+        printf("\n\nMerge-based CsrMV (COO: CSR built once on the device), "); fflush(stdout);
+        const float build_ms = BuildFromCoo(coo, x, pc);
+        avg_ms = TestMerge(c, coo.sorted, x, y_in, gold_c, pc, iterations, setup_ms);
+        DisplayPerf(c.quiet, (int) sizeof(V), build_ms, avg_ms, csr.num_rows, csr.num_nonzeros, dev.giga_bandwidth);
+        DisplayRoofline((int) sizeof(V), avg_ms, csr.num_rows, csr.num_cols, csr.num_nonzeros, dev.giga_bandwidth);
+        printf("\n\nMerge-based CooMV (stateless, CSR built inside every call), "); fflush(stdout);
+        avg_ms = TestCooStateless(c, coo, x, y_in, gold_c, pc, iterations);
+        DisplayPerf(c.quiet, (int) sizeof(V), 0.0, avg_ms, csr.num_rows, csr.num_nonzeros, dev.giga_bandwidth);
+        if (vendor) {
+            rocsparse_handle handle;
+            ROCSPARSE_OK(rocsparse_create_handle(&handle));
+            TimeRocsparseCooBuild(coo, handle);
+            ROCSPARSE_OK(rocsparse_destroy_handle(handle));
+        }
+    }
     if (!c.quiet && c.alpha == 1.0f && c.beta == 0.0f)
         for (int parts : ex.gpus) {
             int used = 0;
@@ -642,7 +799,7 @@ int main(int argc, char **argv)
     if (args.CheckCmdLineFlag("help")) {
         printf("%s [--csrmv | --hybmv | --bsrmv ] [--device=<device-id>] [--quiet] [--v] [--i=<timing iterations>] [--fp32] "
                "[--alpha=<alpha scalar (default: 1.0)>] [--beta=<beta scalar (default: 0.0)>] [--peak-gbs=<GB/s>] "
-               "[--no-strict] [--no-vendor] [--no-hyb] [--check] [--cache] [--prepared] [--plan[=<bands>]] [--hotcols] [--transpose] [--gpus=<G>[,<G2>...]] [--mg-one-device] "
+               "[--no-strict] [--no-vendor] [--no-hyb] [--check] [--cache] [--prepared] [--plan[=<bands>]] [--hotcols] [--transpose] [--coo] [--gpus=<G>[,<G2>...]] [--mg-one-device] "
                "[--mg-exchange=peer|rccl] [--chunk-times=<calls per chunk>]\n"
                "\t--mtx=<matrix market file> \n\t--dense=<cols>\n\t--grid2d=<width>\n\t--grid3d=<width>\n\t--wheel=<spokes>\n",
                argv[0]);
@@ -656,6 +813,7 @@ int main(int argc, char **argv)
     ex.prepared = args.CheckCmdLineFlag("prepared");
     ex.hotcols = args.CheckCmdLineFlag("hotcols");
     ex.transpose = args.CheckCmdLineFlag("transpose");
+    ex.coo = args.CheckCmdLineFlag("coo");
     ex.plan = args.CheckCmdLineFlag("plan");
     args.GetCmdLineArgument("plan", ex.plan_bands);
     ex.mg_one_device = args.CheckCmdLineFlag("mg-one-device");
