@@ -55,7 +55,7 @@ extern "C" {
  * no HIP headers (NULL = the default stream). */
 typedef void *mspmv_stream_t;
 
-#define MSPMV_VERSION 102 /* (the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
+#define MSPMV_VERSION 102 /* (the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, and the mixed-precision ones, mspmv_csrmv_mixed_* / mspmv_csrmv_mixed_prepared_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
 int mspmv_version(void);
 
 /* hipGetErrorString for codes returned by this library. */
@@ -140,6 +140,59 @@ int mspmv_csrmv_prepared_f64(void *d_temp, size_t *temp_bytes, const double *d_v
                              const double *d_x, double *d_y, int32_t rows, int32_t cols,
                              int32_t nnz, double alpha, double beta,
                              mspmv_stream_t stream, int debug_sync);
+
+/* ---- extension: MIXED PRECISION -- the matrix values stored narrow, everything else wide (what the generic SpMV of rocSPARSE /
+ * cuSPARSE offers; mixed-precision Krylov solvers and iterative refinement keep A narrow and the vectors wide).  Two pairs,
+ * written (stored type of d_values -> compute type; x, y, alpha, beta, every product and every sum are in the compute type):
+ *     f32  -> f64     const float *d_values,    const double *d_x, double *d_y
+ *     bf16 -> f32     const uint16_t *d_values (the upper 16 bits of an IEEE fp32), const float *d_x, float *d_y
+ *     y = alpha * A * x + beta * y        (beta == 0: y is never read; alpha = 1, beta = 0 is the plain product)
+ * A stream-bound CsrMV costs the bytes of the CSR stream, and two thirds of an fp64 stream are the values: the call reads 8 bytes
+ * per nonzero instead of 12 (6 instead of 8 for bf16 -> f32) and needs no widened copy of the matrix.  Every value is widened in
+ * registers right before its multiply; widening is exact (every fp32 is an fp64, every bf16 an fp32), so the call computes the
+ * product of the WIDENED matrix.  Conventions of mspmv_csrmv_axpby_*: two-phase temp storage (16-byte aligned), caller-owned
+ * buffers, no state, rows without entries get exactly 0, nothing outside the arrays is touched, rows + nnz <= 2^31 - 65537,
+ * asynchronous on `stream`, debug_sync prints the launch lines.  The 16-byte-per-lane streams need d_row_offsets and
+ * d_column_indices 16-byte aligned and d_values aligned to four of its elements (16 bytes for f32, 8 for bf16; any array length,
+ * a bf16 array of odd length included); other arrays run the dword-per-lane kernel, as in the wide calls.
+ * WHAT IT EQUALS.  Every decision that shapes the association of the sums -- the tile shape, one launch or the classic three,
+ * the rule for matrices of long rows -- is taken exactly as mspmv_csrmv_axpby_f64 / _f32 (the wide call of the COMPUTE type)
+ * takes it, with value_bytes = sizeof(compute type) (and that precision's mspmv_set_tuning in the development library); only what
+ * counts bytes moved sees the stored size (non-temporal loads from a 256 MB stream up).  The mixed call takes none of the
+ * special forms: not the compact front end of small problems (bit for bit the same y as the general kernel anyway), not the
+ * small-shape layout of large fp64 matrices of short rows over a tiny x (mspmv_get_launch_info_cols), and it is never a
+ * column-band CANDIDATE (the rule of the hot-column plan's inner call, below).  Hence:
+ *   * the size query (d_temp == NULL) answers mspmv_get_launch_info(rows, nnz, sizeof(compute type)).temp_bytes -- one buffer
+ *     serves the mixed and the wide call --, and mspmv_csrmv_prepare(..., value_bytes = sizeof(compute type)) prepares the
+ *     coordinates for mspmv_csrmv_mixed_prepared_* (same guarantees as mspmv_csrmv_prepared_*);
+ *   * y is BIT FOR BIT what mspmv_csrmv_axpby_f64 / _f32 (prepared: mspmv_csrmv_prepared_*) returns for the widened values on
+ *     arrays aligned alike, unless the sizes make the wide call a column-band candidate (mspmv_get_band_passes(rows, cols, nnz,
+ *     sizeof(compute type)) > 1) or let it take the small-shape layout (mspmv_get_launch_info_cols reports another
+ *     items_per_thread than mspmv_get_launch_info, and the wide call is given room for it);
+ *   * for column-band candidates y equals the wide call's ONE-LAUNCH form (dev library: mspmv_set_band_passes(vb, -1)), the
+ *     comparison prescribed for the hot-column plan; where the wide call takes the small-shape layout, rows that lie inside
+ *     one tile are still bit for bit equal and a longer row is associated as the tiles of the shape that ran cut it.
+ * fp16 is not offered (one more widening function and set of kernels if somebody asks).  No reference counterpart. ---- */
+int mspmv_csrmv_mixed_f32_f64(void *d_temp, size_t *temp_bytes, const float *d_values,
+                              const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                              const double *d_x, double *d_y, int32_t rows, int32_t cols,
+                              int32_t nnz, double alpha, double beta,
+                              mspmv_stream_t stream, int debug_sync);
+int mspmv_csrmv_mixed_bf16_f32(void *d_temp, size_t *temp_bytes, const uint16_t *d_values,
+                               const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                               const float *d_x, float *d_y, int32_t rows, int32_t cols,
+                               int32_t nnz, float alpha, float beta,
+                               mspmv_stream_t stream, int debug_sync);
+int mspmv_csrmv_mixed_prepared_f32_f64(void *d_temp, size_t *temp_bytes, const float *d_values,
+                                       const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                                       const double *d_x, double *d_y, int32_t rows, int32_t cols,
+                                       int32_t nnz, double alpha, double beta,
+                                       mspmv_stream_t stream, int debug_sync);
+int mspmv_csrmv_mixed_prepared_bf16_f32(void *d_temp, size_t *temp_bytes, const uint16_t *d_values,
+                                        const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                                        const float *d_x, float *d_y, int32_t rows, int32_t cols,
+                                        int32_t nnz, float alpha, float beta,
+                                        mspmv_stream_t stream, int debug_sync);
 
 /* ---- extension: PREPARED PLAN for a gather-bound matrix multiplied many times (opt-in; the stateless
  * drop-in calls above never use it).  When x is larger than an XCD's 4 MiB L2, ~70 % of the x gathers miss

@@ -17,7 +17,7 @@ import ctypes
 import os
 from typing import Optional, Tuple
 
-__all__ = ["DeviceSpmv", "csrmv", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
+__all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -102,6 +102,11 @@ def load_library() -> ctypes.CDLL:
     lib.mspmv_csrmv_prepared_f64.restype = ctypes.c_int
     lib.mspmv_csrmv_prepared_f64.argtypes = [vp, sz_p, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.c_double,
                                              ctypes.c_double, vp, ctypes.c_int]
+    for pair, ct in (("f32_f64", ctypes.c_double), ("bf16_f32", ctypes.c_float)):
+        for name in ("mspmv_csrmv_mixed_" + pair, "mspmv_csrmv_mixed_prepared_" + pair):
+            fn = getattr(lib, name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = [vp, sz_p, vp, vp, vp, vp, vp, i32, i32, i32, ct, ct, vp, ctypes.c_int]
     lib.mspmv_csrmm_f32.restype = ctypes.c_int
     lib.mspmv_csrmm_f32.argtypes = [vp, sz_p, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, ctypes.c_float, ctypes.c_float,
                                     vp, ctypes.c_int]
@@ -256,7 +261,7 @@ def _stream_handle(stream) -> ctypes.c_void_p:
 
 
 def _validate(values, row_offsets, column_indices, x, y, rows: int, cols: int, nnz: int, what: str,
-              x_rows: Optional[int] = None, y_rows: Optional[int] = None) -> None:
+              x_rows: Optional[int] = None, y_rows: Optional[int] = None, values_dtype=None) -> None:
     """The checks the C ABI cannot make (it sees raw pointers): every csrmv / csrmm / DeviceSpmv.CsrMV
     call goes through here, so a wrong dtype, device, stride or length is an MspmvError instead of
     a reinterpretation of memory.  x / y may be 1-D (CsrMV) or 2-D row-major (SpMM)."""
@@ -276,8 +281,9 @@ def _validate(values, row_offsets, column_indices, x, y, rows: int, cols: int, n
         if t.device != dev or not t.is_contiguous() or t.numel() < need:
             raise MspmvError(f"{what}: {name} must be a contiguous tensor on {dev} with at least {need} entries")
     if nnz > 0:
-        if values is None or values.dtype != y.dtype or values.device != dev or not values.is_contiguous() or values.numel() < nnz:
-            raise MspmvError(f"{what}: values must be a contiguous {y.dtype} tensor on {dev} with at least {nnz} entries")
+        vdt = y.dtype if values_dtype is None else values_dtype       # (csrmv_mixed: the matrix is stored narrower than y)
+        if values is None or values.dtype != vdt or values.device != dev or not values.is_contiguous() or values.numel() < nnz:
+            raise MspmvError(f"{what}: values must be a contiguous {vdt} tensor on {dev} with at least {nnz} entries")
     for t, name, need in ((x, "x", cols if x_rows is None else x_rows), (y, "y", rows if y_rows is None else y_rows)):
         if t is None:
             if need == 0 or (name == "x" and nnz == 0):
@@ -428,6 +434,66 @@ def csrmv(values, row_offsets, column_indices, x, y=None, num_cols: Optional[int
                                  rows, cols, nnz, stream=stream, debug_synchronous=debug_synchronous,
                                  alpha=alpha, beta=beta, _checked=True)
     _check(status, "mspmv_csrmv")
+    return y
+
+
+def _mixed_pair(values_dtype, x_dtype) -> str:
+    """suffix of the mspmv_csrmv_mixed_* entry points for (stored dtype of the matrix values, compute dtype of x and y)"""
+    import torch
+    if (values_dtype, x_dtype) == (torch.float32, torch.float64):
+        return "f32_f64"
+    if (values_dtype, x_dtype) == (torch.bfloat16, torch.float32):
+        return "bf16_f32"
+    raise MspmvError(f"csrmv_mixed: values / x must be (float32, float64) or (bfloat16, float32), got ({values_dtype}, {x_dtype}); "
+                     "equal dtypes go through csrmv")
+
+
+def csrmv_mixed(values, row_offsets, column_indices, x, y=None, num_cols: Optional[int] = None,
+                workspace: Optional[CsrMVWorkspace] = None, stream=None, alpha=None, beta=None,
+                debug_synchronous: bool = False):
+    """Mixed-precision CsrMV (mspmv_csrmv_mixed_*): y = alpha*A*x + beta*y with the matrix values STORED narrow -- float32
+    values with float64 x / y, or bfloat16 values with float32 x / y -- and widened in registers; x, y, alpha, beta and
+    every sum are in x's dtype.  Bit for bit what csrmv returns for values.to(x.dtype) (mspmv.h says when), on a third
+    less of a stream.  `workspace`: a CsrMVWorkspace of the COMPUTE dtype (x.dtype); a prepared one routes to
+    mspmv_csrmv_mixed_prepared_*.  Returns y."""
+    import torch
+    for t, name in ((values, "values"), (row_offsets, "row_offsets"), (column_indices, "column_indices"), (x, "x")):
+        if not isinstance(t, torch.Tensor):
+            raise MspmvError(f"csrmv_mixed: {name} must be a tensor")
+    pair = _mixed_pair(values.dtype, x.dtype)
+    if not values.is_cuda or not row_offsets.is_cuda or not column_indices.is_cuda or not x.is_cuda:
+        raise MspmvError("csrmv_mixed needs CUDA (HIP) tensors: the merge-path kernels only run on the GPU")
+    if row_offsets.dtype != torch.int32 or column_indices.dtype != torch.int32:
+        raise MspmvError("csrmv_mixed: row_offsets / column_indices must be int32")
+    if row_offsets.numel() < 1:
+        raise MspmvError("csrmv_mixed: row_offsets needs rows + 1 entries")
+    rows = row_offsets.numel() - 1
+    nnz = values.numel()
+    cols = int(num_cols) if num_cols is not None else x.numel()
+    if y is None:
+        y = torch.empty(rows, dtype=x.dtype, device=x.device)
+    if workspace is None:
+        _validate(values, row_offsets, column_indices, x, y, rows, cols, nnz, "csrmv_mixed", values_dtype=values.dtype)
+        workspace = CsrMVWorkspace(rows, nnz, x.dtype, device=x.device)
+    else:
+        if workspace.rows != rows or workspace.nnz != nnz or workspace.dtype != x.dtype:
+            raise MspmvError("csrmv_mixed: the workspace was sized for another matrix shape or compute precision")
+        if workspace.buffer.device != x.device:
+            raise MspmvError("csrmv_mixed: the workspace lives on another device")
+        checked = workspace._checked
+        if not (checked is not None and checked[0] is values and checked[1] is row_offsets and checked[2] is column_indices
+                and checked[3] is x and checked[4] is y and checked[5] == cols):
+            _validate(values, row_offsets, column_indices, x, y, rows, cols, nnz, "csrmv_mixed", values_dtype=values.dtype)
+            workspace._checked = (values, row_offsets, column_indices, x, y, cols)
+    prepared = workspace.is_prepared_for(row_offsets, rows, nnz, x.dtype)
+    lib = load_library()
+    fn = getattr(lib, ("mspmv_csrmv_mixed_prepared_" if prepared else "mspmv_csrmv_mixed_") + pair)
+    ct = ctypes.c_double if x.dtype == torch.float64 else ctypes.c_float
+    size = ctypes.c_size_t(workspace.bytes)
+    status = fn(ctypes.c_void_p(workspace.buffer.data_ptr()), ctypes.byref(size), _ptr(values), _ptr(row_offsets),
+                _ptr(column_indices), _ptr(x), _ptr(y), rows, cols, nnz, ct(1.0 if alpha is None else alpha),
+                ct(0.0 if beta is None else beta), _stream_handle(stream), int(bool(debug_synchronous)))
+    _check(int(status), fn.__name__)
     return y
 
 

@@ -485,19 +485,28 @@ struct CallPlan {
     int max_polls, lean_avg;     // of the one-launch kernel: LookBack::max_polls, consume_tile_rows
 };
 
-static CallPlan resolve_call(int rows, int cols, int nnz, int value_bytes, const CallExtra &ex, uint64_t temp_offered, bool aligned)
+// value_bytes: the COMPUTE type (x, y, the products, every sum) -- what every decision that shapes the association of the sums is
+// taken on (tile shape, one launch or classic, long_rows_rule); mv_bytes (0 = the same): the type the matrix values are STORED in
+// (mixed precision, mspmv_csrmv_mixed_*), seen only by what counts bytes moved: stream_bytes, hence nt.  A mixed call takes none of
+// the special forms: no skinny layout (the size query still answers what the compute type's answers: one buffer serves both), no
+// compact front end, never a column-band candidate.
+static CallPlan resolve_call(int rows, int cols, int nnz, int value_bytes, const CallExtra &ex, uint64_t temp_offered, bool aligned, int mv_bytes = 0)
 {
     const Tune &t = ex.tune;
     CallPlan pl;
+    const bool mixed = mv_bytes != 0 && mv_bytes != value_bytes;
+    if (!mixed) mv_bytes = value_bytes;
     pl.phase = ex.phase; pl.tile_map = ex.tile_map; pl.num_cols = cols;
-    pl.stream_bytes = (unsigned long long) nnz * (value_bytes + 4) + 4ull * rows;
+    pl.stream_bytes = (unsigned long long) nnz * (mv_bytes + 4) + 4ull * rows;
     pl.L = make_layout(rows, nnz, value_bytes, t);
     pl.base = 0; pl.query_bytes = pl.L.total; pl.skinny = false;
     // 16-byte streaming needs 16-byte aligned array bases (hipMalloc gives 256) and at
     // least one full 4-element chunk in each array
     const bool streams16 = aligned && nnz >= 4 && rows >= 3;
     // (without a column count: the default layout, and a size large enough for the small shape if the rule holds for SOME column count)
-    if (ex.allow_skinny && skinny_rule(rows, cols == COLS_UNKNOWN ? 1 : cols, nnz, value_bytes, t, pl.L, pl.stream_bytes)) {
+    // (the rule is asked with the COMPUTE type's stream: a mixed call answers the size query exactly as
+    //  mspmv_get_launch_info does, i.e. without regard to the column count -- one buffer sized there serves both calls)
+    if (ex.allow_skinny && skinny_rule(rows, cols == COLS_UNKNOWN || mixed ? 1 : cols, nnz, value_bytes, t, pl.L, (unsigned long long) nnz * (value_bytes + 4) + 4ull * rows)) {
         // The small-shape layout lives BEHIND the default one in temp storage, so a call that takes it never touches the default
         // layout's coordinates (what mspmv_csrmv_prepare stored, what the classic pipeline of a prepared call trusts): the size query
         // asks for both; a caller that sized its storage without the column count (mspmv_get_launch_info) and brings less runs the
@@ -505,7 +514,7 @@ static CallPlan resolve_call(int rows, int cols, int nnz, int value_bytes, const
         // verified, whatever the region held before).
         const Layout S = make_layout(rows, nnz, value_bytes, t, true);
         pl.query_bytes = pl.L.total + S.total;
-        if (cols != COLS_UNKNOWN && temp_offered >= pl.query_bytes && streams16 && S.snap) { pl.base = pl.L.total; pl.L = S; pl.skinny = true; }
+        if (!mixed && cols != COLS_UNKNOWN && temp_offered >= pl.query_bytes && streams16 && S.snap) { pl.base = pl.L.total; pl.L = S; pl.skinny = true; }
     }
     const Layout &L = pl.L;
     pl.vec = streams16 && !(L.flags & MSPMV_TUNE_NO_VEC);
@@ -516,7 +525,8 @@ static CallPlan resolve_call(int rows, int cols, int nnz, int value_bytes, const
     pl.nt = (L.flags & MSPMV_TUNE_FORCE_NT) || (!(L.flags & MSPMV_TUNE_FORCE_TEMPORAL) && pl.stream_bytes > (256ull << 20));
     // a tiny x is gathered from LDS by the vectorised tile kernels (dynamic shared memory of the launch)
     pl.x_lds = (cols > 0 && (size_t) cols * (size_t) value_bytes <= (size_t) X_LDS_MAX_BYTES && !(L.flags & MSPMV_TUNE_NO_XLDS)) ? cols : 0;
-    pl.band_passes = band_passes_for(L, (long long) cols * value_bytes, value_bytes, rows, nnz, pl.stream_bytes, ex, &pl.band_force);
+    pl.band_force = 0;
+    pl.band_passes = mixed ? 0 : band_passes_for(L, (long long) cols * value_bytes, value_bytes, rows, nnz, pl.stream_bytes, ex, &pl.band_force);
     pl.band_cols = pl.band_passes > 1 ? (cols + pl.band_passes - 1) / pl.band_passes : 0;
     pl.tdm_shift = tdm_shift_for(cols, value_bytes, pl.band_passes, ex);
     pl.tdm_bands = pl.tdm_shift > 0 ? (int) (((long long) cols + (1LL << pl.tdm_shift) - 1) >> pl.tdm_shift) : 0;
@@ -528,7 +538,7 @@ static CallPlan resolve_call(int rows, int cols, int nnz, int value_bytes, const
     // small problems (compact_max_tiles), and the skinny layout whatever its tile count: the one-launch kernel behind its compact front
     // end (kernels: compact_front) -- bit for bit the same y
     pl.compact_cap = pl.skinny ? 0x7fffffff : t.compact_tiles > 0 ? t.compact_tiles : t.compact_tiles < 0 ? 0 : compact_max_tiles(value_bytes);
-    pl.compact = L.shape.block == COMPACT_BLOCK && L.shape.ipt == COMPACT_IPT && !pl.nt && ex.tile_map == 0 && L.num_tiles > 1 && L.num_tiles <= pl.compact_cap &&
+    pl.compact = !mixed && L.shape.block == COMPACT_BLOCK && L.shape.ipt == COMPACT_IPT && !pl.nt && ex.tile_map == 0 && L.num_tiles > 1 && L.num_tiles <= pl.compact_cap &&
                  (unsigned long long) cols * value_bytes < (1ull << 32) && (unsigned long long) nnz * value_bytes < (1ull << 32) &&
                  (unsigned long long) rows * 4ull < (1ull << 32) - 8;      // (32-bit byte offsets in the fast lane: every array < 4 GB)
     // XCD-chunked block -> tile mapping: runs of 2^6 consecutive tiles per XCD.  Measured against
@@ -548,8 +558,8 @@ static CallPlan resolve_call(int rows, int cols, int nnz, int value_bytes, const
 
 // ---- THE STAGES OF A CALL (run_shape puts them together) ----
 // what they share: the resolved plan, the kernels' parameters, and the call's regions of temp storage (`base` = where the layout starts)
-template <typename V> struct Stage {
-    const CallPlan &pl; const Params<V> &p;
+template <typename V, typename MV = V> struct Stage {
+    const CallPlan &pl; const Params<V, MV> &p;
     char *base; Coord *coords; Carry<V> *carries; int *rstart;
     bool axpby; hipStream_t stream; int debug_sync;
 };
@@ -558,10 +568,10 @@ template <typename V> struct Stage {
 // the first of the classic launches, and all that mspmv_csrmv_prepare runs.  `band`: the call is a candidate for column bands, so
 // 64 sampled windows of column indices decide, on the device, whether the tile kernel (its BAND variant) runs its ordinary body or
 // the bands.
-template <typename V, int BLOCK, int IPT>
-static hipError_t coords_stage(const Stage<V> &c, bool band, const BandDetectArgs &da)
+template <typename V, int BLOCK, int IPT, typename MV = V>
+static hipError_t coords_stage(const Stage<V, MV> &c, bool band, const BandDetectArgs &da)
 {
-    const CallPlan &pl = c.pl; const Params<V> &p = c.p; const int num_tiles = pl.L.num_tiles;
+    const CallPlan &pl = c.pl; const Params<V, MV> &p = c.p; const int num_tiles = pl.L.num_tiles;
     BoundaryOut bo; bo.coords = c.coords; bo.rstart = c.rstart;
     bool band_sampled = false;
     if (pl.phase == PHASE_SKIP_COORDS) {
@@ -596,10 +606,10 @@ static hipError_t coords_stage(const Stage<V> &c, bool band, const BandDetectArg
 }
 
 // ---- ONE launch: row-snapped tiles on verified coordinate hints (tile_kernel_snap) ----
-template <typename V, int BLOCK, int IPT>
-static hipError_t one_launch_stage(const Stage<V> &c)
+template <typename V, int BLOCK, int IPT, typename MV = V>
+static hipError_t one_launch_stage(const Stage<V, MV> &c)
 {
-    const CallPlan &pl = c.pl; const Params<V> &p = c.p; const Layout &L = pl.L;
+    const CallPlan &pl = c.pl; const Params<V, MV> &p = c.p; const Layout &L = pl.L;
     const unsigned long long tag = next_call_tag();
     LookBack lb; lb.rec = reinterpret_cast<unsigned long long *>(c.base + L.pub_off);
     lb.tag_a = (unsigned) (tag >> 32) | 1u; lb.tag_b = (unsigned) tag; lb.error = reinterpret_cast<int *>(c.base + L.err_off);
@@ -610,7 +620,7 @@ static hipError_t one_launch_stage(const Stage<V> &c)
     //  variant needs nothing else from it: the reference's timing loop is bound by the enqueueing thread for small problems)
     hipError_t launched = hipSuccess;
     bool compact = false;
-    if constexpr (BLOCK == COMPACT_BLOCK && IPT == COMPACT_IPT) {
+    if constexpr (BLOCK == COMPACT_BLOCK && IPT == COMPACT_IPT && std::is_same<V, MV>::value) {      // (never for mixed precision: resolve_call)
         compact = pl.compact;
         if (compact) {
             // (a tiny x is gathered from memory here, not from an LDS copy: the copy pays on matrices that stream from HBM, a problem of
@@ -629,9 +639,9 @@ static hipError_t one_launch_stage(const Stage<V> &c)
         // (dev library: MSPMV_SNAP_MAP in the environment, read once: 30 = one contiguous tile range per XCD for every one-launch call, 0 .. 8 = that run length)
         static const int env_map = env_int("MSPMV_SNAP_MAP", -1);
         const int chunk_log2 = pl.tile_map ? pl.tile_map : env_map == TILE_MAP_CONTIGUOUS_CODE ? env_map
-                             : safe_chunk_log2(env_map >= 0 && env_map <= 8 ? env_map : pl.chunk_log2, resident_blocks(tile_kernel_snap<V, BLOCK, IPT, true, true>, BLOCK, snap_cache));
+                             : safe_chunk_log2(env_map >= 0 && env_map <= 8 ? env_map : pl.chunk_log2, resident_blocks(tile_kernel_snap<V, BLOCK, IPT, true, true, false, MV>, BLOCK, snap_cache));
         launched = with_bools([&](auto ax, auto ntf) {
-            return launch_exact(tile_kernel_snap<V, BLOCK, IPT, ax.value, ntf.value>, dim3(grid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), c.stream,
+            return launch_exact(tile_kernel_snap<V, BLOCK, IPT, ax.value, ntf.value, false, MV>, dim3(grid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), c.stream,
                                 c.coords, c.rstart, L.num_tiles, chunk_log2, p, c.carries, lb, pl.lean_avg);
         }, c.axpby, pl.nt);
     }
@@ -642,11 +652,11 @@ static hipError_t one_launch_stage(const Stage<V> &c)
 
 // Band set-up of a classic call that is a candidate for column bands (plan: band_passes > 1): which blocks of the tile launch run
 // them, and the slot of the clock-scheduled form.  grid == 0 (no_bands): the call runs without.
-template <typename V, int BLOCK, int IPT>
-static BandArgs band_setup(const Stage<V> &c)
+template <typename V, int BLOCK, int IPT, typename MV = V>
+static BandArgs band_setup(const Stage<V, MV> &c)
 {
     BandArgs ba = no_bands();
-    if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V))) {
+    if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V)) && std::is_same<V, MV>::value) {
         const CallPlan &pl = c.pl; const Params<V> &p = c.p; const Layout &L = pl.L;
         if (!pl.vec || pl.band_passes <= 1 || pl.phase == PHASE_COORDS_ONLY) return ba;
         // the passes are run by 4 (fp64: 5) blocks per CU, or as many as are resident at once if that is fewer: the gathers
@@ -691,14 +701,14 @@ static BandArgs band_setup(const Stage<V> &c)
 
 // The classic tile launch: tile_kernel_vec (plain; its BAND variant when band_setup found blocks for the bands, TDM: the clocked
 // form), or the dword-per-lane tile_kernel for arrays that cannot be streamed 16 bytes at a time.
-template <typename V, int BLOCK, int IPT>
-static hipError_t classic_tiles_stage(const Stage<V> &c, const BandArgs &ba)
+template <typename V, int BLOCK, int IPT, typename MV = V>
+static hipError_t classic_tiles_stage(const Stage<V, MV> &c, const BandArgs &ba)
 {
-    const CallPlan &pl = c.pl; const Params<V> &p = c.p; const Layout &L = pl.L;
+    const CallPlan &pl = c.pl; const Params<V, MV> &p = c.p; const Layout &L = pl.L;
     const unsigned grid = (unsigned) L.num_tiles;
     if (!pl.vec) {
         with_bools([&](auto ax) {
-            hipLaunchKernelGGL((tile_kernel<V, BLOCK, IPT, ax.value>), dim3(grid), dim3(BLOCK), 0, c.stream, p, c.coords, c.carries, L.num_tiles);
+            hipLaunchKernelGGL((tile_kernel<V, BLOCK, IPT, ax.value, MV>), dim3(grid), dim3(BLOCK), 0, c.stream, p, c.coords, c.carries, L.num_tiles);
         }, c.axpby);
         return after_launch(c.stream, c.debug_sync, "tile_kernel", grid, BLOCK);
     }
@@ -709,9 +719,9 @@ static hipError_t classic_tiles_stage(const Stage<V> &c, const BandArgs &ba)
     const size_t xl = (size_t) p.x_lds * sizeof(V);
     bool launched = false;
 #ifdef MSPMV_DEV
-    launched = launch_dev_variant<V, BLOCK, IPT>(L, p, c.axpby, pl.nt, c.coords, c.carries, pl.chunk_log2, c.stream);
+    if constexpr (std::is_same<V, MV>::value) launched = launch_dev_variant<V, BLOCK, IPT>(L, p, c.axpby, pl.nt, c.coords, c.carries, pl.chunk_log2, c.stream);
 #endif
-    if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V))) {
+    if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V)) && std::is_same<V, MV>::value) {
         if (ba.grid > 0 && !launched) {
             with_bools([&](auto ax, auto ntf, auto td) {
                 hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, ax.value, false, ntf.value, 0, false, true, td.value>), dim3(grid), dim3(BLOCK), xl, c.stream,
@@ -722,7 +732,7 @@ static hipError_t classic_tiles_stage(const Stage<V> &c, const BandArgs &ba)
     }
     if (!launched)
         with_bools([&](auto ax, auto ntf) {
-            hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, ax.value, false, ntf.value, 0, false>), dim3(grid), dim3(BLOCK), xl, c.stream,
+            hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, ax.value, false, ntf.value, 0, false, false, false, MV>), dim3(grid), dim3(BLOCK), xl, c.stream,
                                p, c.coords, c.carries, L.num_tiles, pl.chunk_log2, ba);
         }, c.axpby, pl.nt);
     return after_launch(c.stream, c.debug_sync, "tile_kernel_vec", grid, BLOCK);
@@ -730,10 +740,10 @@ static hipError_t classic_tiles_stage(const Stage<V> &c, const BandArgs &ba)
 
 // Carry fix-up (not needed for a single tile: its carry is the (rows, 0) pair; nor when the self-searching
 // tiles of a small problem have added the carries themselves)
-template <typename V>
-static hipError_t fixup_stage(const Stage<V> &c)
+template <typename V, typename MV = V>
+static hipError_t fixup_stage(const Stage<V, MV> &c)
 {
-    const Params<V> &p = c.p; const Layout &L = c.pl.L;
+    const Params<V, MV> &p = c.p; const Layout &L = c.pl.L;
     if (L.num_tiles <= 1) return hipSuccess;
     if (L.flags & MSPMV_TUNE_ATOMIC_FIX) {
         const unsigned grid = (unsigned) ((L.num_tiles + FIX_BLOCK - 1) / FIX_BLOCK);
@@ -761,11 +771,11 @@ static hipError_t fixup_stage(const Stage<V> &c)
 }
 
 // One call in tile shape BLOCK x IPT: the one launch, or the classic three; the profiler's marks bracket search | tiles | fix-up
-template <typename V, int BLOCK, int IPT>
-static hipError_t run_shape(const CallPlan &pl, char *base, const Params<V> &p, bool axpby, hipStream_t stream, int debug_sync)
+template <typename V, int BLOCK, int IPT, typename MV = V>
+static hipError_t run_shape(const CallPlan &pl, char *base, const Params<V, MV> &p, bool axpby, hipStream_t stream, int debug_sync)
 {
     const Layout &L = pl.L;
-    const Stage<V> c{pl, p, base, reinterpret_cast<Coord *>(base + L.coords_off), reinterpret_cast<Carry<V> *>(base + L.carries_off),
+    const Stage<V, MV> c{pl, p, base, reinterpret_cast<Coord *>(base + L.coords_off), reinterpret_cast<Carry<V> *>(base + L.carries_off),
                      reinterpret_cast<int *>(base + L.rstart_off), axpby, stream, debug_sync};
     // a profiler slot is taken only by calls that run all the passes it brackets
     const int slot = pl.phase == PHASE_COORDS_ONLY ? -1 : prof_take_slot();
@@ -788,7 +798,7 @@ static hipError_t run_shape(const CallPlan &pl, char *base, const Params<V> &p, 
     prof_mark(stream, slot, 1);
     MSPMV_CHECK((classic_tiles_stage<V, BLOCK, IPT>(c, ba)));
     prof_mark(stream, slot, 2);
-    MSPMV_CHECK(fixup_stage<V>(c));
+    MSPMV_CHECK(fixup_stage(c));
     prof_mark(stream, slot, 3);
     return hipSuccess;
 }
@@ -829,15 +839,31 @@ hipError_t dispatch_shape<double>(const CallPlan &pl, char *base, const Params<d
     return hipErrorInvalidValue;
 }
 
-template <typename V>
-int csrmv_call(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_t *d_row_offsets, const int32_t *d_cols,
+// mixed precision (stored type -> compute type): the two product shapes
+static hipError_t dispatch_shape_mixed(const CallPlan &pl, char *base, const Params<double, float> &p, bool axpby, hipStream_t stream, int debug_sync)
+{
+    MSPMV_SHAPE_CASE(double, 256, 7)
+    MSPMV_SHAPE_CASE(double, 256, 11)
+    return hipErrorInvalidValue;
+}
+static hipError_t dispatch_shape_mixed(const CallPlan &pl, char *base, const Params<float, bf16> &p, bool axpby, hipStream_t stream, int debug_sync)
+{
+    MSPMV_SHAPE_CASE(float, 256, 7)
+    MSPMV_SHAPE_CASE(float, 256, 11)
+    return hipErrorInvalidValue;
+}
+
+template <typename V, typename MV>
+static int csrmv_call_mv(void *d_temp, size_t *temp_bytes, const MV *d_values, const int32_t *d_row_offsets, const int32_t *d_cols,
                const V *d_x, V *d_y, int32_t rows, int32_t cols, int32_t nnz, V alpha, V beta, bool axpby,
                hipStream_t stream, int debug_sync, const CallExtra &ex)
 {
     if (!temp_bytes || rows < 0 || cols < 0 || nnz < 0) return hipErrorInvalidValue;
     if ((long long) rows + nnz > MAX_ITEMS) return hipErrorInvalidValue;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(d_values) | reinterpret_cast<uintptr_t>(d_cols) | reinterpret_cast<uintptr_t>(d_row_offsets)) & 15) == 0;
-    const CallPlan pl = resolve_call(rows, cols, nnz, (int) sizeof(V), ex, d_temp ? (uint64_t) *temp_bytes : 0, aligned);
+    // (the value stream is read one 4-element chunk per load: 16-byte loads for 4- and 8-byte values, 8-byte loads for bf16)
+    constexpr uintptr_t value_align = sizeof(MV) >= 4 ? 15 : 4 * sizeof(MV) - 1;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(d_cols) | reinterpret_cast<uintptr_t>(d_row_offsets)) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_values) & value_align) == 0;
+    const CallPlan pl = resolve_call(rows, cols, nnz, (int) sizeof(V), ex, d_temp ? (uint64_t) *temp_bytes : 0, aligned, (int) sizeof(MV));
     if (d_temp == nullptr) {                      // size query (dispatch_spmv_orig.cuh:651-655)
         *temp_bytes = (size_t) pl.query_bytes;
         return hipSuccess;
@@ -849,12 +875,20 @@ int csrmv_call(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_
     if (rows == 0) return hipSuccess;             // nothing to write
     if (ex.phase == PHASE_COORDS_ONLY) { if (!d_row_offsets) return hipErrorInvalidValue; }
     else if (!d_row_offsets || !d_y || (nnz > 0 && (!d_values || !d_cols || !d_x))) return hipErrorInvalidValue;
-    Params<V> p;
+    Params<V, MV> p;
     p.values = d_values; p.row_end = d_row_offsets + 1; p.cols = d_cols; p.x = d_x; p.y = d_y;
     p.rows = rows; p.nnz = nnz; p.alpha = alpha; p.beta = beta;
     p.x_lds = pl.x_lds;
     p.band_lo = 0; p.band_len = 0; p.band_pass = 0;
-    return (int) dispatch_shape<V>(pl, static_cast<char *>(d_temp) + pl.base, p, axpby, stream, debug_sync);
+    if constexpr (std::is_same<V, MV>::value) return (int) dispatch_shape<V>(pl, static_cast<char *>(d_temp) + pl.base, p, axpby, stream, debug_sync);
+    else return (int) dispatch_shape_mixed(pl, static_cast<char *>(d_temp) + pl.base, p, axpby, stream, debug_sync);
+}
+template <typename V>
+int csrmv_call(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_t *d_row_offsets, const int32_t *d_cols,
+               const V *d_x, V *d_y, int32_t rows, int32_t cols, int32_t nnz, V alpha, V beta, bool axpby,
+               hipStream_t stream, int debug_sync, const CallExtra &ex)
+{
+    return csrmv_call_mv<V, V>(d_temp, temp_bytes, d_values, d_row_offsets, d_cols, d_x, d_y, rows, cols, nnz, alpha, beta, axpby, stream, debug_sync, ex);
 }
 template int csrmv_call<float>(void *, size_t *, const float *, const int32_t *, const int32_t *, const float *, float *, int32_t,
                                int32_t, int32_t, float, float, bool, hipStream_t, int, const CallExtra &);
@@ -863,14 +897,14 @@ template int csrmv_call<double>(void *, size_t *, const double *, const int32_t 
 
 uint64_t csrmv_temp_bytes(int32_t rows, int32_t nnz, int32_t value_bytes) { return resolve_call(rows, COLS_UNKNOWN, nnz, value_bytes, CallExtra{}, 0, true).query_bytes; }
 
-template <typename V>
-static int csrmv_impl(void *d_temp, size_t *temp_bytes, const V *d_values, const int32_t *d_row_offsets,
+template <typename V, typename MV = V>
+static int csrmv_impl(void *d_temp, size_t *temp_bytes, const MV *d_values, const int32_t *d_row_offsets,
                       const int32_t *d_cols, const V *d_x, V *d_y, int32_t rows, int32_t cols, int32_t nnz, V alpha,
                       V beta, bool axpby, mspmv_stream_t stream_, int debug_sync, int phase = PHASE_ALL)
 {
     CallExtra ex; ex.phase = phase; ex.tune = thread_tune((int) sizeof(V));
     ex.allow_skinny = phase != PHASE_COORDS_ONLY;       // (stateless and prepared calls pick their shape by the same rule: bitwise the same y)
-    return csrmv_call<V>(d_temp, temp_bytes, d_values, d_row_offsets, d_cols, d_x, d_y, rows, cols, nnz, alpha, beta, axpby,
+    return csrmv_call_mv<V, MV>(d_temp, temp_bytes, d_values, d_row_offsets, d_cols, d_x, d_y, rows, cols, nnz, alpha, beta, axpby,
                          reinterpret_cast<hipStream_t>(stream_), debug_sync, ex);
 }
 
@@ -1032,7 +1066,7 @@ static int csrmm_impl(void *d_temp, size_t *temp_bytes, const T *d_values, const
     size_t need = (size_t) L.total;
     if (as_csrmv) {
         size_t mv = 0;
-        const int st = csrmv_impl<T>(nullptr, &mv, nullptr, nullptr, nullptr, nullptr, nullptr, rows, cols, nnz, alpha, beta, true, stream_, 0);
+        const int st = csrmv_impl<T, T>(nullptr, &mv, nullptr, nullptr, nullptr, nullptr, nullptr, rows, cols, nnz, alpha, beta, true, stream_, 0);
         if (st != 0) return st;
         need = std::max(need, mv);
     }
@@ -1132,10 +1166,10 @@ int mspmv_csrmv_prepare(void *d_temp, size_t *temp_bytes, const int32_t *d_row_o
                         int32_t value_bytes, mspmv_stream_t stream, int debug_sync)
 {
     if (value_bytes == 4)
-        return csrmv_impl<float>(d_temp, temp_bytes, nullptr, d_row_offsets, nullptr, nullptr, nullptr, rows, 0, nnz, 1.0f, 0.0f,
+        return csrmv_impl<float, float>(d_temp, temp_bytes, nullptr, d_row_offsets, nullptr, nullptr, nullptr, rows, 0, nnz, 1.0f, 0.0f,
                                  false, stream, debug_sync, PHASE_COORDS_ONLY);
     if (value_bytes == 8)
-        return csrmv_impl<double>(d_temp, temp_bytes, nullptr, d_row_offsets, nullptr, nullptr, nullptr, rows, 0, nnz, 1.0, 0.0,
+        return csrmv_impl<double, double>(d_temp, temp_bytes, nullptr, d_row_offsets, nullptr, nullptr, nullptr, rows, 0, nnz, 1.0, 0.0,
                                   false, stream, debug_sync, PHASE_COORDS_ONLY);
     return hipErrorInvalidValue;
 }
@@ -1156,6 +1190,42 @@ int mspmv_csrmv_prepared_f64(void *d_temp, size_t *temp_bytes, const double *d_v
     if (!d_temp) return hipErrorInvalidValue;
     return csrmv_impl<double>(d_temp, temp_bytes, d_values, d_row_offsets, d_column_indices, d_x, d_y, rows, cols, nnz,
                               alpha, beta, !(alpha == 1.0 && beta == 0.0), stream, debug_sync, PHASE_SKIP_COORDS);
+}
+
+// Mixed precision: the matrix values stored narrow, everything else in the compute type (mspmv.h).  alpha = 1, beta = 0 runs the
+// plain kernels, as in the prepared calls.
+int mspmv_csrmv_mixed_f32_f64(void *d_temp, size_t *temp_bytes, const float *d_values, const int32_t *d_row_offsets,
+                              const int32_t *d_column_indices, const double *d_x, double *d_y, int32_t rows, int32_t cols,
+                              int32_t nnz, double alpha, double beta, mspmv_stream_t stream, int debug_sync)
+{
+    return csrmv_impl<double, float>(d_temp, temp_bytes, d_values, d_row_offsets, d_column_indices, d_x, d_y, rows, cols, nnz,
+                                     alpha, beta, true, stream, debug_sync);
+}
+
+int mspmv_csrmv_mixed_bf16_f32(void *d_temp, size_t *temp_bytes, const uint16_t *d_values, const int32_t *d_row_offsets,
+                               const int32_t *d_column_indices, const float *d_x, float *d_y, int32_t rows, int32_t cols,
+                               int32_t nnz, float alpha, float beta, mspmv_stream_t stream, int debug_sync)
+{
+    return csrmv_impl<float, bf16>(d_temp, temp_bytes, reinterpret_cast<const bf16 *>(d_values), d_row_offsets, d_column_indices, d_x, d_y, rows, cols, nnz,
+                                   alpha, beta, true, stream, debug_sync);
+}
+
+int mspmv_csrmv_mixed_prepared_f32_f64(void *d_temp, size_t *temp_bytes, const float *d_values, const int32_t *d_row_offsets,
+                                       const int32_t *d_column_indices, const double *d_x, double *d_y, int32_t rows, int32_t cols,
+                                       int32_t nnz, double alpha, double beta, mspmv_stream_t stream, int debug_sync)
+{
+    if (!d_temp) return hipErrorInvalidValue;
+    return csrmv_impl<double, float>(d_temp, temp_bytes, d_values, d_row_offsets, d_column_indices, d_x, d_y, rows, cols, nnz,
+                                     alpha, beta, !(alpha == 1.0 && beta == 0.0), stream, debug_sync, PHASE_SKIP_COORDS);
+}
+
+int mspmv_csrmv_mixed_prepared_bf16_f32(void *d_temp, size_t *temp_bytes, const uint16_t *d_values, const int32_t *d_row_offsets,
+                                        const int32_t *d_column_indices, const float *d_x, float *d_y, int32_t rows, int32_t cols,
+                                        int32_t nnz, float alpha, float beta, mspmv_stream_t stream, int debug_sync)
+{
+    if (!d_temp) return hipErrorInvalidValue;
+    return csrmv_impl<float, bf16>(d_temp, temp_bytes, reinterpret_cast<const bf16 *>(d_values), d_row_offsets, d_column_indices, d_x, d_y, rows, cols, nnz,
+                                   alpha, beta, !(alpha == 1.0f && beta == 0.0f), stream, debug_sync, PHASE_SKIP_COORDS);
 }
 
 int mspmv_csrmm_f32(void *d_temp, size_t *temp_bytes, const float *d_values, const int32_t *d_row_offsets,

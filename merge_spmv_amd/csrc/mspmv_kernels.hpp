@@ -43,6 +43,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <tuple>
+#include <type_traits>
 #include <utility>
 
 namespace mspmv {
@@ -63,9 +64,12 @@ template <typename V> struct Carry;
 template <> struct alignas(8) Carry<float> { int key; float value; };
 template <> struct alignas(16) Carry<double> { int key; int pad; double value; };
 
-template <typename V>
+// MV: the type the matrix values are STORED in (mixed precision: float values in a double product, bf16 values in a float one).  Every
+// value is widened to V in registers right before its multiply (widen<V>); x, y, alpha, beta, the products and every sum are V.
+struct bf16 { unsigned short bits; };         // the upper 16 bits of an IEEE fp32
+template <typename V, typename MV = V>
 struct Params {
-    const V *__restrict__ values;
+    const MV *__restrict__ values;
     const int *__restrict__ row_end;  // d_row_offsets + 1 (device_spmv.cuh:148)
     const int *__restrict__ cols;
     const V *__restrict__ x;
@@ -625,6 +629,23 @@ template <> struct Vec4<int> { int4v v; __device__ __forceinline__ int get(int i
 template <> struct Vec4<float> { float4v v; __device__ __forceinline__ float get(int i) const { return v[i]; } };
 template <> struct Vec4<double> { double2v a, b; __device__ __forceinline__ double get(int i) const { return i < 2 ? a[i] : b[i - 2]; } };
 
+template <> struct Vec4<bf16> {
+    int2v v;
+    __device__ __forceinline__ bf16 get(int i) const { bf16 r; r.bits = (unsigned short) ((unsigned) v[i >> 1] >> (16 * (i & 1))); return r; }
+};
+// matrix value -> compute type: exact (every fp32 is an fp64, every bf16 an fp32), so a mixed call's products are those of the widened matrix
+template <typename V> __device__ __forceinline__ V widen(V v) { return v; }
+template <typename V> __device__ __forceinline__ V widen(bf16 v) { return __builtin_bit_cast(float, (unsigned) v.bits << 16); }
+template <typename V, typename = typename std::enable_if<sizeof(V) == 8>::type> __device__ __forceinline__ V widen(float v) { return (V) v; }
+
+template <bool NT>
+__device__ __forceinline__ bf16 ld_stream(const bf16 *p) { bf16 r; r.bits = ld_stream<NT>(&p->bits); return r; }
+template <bool NT>
+__device__ __forceinline__ Vec4<bf16> ld_stream4(const bf16 *p)       // 8 bytes per chunk
+{
+    Vec4<bf16> r; const int2v *q = reinterpret_cast<const int2v *>(p);
+    r.v = NT ? __builtin_nontemporal_load(q) : *q; return r;
+}
 template <bool NT>
 __device__ __forceinline__ Vec4<int> ld_stream4(const int *p)
 {
@@ -692,8 +713,8 @@ __device__ __forceinline__ int swz_prod(int i) { return i ^ (((i >> 5) & 7) << 2
 //               array for the last tile);
 //   s_prod[j] = values[j] * x[cols[j]] for the tile's nonzeros.
 // ---------------------------------------------------------------------------
-template <typename V, int BLOCK, int IPT, bool AXPBY, bool SWZ = false>
-__device__ __forceinline__ void consume_tile_lds(const Params<V> &p, const Coord c0, int tile_rows, int tile_nnz,
+template <typename V, int BLOCK, int IPT, bool AXPBY, bool SWZ = false, typename MV = V>
+__device__ __forceinline__ void consume_tile_lds(const Params<V, MV> &p, const Coord c0, int tile_rows, int tile_nnz,
                                                  const int *s_end, const V *s_prod, V *s_y, int *s_wave_key,
                                                  V *s_wave_val, Carry<V> *__restrict__ carry_out, int pshift = 0)
 {
@@ -908,11 +929,11 @@ __device__ __forceinline__ V lb_take_block(const LookBack &lb, int count, V *s_w
 // What the records of tiles [first piece, this tile) add up to, computed from the matrix instead: the products of the
 // nonzeros [j0, j1) of the row that ends in this tile (from the row's first nonzero to the tile's first) -- the path of a
 // consumer whose poll ran out.  Whole block (barriers inside); fixed order; the result on every thread.
-template <typename V, int BLOCK>
-__device__ __forceinline__ V recompute_row_head(const Params<V> &p, int j0, int j1, V *s_wave_val)
+template <typename V, int BLOCK, typename MV = V>
+__device__ __forceinline__ V recompute_row_head(const Params<V, MV> &p, int j0, int j1, V *s_wave_val)
 {
     V part = 0;
-    for (int j = j0 + (int) threadIdx.x; j < j1; j += BLOCK) part += p.values[j] * p.x[p.cols[j]];
+    for (int j = j0 + (int) threadIdx.x; j < j1; j += BLOCK) part += widen<V>(p.values[j]) * p.x[p.cols[j]];
 #pragma unroll
     for (int d = 1; d < WAVE; d <<= 1) part += __shfl_xor(part, d, WAVE);
     __syncthreads();                                   // (s_wave_val may still be read by a take that preceded)
@@ -1028,8 +1049,8 @@ __device__ __forceinline__ V block_exclusive_segsum(bool flag, V val, int *s_wav
     return lane == 0 ? pv : (ef ? ev : pv + ev);
 }
 
-template <typename V, int BLOCK, int IPT, bool AXPBY, int LB_BATCH = 1>
-__device__ __forceinline__ void consume_tile_flags(const Params<V> &p, const Coord c0, int tile_rows, int tile_nnz,
+template <typename V, int BLOCK, int IPT, bool AXPBY, int LB_BATCH = 1, typename MV = V>
+__device__ __forceinline__ void consume_tile_flags(const Params<V, MV> &p, const Coord c0, int tile_rows, int tile_nnz,
                                                    const end16_t *s_end, V *s_prod_raw, unsigned *s_flag,
                                                    int *s_wave_flag, V *s_wave_val, Carry<V> *__restrict__ carry_out,
                                                    int pshift, unsigned long long *tr = nullptr, const LookBack *lb = nullptr,
@@ -1337,8 +1358,8 @@ __device__ __forceinline__ void lean_long_rows(const V *s_prod, int pos, int len
 }
 
 constexpr int LEAN_BATCH = 8;          // products of a row requested before any is looked at
-template <typename V, int BLOCK, int IPT, bool AXPBY>
-__device__ __forceinline__ void consume_tile_rows(const Params<V> &p, const Coord c0, int tile_rows, const end16_t *s_end,
+template <typename V, int BLOCK, int IPT, bool AXPBY, typename MV = V>
+__device__ __forceinline__ void consume_tile_rows(const Params<V, MV> &p, const Coord c0, int tile_rows, const end16_t *s_end,
                                                   const V *s_prod_raw, int pshift, Carry<V> *__restrict__ carry_out,
                                                   unsigned long long *tr = nullptr)
 {
@@ -1430,8 +1451,8 @@ __device__ __forceinline__ void consume_tile_rows(const Params<V> &p, const Coor
 // ref: DeviceSpmvKernel / AgentSpmv::ConsumeTile, dispatch_spmv_orig.cuh:157-186,
 // agent_spmv_orig.cuh:413-639,856-914.
 // ---------------------------------------------------------------------------
-template <typename V, int BLOCK, int IPT, bool AXPBY>
-__global__ __launch_bounds__(BLOCK) void tile_kernel(Params<V> p, const Coord *__restrict__ coords,
+template <typename V, int BLOCK, int IPT, bool AXPBY, typename MV = V>
+__global__ __launch_bounds__(BLOCK) void tile_kernel(Params<V, MV> p, const Coord *__restrict__ coords,
                                                      Carry<V> *__restrict__ carries, int num_tiles)
 {
     constexpr int TILE = BLOCK * IPT;
@@ -1450,9 +1471,9 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(Params<V> p, const Coord *_
     const int tile_nnz = c1.y - c0.y;
 
     const int *__restrict__ cols = p.cols + c0.y;
-    const V *__restrict__ vals = p.values + c0.y;
+    const MV *__restrict__ vals = p.values + c0.y;
     int col_r[IPT];
-    V val_r[IPT];
+    MV val_r[IPT];
 #pragma unroll
     for (int k = 0; k < IPT; ++k) {
         const int j = tid + k * BLOCK;
@@ -1463,7 +1484,7 @@ __global__ __launch_bounds__(BLOCK) void tile_kernel(Params<V> p, const Coord *_
 #pragma unroll
     for (int k = 0; k < IPT; ++k) {
         const int j = tid + k * BLOCK;
-        s_prod[j] = j < tile_nnz ? val_r[k] * p.x[col_r[k]] : (V) 0;
+        s_prod[j] = j < tile_nnz ? widen<V>(val_r[k]) * p.x[col_r[k]] : (V) 0;
     }
     if (tid < PAD) s_prod[TILE + tid] = (V) 0;
     __syncthreads();
@@ -1525,11 +1546,11 @@ constexpr int tile_waves_per_simd()
 // ordinary body of the same kernel 20 %).
 template <typename V, bool BAND> constexpr bool band_lazy_values() { return BAND && sizeof(V) == 8; }
 
-template <typename V, int BLOCK, int IPT>
+template <typename V, int BLOCK, int IPT, typename MV = V>
 struct TileRegs {
     static constexpr int CPT = IPT / 4 + 1;   // 4-element chunks per thread: covers TILE + 3
     Vec4<int> col[CPT];
-    Vec4<V> val[CPT];
+    Vec4<MV> val[CPT];                        // as stored: 16 bytes (fp32), 32 (fp64) or 8 (bf16) per chunk
 };
 
 // fp64 values of a 4-element chunk are 32 bytes: fetched as two 16-byte loads per lane, each load instruction of a wave would
@@ -1568,9 +1589,11 @@ __device__ __forceinline__ Vec4<double> linewise_own(const Vec4<double> &w)
     return r;
 }
 __device__ __forceinline__ Vec4<float> linewise_own(const Vec4<float> &w) { return w; }
+__device__ __forceinline__ Vec4<bf16> linewise_own(const Vec4<bf16> &w) { return w; }
 // values as issue_nonzero_loads left them in the tile's registers -> the values of the lane's own chunk k
-template <typename V, bool NT, bool LAZY>
-constexpr bool vals_linewise() { return sizeof(V) == 8 && NT && !LAZY; }
+// (MV: 8-byte STORED values only -- fp32 values of an fp64 product are one 16-byte load per chunk, the fp32 path's)
+template <typename V, bool NT, bool LAZY, typename MV = V>
+constexpr bool vals_linewise() { return sizeof(MV) == 8 && NT && !LAZY; }
 // WIRE staging (the production kernels): the values stay as ld_stream4_linewise fetched them -- val.a = the first half of the own chunk
 // (lanes 0-31) / the second half of the chunk 32 lanes down (lanes 32-63), val.b = the first half of the chunk 32 lanes up / the own
 // second half -- and the COLUMNS are swapped to match (two v_permlane32_swap instead of four): every lane then multiplies two pairs that
@@ -1597,9 +1620,9 @@ __device__ __forceinline__ WirePos wire_pos(int q, int tid)
 //  result was mixed -- grid3d-200 -2.3 %, band5 -3 %, but the circuit-shaped matrix +8 %, dense32 fp64 +3.5 %, dense5 +2 %:
 //  profiles/r05_ab_wave_skip_general_kernel.txt.  The compact front end, whose loads are few and whose tiles share a CU in small
 //  numbers, keeps it.)
-template <typename V, int BLOCK, int IPT, bool NT, bool VALS = true, bool LINEWISE_OK = true>
-__device__ __forceinline__ void issue_nonzero_loads(const Params<V> &p, const Coord c0, const Coord c1,
-                                                    TileRegs<V, BLOCK, IPT> &r, int tid_in = -1)
+template <typename V, int BLOCK, int IPT, bool NT, bool VALS = true, bool LINEWISE_OK = true, typename MV = V>
+__device__ __forceinline__ void issue_nonzero_loads(const Params<V, MV> &p, const Coord c0, const Coord c1,
+                                                    TileRegs<V, BLOCK, IPT, MV> &r, int tid_in = -1)
 {
     const int tid = tid_in < 0 ? (int) threadIdx.x : tid_in;
     constexpr int CPT = IPT / 4 + 1;
@@ -1614,7 +1637,7 @@ __device__ __forceinline__ void issue_nonzero_loads(const Params<V> &p, const Co
         // cached address), so no byte of HBM traffic is spent on data this tile does not use
         e0 = (e0 < c1.y && e0 <= last_full) ? e0 : safe;
         r.col[k] = ld_stream4<NT>(p.cols + e0);
-        if constexpr (VALS && LINEWISE_OK && vals_linewise<V, NT, false>()) {     // (ordinary loads: the second half hits the CU's cache anyway, and the swaps cost 3 % on dense5)
+        if constexpr (VALS && LINEWISE_OK && vals_linewise<V, NT, false, MV>()) {     // (ordinary loads: the second half hits the CU's cache anyway, and the swaps cost 3 % on dense5)
             int e1 = a0 + 4 * ((tid ^ 32) + k * BLOCK);          // the chunk of the lane 32 away, by the same rule
             e1 = (e1 < c1.y && e1 <= last_full) ? e1 : safe;
             r.val[k] = ld_stream4_linewise<NT>(p.values, e0, e1, tid);
@@ -1629,9 +1652,9 @@ __device__ __forceinline__ void issue_nonzero_loads(const Params<V> &p, const Co
 // (after_gather: called once the x gathers have been requested -- scalar work of the caller that then runs in the shadow of their
 //  latency instead of after the staging barrier: the hint verdict of tile_kernel_snap)
 struct NoAfterGather { __device__ __forceinline__ void operator()() const {} };
-template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool XL = false, bool BAND = false, typename AG = NoAfterGather>
-__device__ __forceinline__ void stage_tile_careful(const Params<V> &p, const Coord c0, const Coord c1,
-                                           const TileRegs<V, BLOCK, IPT> &regs, typename EndType<FL>::type *s_end_raw, V *s_prod_raw,
+template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool XL = false, bool BAND = false, typename AG = NoAfterGather, typename MV = V>
+__device__ __forceinline__ void stage_tile_careful(const Params<V, MV> &p, const Coord c0, const Coord c1,
+                                           const TileRegs<V, BLOCK, IPT, MV> &regs, typename EndType<FL>::type *s_end_raw, V *s_prod_raw,
                                            int last_full_nz, int last_full_ro, unsigned *s_flag, const V *s_x = nullptr, int tid_in = -1,
                                            bool lean = false, AG after_gather = AG())
 {
@@ -1660,8 +1683,8 @@ __device__ __forceinline__ void stage_tile_careful(const Params<V> &p, const Coo
     V xv[CPT][4];
     unsigned in_band = 0u;                     // BAND: one bit per staged nonzero of this thread (its column lies in the pass's band)
     constexpr bool LAZY = band_lazy_values<V, BAND>();
-    Vec4<V> bval[LAZY ? CPT : 1];              // LAZY: the values, fetched here and only for chunks with a nonzero of the band
-    constexpr bool WIRE = vals_linewise<V, NT, LAZY>() && FL;
+    Vec4<MV> bval[LAZY ? CPT : 1];              // LAZY: the values, fetched here and only for chunks with a nonzero of the band
+    constexpr bool WIRE = vals_linewise<V, NT, LAZY, MV>() && FL;
     unsigned wire_in = 0u;                     // WIRE: one bit per held nonzero that lies in the tile
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
@@ -1712,10 +1735,10 @@ __device__ __forceinline__ void stage_tile_careful(const Params<V> &p, const Coo
     }
     if (FL && !lean && tid == 0) atomicOr(&s_flag[0], 1u << (c0.y - a0));
     // ---- stage products
-    Vec4<V> own_val[LAZY || WIRE ? 1 : CPT];
+    Vec4<MV> own_val[LAZY || WIRE ? 1 : CPT];
     if constexpr (!LAZY && !WIRE) {
 #pragma unroll
-        for (int k = 0; k < CPT; ++k) own_val[k] = vals_linewise<V, NT, LAZY>() ? linewise_own(regs.val[k]) : regs.val[k];
+        for (int k = 0; k < CPT; ++k) own_val[k] = vals_linewise<V, NT, LAZY, MV>() ? linewise_own(regs.val[k]) : regs.val[k];
     }
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
@@ -1740,7 +1763,7 @@ __device__ __forceinline__ void stage_tile_careful(const Params<V> &p, const Coo
             const bool in = BAND ? ((in_band >> (4 * k + i)) & 1u) != 0u
                                  : (unsigned) (e0 + i - c0.y) < (unsigned) tile_nnz && e0 <= last_full_nz;
             if constexpr (LAZY) prod[i] = in ? bval[k].get(i) * xv[k][i] : (V) 0;
-            else prod[i] = in ? own_val[k].get(i) * xv[k][i] : (V) 0;
+            else prod[i] = in ? widen<V>(own_val[k].get(i)) * xv[k][i] : (V) 0;
         }
         if (FL) st_prod_chunk<CPT>(s_prod_raw, chunk, prod, lean);
         else st_lds4(&s_prod_raw[swz_prod(4 * chunk)], prod);
@@ -1756,7 +1779,7 @@ __device__ __forceinline__ void stage_tile_careful(const Params<V> &p, const Coo
         if (nz_tail && j < c1.y && j >= c0.y) {
             const int c = ld_stream<NT>(p.cols + j);
             const bool inb = !BAND || (unsigned) (c - p.band_lo) < (unsigned) p.band_len;
-            s_prod_raw[FL ? prod_slot<V, CPT>(j - a0, lean) : swz_prod(j - a0)] = inb ? ld_stream<NT>(p.values + j) * (XL ? s_x[c] : p.x[c]) : (V) 0;
+            s_prod_raw[FL ? prod_slot<V, CPT>(j - a0, lean) : swz_prod(j - a0)] = inb ? widen<V>(ld_stream<NT>(p.values + j)) * (XL ? s_x[c] : p.x[c]) : (V) 0;
         }
         const int i = last_full_ro + 4 + tid;                       // absolute d_row_offsets index
         const int r = i - first;
@@ -1781,9 +1804,9 @@ __device__ __forceinline__ void stage_tile_careful(const Params<V> &p, const Coo
 //    least IPT path items past every thread of a full tile.
 // Only whole chunks beyond the needed range are redirected to a cached address (no HBM bytes
 // for data the tile does not use).  This removes ~200 of the ~1100 instructions per wave per tile.
-template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool XL = false, bool BAND = false, typename AG = NoAfterGather>
-__device__ __forceinline__ void stage_tile_interior(const Params<V> &p, const Coord c0, const Coord c1,
-                                                    const TileRegs<V, BLOCK, IPT> &regs,
+template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool XL = false, bool BAND = false, typename AG = NoAfterGather, typename MV = V>
+__device__ __forceinline__ void stage_tile_interior(const Params<V, MV> &p, const Coord c0, const Coord c1,
+                                                    const TileRegs<V, BLOCK, IPT, MV> &regs,
                                                     typename EndType<FL>::type *s_end_raw, V *s_prod_raw, unsigned *s_flag,
                                                     const V *s_x = nullptr, int tid_in = -1, bool lean = false, AG after_gather = AG())
 {
@@ -1810,8 +1833,8 @@ __device__ __forceinline__ void stage_tile_interior(const Params<V> &p, const Co
     V xv[CPT][4];
     unsigned in_band = 0u;                     // BAND: one bit per staged nonzero of this thread
     constexpr bool LAZY = band_lazy_values<V, BAND>();
-    Vec4<V> bval[LAZY ? CPT : 1];              // LAZY: the values, fetched here and only for chunks with a nonzero of the band
-    constexpr bool WIRE = vals_linewise<V, NT, LAZY>() && FL;
+    Vec4<MV> bval[LAZY ? CPT : 1];              // LAZY: the values, fetched here and only for chunks with a nonzero of the band
+    constexpr bool WIRE = vals_linewise<V, NT, LAZY, MV>() && FL;
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
         if constexpr (WIRE) {
@@ -1858,10 +1881,10 @@ __device__ __forceinline__ void stage_tile_interior(const Params<V> &p, const Co
         }
     }
     if (FL && !lean && tid == 0) atomicOr(&s_flag[0], 1u << (c0.y - (c0.y & ~3)));
-    Vec4<V> own_val[LAZY || WIRE ? 1 : CPT];
+    Vec4<MV> own_val[LAZY || WIRE ? 1 : CPT];
     if constexpr (!LAZY && !WIRE) {
 #pragma unroll
-        for (int k = 0; k < CPT; ++k) own_val[k] = vals_linewise<V, NT, LAZY>() ? linewise_own(regs.val[k]) : regs.val[k];
+        for (int k = 0; k < CPT; ++k) own_val[k] = vals_linewise<V, NT, LAZY, MV>() ? linewise_own(regs.val[k]) : regs.val[k];
     }
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
@@ -1880,7 +1903,7 @@ __device__ __forceinline__ void stage_tile_interior(const Params<V> &p, const Co
         for (int i = 0; i < 4; ++i) {
             if constexpr (LAZY) prod[i] = ((in_band >> (4 * k + i)) & 1u) ? bval[k].get(i) * xv[k][i] : (V) 0;
             else if constexpr (BAND) prod[i] = ((in_band >> (4 * k + i)) & 1u) ? own_val[k].get(i) * xv[k][i] : (V) 0;
-            else prod[i] = own_val[k].get(i) * xv[k][i];
+            else prod[i] = widen<V>(own_val[k].get(i)) * xv[k][i];
         }
         if (FL) st_prod_chunk<CPT>(s_prod_raw, chunk, prod, lean);
         else st_lds4(&s_prod_raw[swz_prod(4 * chunk)], prod);
@@ -1899,9 +1922,9 @@ __device__ __forceinline__ bool tile_is_interior(const Coord c0, const Coord c1,
     return tile != num_tiles - 1 && c1.y <= last_full_nz + 4 && i0 + 4 * ro_chunks <= last_full_ro + 4;
 }
 
-template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool BAND = false, typename AG = NoAfterGather>
-__device__ __forceinline__ void stage_tile(const Params<V> &p, const Coord c0, const Coord c1, int tile, int num_tiles,
-                                           const TileRegs<V, BLOCK, IPT> &regs, typename EndType<FL>::type *s_end_raw,
+template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool BAND = false, typename AG = NoAfterGather, typename MV = V>
+__device__ __forceinline__ void stage_tile(const Params<V, MV> &p, const Coord c0, const Coord c1, int tile, int num_tiles,
+                                           const TileRegs<V, BLOCK, IPT, MV> &regs, typename EndType<FL>::type *s_end_raw,
                                            V *s_prod_raw, int last_full_nz, int last_full_ro, unsigned *s_flag, const V *s_x = nullptr, int tid_in = -1,
                                            bool lean = false, AG after_gather = AG())
 {
@@ -1924,8 +1947,8 @@ __device__ __forceinline__ void stage_tile(const Params<V> &p, const Coord c0, c
 
 // x -> LDS (dynamic shared memory, p.x_lds entries) at block start; nullptr when the call does not use it.
 // The copy is visible after the block's first barrier.
-template <typename V>
-__device__ __forceinline__ const V *stage_x_in_lds(const Params<V> &p, unsigned char *s_dyn, int block)
+template <typename V, typename MV = V>
+__device__ __forceinline__ const V *stage_x_in_lds(const Params<V, MV> &p, unsigned char *s_dyn, int block)
 {
     if (p.x_lds <= 0) return nullptr;
     V *s_x = reinterpret_cast<V *>(s_dyn);
@@ -1938,8 +1961,8 @@ __device__ __forceinline__ const V *stage_x_in_lds(const Params<V> &p, unsigned 
 // (vector loads return in order: waiting for the oldest does not wait for the streams).  In one step the block sat through
 // hint latency + x latency with nothing else in flight: 0.5 us of a 5.7 us block life on the reference's --dense inputs.
 template <typename V, int BLOCK> struct XRegs { static constexpr int N = X_LDS_MAX_BYTES / (int) sizeof(V) / BLOCK; V v[N]; };
-template <typename V, int BLOCK>
-__device__ __forceinline__ void request_x_for_lds(const Params<V> &p, XRegs<V, BLOCK> &xr)
+template <typename V, int BLOCK, typename MV = V>
+__device__ __forceinline__ void request_x_for_lds(const Params<V, MV> &p, XRegs<V, BLOCK> &xr)
 {
     static_assert(XRegs<V, BLOCK>::N >= 1, "x_lds entries per thread");
 #pragma unroll
@@ -1948,8 +1971,8 @@ __device__ __forceinline__ void request_x_for_lds(const Params<V> &p, XRegs<V, B
         xr.v[j] = i < p.x_lds ? p.x[i] : (V) 0;
     }
 }
-template <typename V, int BLOCK>
-__device__ __forceinline__ void commit_x_to_lds(const Params<V> &p, const XRegs<V, BLOCK> &xr, unsigned char *s_dyn)
+template <typename V, int BLOCK, typename MV = V>
+__device__ __forceinline__ void commit_x_to_lds(const Params<V, MV> &p, const XRegs<V, BLOCK> &xr, unsigned char *s_dyn)
 {
     V *s_x = reinterpret_cast<V *>(s_dyn);
 #pragma unroll
@@ -2118,8 +2141,8 @@ __device__ __forceinline__ void run_band_passes(Params<V> p, const Coord *__rest
 __device__ unsigned long long *g_mspmv_trace = nullptr;
 #endif
 
-template <typename V, int BLOCK, int IPT, bool AXPBY, bool XCD_REMAP, bool NT, int ABLATE = 0, bool PERSIST = false, bool BAND = false, bool TDM = false>
-__global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !PERSIST, ABLATE == 7>())) void tile_kernel_vec(Params<V> p, const Coord *__restrict__ coords,
+template <typename V, int BLOCK, int IPT, bool AXPBY, bool XCD_REMAP, bool NT, int ABLATE = 0, bool PERSIST = false, bool BAND = false, bool TDM = false, typename MV = V>
+__global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !PERSIST, ABLATE == 7>())) void tile_kernel_vec(Params<V, MV> p, const Coord *__restrict__ coords,
                                                                 Carry<V> *__restrict__ carries, int num_tiles, int xcd_chunk_log2,
                                                                 BandArgs ba)
 {
@@ -2136,6 +2159,7 @@ __global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !PERSIST
     // BAND: a call that the column-band passes may serve better; the sampled windows decide, here, on the device.  The
     // verdicts are requested now and looked at once the tile's coordinates are there too (one load latency, not two:
     // with the residency capped by LDS every microsecond a block waits before streaming is throughput lost)
+    static_assert(std::is_same<V, MV>::value || (!BAND && !TDM), "mixed precision: never the column bands");
     int band_v = 0;
     if constexpr (BAND) {
         static_assert(FL && !PERSIST && ABLATE == 0 && !XCD_REMAP, "band passes: production variant only");
@@ -2205,7 +2229,7 @@ __global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !PERSIST
             }
         }
     }
-    TileRegs<V, BLOCK, IPT> regs;
+    TileRegs<V, BLOCK, IPT, MV> regs;
     issue_nonzero_loads<V, BLOCK, IPT, NT>(p, c0, c1, regs);
     const int last_full_nz = (p.nnz & ~3) - 4;
     const int last_full_ro = ((p.rows + 1) & ~3) - 4;   // rows + 1 >= 4
@@ -2794,10 +2818,10 @@ longer_rows:
     goto store_row;
 }
 
-template <typename V, int BLOCK, int IPT, bool AXPBY, bool NT, bool COMPACT = false>
+template <typename V, int BLOCK, int IPT, bool AXPBY, bool NT, bool COMPACT = false, typename MV = V>
 __global__ __launch_bounds__(BLOCK, (COMPACT ? 4 : tile_waves_per_simd<V, BLOCK, IPT, true>())) void tile_kernel_snap(Coord *__restrict__ coords, int *__restrict__ rstart,
                                                            int num_tiles, int xcd_chunk_log2,
-                                                           Params<V> p, Carry<V> *__restrict__ carries, LookBack lb, int lean_avg)
+                                                           Params<V, MV> p, Carry<V> *__restrict__ carries, LookBack lb, int lean_avg)
 {
     constexpr int TILE = BLOCK * IPT;
     constexpr int NW = BLOCK / WAVE;
@@ -2819,6 +2843,7 @@ __global__ __launch_bounds__(BLOCK, (COMPACT ? 4 : tile_waves_per_simd<V, BLOCK,
     // from the start, on the hints the front end loaded.  Same tile (compact_tile) in both.
     int4v front_hc = {0, 0, 0, 0}; int2v front_hr = {0, 0};
     if constexpr (COMPACT) {
+        static_assert(std::is_same<V, MV>::value, "mixed precision: never the compact front end");
         static_assert(BLOCK == COMPACT_BLOCK && IPT == COMPACT_IPT && !NT, "the compact front end is written for the small tile shape");
         compact_front<V, AXPBY>(coords, rstart, num_tiles, p, carries, lean_avg, compact_tile((int) blockIdx.x, num_tiles, xcd_chunk_log2), s_prod_raw, s_end_words,
                                 front_hc, front_hr);      // (a tile it takes ends there)
@@ -2921,7 +2946,7 @@ __global__ __launch_bounds__(BLOCK, (COMPACT ? 4 : tile_waves_per_simd<V, BLOCK,
             idx = idx < 0 ? 0 : idx >= p.rows ? p.rows - 1 : idx;   // (rows >= 3 on this path)
             vre = p.row_end[idx];
         }
-        TileRegs<V, BLOCK, IPT> regs;
+        TileRegs<V, BLOCK, IPT, MV> regs;
         issue_nonzero_loads<V, BLOCK, IPT, NT>(p, c0, c1, regs);
         MSPMV_SNAP_TR(2);
         if (MSPMV_UNLIKELY((layout_hints<V, IPT>()), late_barrier)) { commit_x_to_lds<V, BLOCK>(p, xr, s_dyn); __syncthreads(); }
@@ -2961,7 +2986,7 @@ __global__ __launch_bounds__(BLOCK, (COMPACT ? 4 : tile_waves_per_simd<V, BLOCK,
         c0.x = x0; c0.y = snap0 ? rs0 : y0;
         c1.x = x1; c1.y = snap1 ? rs1 : y1;
         lean = snap0 && snap1 && (unsigned) (c1.y - c0.y) <= (unsigned) lean_avg * (unsigned) (c1.x - c0.x);
-        TileRegs<V, BLOCK, IPT> regs;
+        TileRegs<V, BLOCK, IPT, MV> regs;
         issue_nonzero_loads<V, BLOCK, IPT, NT>(p, c0, c1, regs);
         stage_tile<V, BLOCK, IPT, NT, true>(p, c0, c1, tile, num_tiles, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, s_x, -1, lean);
     }

@@ -89,6 +89,28 @@ struct DeviceSpmv {
                                                      debug_synchronous ? 1 : 0);
     }
 
+    // ---- mixed precision (extension): the matrix values stored narrow -- float with double x / y, bf16 (uint16_t: the upper half of
+    //      a float) with float x / y --, y = alpha*A*x + beta*y in the vectors' type; bit for bit the wide call on the widened values
+    //      (mspmv.h says when).  prepared: d_temp_storage as left by CsrMVPrepare<type of x>.
+    static hipError_t CsrMVMixed(void *d_temp_storage, size_t &temp_storage_bytes, const float *d_values,
+                                 const int *d_row_offsets, const int *d_column_indices, const double *d_vector_x,
+                                 double *d_vector_y, int num_rows, int num_cols, int num_nonzeros, double alpha = 1.0,
+                                 double beta = 0.0, hipStream_t stream = 0, bool debug_synchronous = false, bool prepared = false)
+    {
+        return (hipError_t) (prepared ? mspmv_csrmv_mixed_prepared_f32_f64 : mspmv_csrmv_mixed_f32_f64)(
+            d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices, d_vector_x, d_vector_y, num_rows, num_cols,
+            num_nonzeros, alpha, beta, (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+    }
+    static hipError_t CsrMVMixed(void *d_temp_storage, size_t &temp_storage_bytes, const uint16_t *d_values,
+                                 const int *d_row_offsets, const int *d_column_indices, const float *d_vector_x,
+                                 float *d_vector_y, int num_rows, int num_cols, int num_nonzeros, float alpha = 1.f,
+                                 float beta = 0.f, hipStream_t stream = 0, bool debug_synchronous = false, bool prepared = false)
+    {
+        return (hipError_t) (prepared ? mspmv_csrmv_mixed_prepared_bf16_f32 : mspmv_csrmv_mixed_bf16_f32)(
+            d_temp_storage, &temp_storage_bytes, d_values, d_row_offsets, d_column_indices, d_vector_x, d_vector_y, num_rows, num_cols,
+            num_nonzeros, alpha, beta, (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+    }
+
     // ---- prepared band-major plan (extension, opt-in): build once, multiply many times
     template <typename ValueT>
     static hipError_t PlanSize(int num_rows, int num_cols, int num_nonzeros, int bands, size_t &plan_bytes, int &bands_used)
