@@ -55,7 +55,7 @@ extern "C" {
  * no HIP headers (NULL = the default stream). */
 typedef void *mspmv_stream_t;
 
-#define MSPMV_VERSION 102 /* (the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, and the mixed-precision ones, mspmv_csrmv_mixed_* / mspmv_csrmv_mixed_prepared_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
+#define MSPMV_VERSION 102 /* (the matrix addition mspmv_csr_add_*, the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, and the mixed-precision ones, mspmv_csrmv_mixed_* / mspmv_csrmv_mixed_prepared_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
 int mspmv_version(void);
 
 /* hipGetErrorString for codes returned by this library. */
@@ -399,6 +399,45 @@ int mspmv_coomv_f64(void *d_temp, size_t *temp_bytes, const double *d_values,
                     const int32_t *d_row_indices, const int32_t *d_column_indices,
                     const double *d_x, double *d_y, int32_t rows, int32_t cols, int32_t nnz,
                     double alpha, double beta, mspmv_stream_t stream, int debug_sync);
+
+/* ---- extension: MATRIX ADDITION  C = alpha * A + beta * B  on the device (csrc/mspmv_add.hip; what csrgeam is in rocSPARSE /
+ * cuSPARSE): A + A^T of an edge list after mspmv_coo_to_csr_* and mspmv_csr_transpose_*, A - sigma I, M + dt K, L = D - A.
+ * INPUTS: two CSR matrices of the same rows x cols, every row sorted by column with no column twice -- what
+ * mspmv_csr_sum_duplicates_* writes, what mspmv_coo_to_csr_* writes for triples without duplicates and mspmv_csr_transpose_* for
+ * such a matrix.  Not checked: on other rows the result is unspecified, but nothing outside the arrays is read or written and the
+ * call terminates (row offsets must be valid, as for every call).  A and B may be the same arrays; outputs must not alias inputs.
+ * OUTPUT: C in the same canonical form.  Its pattern is the UNION of the two patterns, a function of the patterns alone: an entry
+ * whose value comes out 0 stays, alpha == 0 does not drop A's pattern.  d_row_offsets_c has rows + 1 entries and is right for empty
+ * rows anywhere.  d_column_indices_c / d_values_c are sized by the caller for nnz_a + nnz_b entries; the first *d_nnz_c are
+ * written, the rest are left untouched.  *d_nnz_c is one int32 on the device (as for mspmv_csr_sum_duplicates_*): the host does
+ * not learn it inside the call.
+ * VALUES, defined bit for bit in the value type, every operation rounded on its own (no fused multiply-add):
+ *     entry only in A: alpha * a      only in B: beta * b      in both: (alpha * a) + (beta * b)
+ * so alpha = beta = 1 gives exactly a, b, a + b.  d_values_a == d_values_b == d_values_c == NULL: structure only (either entry
+ * point; alpha and beta are ignored); values for some of the matrices and not for others: hipErrorInvalidValue (the pointer of an
+ * input without entries has no say).
+ * HOW: the union of two sorted sequences of the key (row, column) is a merge.  It is cut into tiles of 1792 merged entries at
+ * equally spaced diagonals -- one row holding every entry costs what a million short ones cost --; a count pass, a scan of the tile
+ * counts and a fill pass, 5 launches whatever the data.  No atomics on global memory, no workgroup waits on another, the host never
+ * reads device memory: every output position and value is a function of the input alone and the call can be captured in a graph.
+ * Same two-phase temp storage (d_temp == NULL -> size, no work), 16-byte alignment, ownership, stream, debug_sync (one line per
+ * launch) and error conventions as mspmv_csr_transpose_*.  Temp storage: 24 bytes per TILE (a 100 M + 100 M addition: 2.7 MB).
+ * LIMITS: rows, cols, nnz_a, nnz_b >= 0; rows + nnz_a + nnz_b <= 2^31 - 65537 (int32 diagonals with the usual tile of slack, and
+ * whatever comes out can be multiplied); rows == 0 or cols == 0 with entries is refused; nnz_a == nnz_b == 0 gives all-zero
+ * offsets and a count of 0.  Measured on MI355X against rocSPARSE's csrgeam_nnz + csrgeam on the same arrays, patterns equal
+ * (profiles/add_bench.txt; DESIGN.md 4 "Addition"): a uniform 100 M-entry matrix plus its transpose 2.72 ms fp32 / 3.18 ms fp64
+ * against 48.4 / 51.7 ms; an R-MAT graph of 62 M entries plus its transpose 1.85 / 2.14 against 236 / 251 ms; 2^26 + 2^26 entries over
+ * 2^21 rows 2.02 / 2.35 against 2.58 / 2.76 ms; the same entries in ONE row 1.57 / 1.87 ms against 10.9 / 12.0 s. ---- */
+int mspmv_csr_add_f32(void *d_temp, size_t *temp_bytes, int32_t rows, int32_t cols,
+                      float alpha, const float *d_values_a, const int32_t *d_row_offsets_a, const int32_t *d_column_indices_a, int32_t nnz_a,
+                      float beta, const float *d_values_b, const int32_t *d_row_offsets_b, const int32_t *d_column_indices_b, int32_t nnz_b,
+                      float *d_values_c, int32_t *d_row_offsets_c /* [rows + 1] */, int32_t *d_column_indices_c, int32_t *d_nnz_c,
+                      mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_add_f64(void *d_temp, size_t *temp_bytes, int32_t rows, int32_t cols,
+                      double alpha, const double *d_values_a, const int32_t *d_row_offsets_a, const int32_t *d_column_indices_a, int32_t nnz_a,
+                      double beta, const double *d_values_b, const int32_t *d_row_offsets_b, const int32_t *d_column_indices_b, int32_t nnz_b,
+                      double *d_values_c, int32_t *d_row_offsets_c /* [rows + 1] */, int32_t *d_column_indices_c, int32_t *d_nnz_c,
+                      mspmv_stream_t stream, int debug_sync);
 
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */

@@ -18,6 +18,7 @@ import os
 from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
+           "csr_add", "CsrAdd", "csr_symmetrize",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -181,6 +182,9 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "mspmv_coomv_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, sz_p, vp, vp, vp, vp, vp, i32, i32, i32, ct, ct, vp, ctypes.c_int]
+        fn = getattr(lib, "mspmv_csr_add_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, sz_p, i32, i32, ct, vp, vp, vp, i32, ct, vp, vp, vp, i32, vp, vp, vp, vp, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_size.restype = ctypes.c_int
     lib.mspmv_csrmv_hotcols_size.argtypes = [i32, i32, i32, i32, sz_p]
     lib.mspmv_csrmv_hotcols_build.restype = ctypes.c_int
@@ -795,6 +799,102 @@ def coomv(values, row_indices, column_indices, x, y=None, num_rows: Optional[int
     if stream is not None and hasattr(stream, "cuda_stream"):
         temp.record_stream(stream)
     return y
+
+
+def _add_check(m, name: str, what: str):
+    """the checks the C ABI cannot make for one addend (a generators.DeviceCsr or anything with its five fields); returns nnz"""
+    import torch
+    off, col, val = m.row_offsets, m.column_indices, m.values
+    if off is None or not off.is_cuda or off.dtype != torch.int32 or not off.is_contiguous() or off.dim() != 1 or off.numel() != int(m.rows) + 1:
+        raise MspmvError(f"{what}: {name}.row_offsets must be a contiguous 1-D int32 CUDA tensor of rows + 1 entries")
+    if col is None or col.dtype != torch.int32 or col.device != off.device or not col.is_contiguous() or col.dim() != 1:
+        raise MspmvError(f"{what}: {name}.column_indices must be a contiguous 1-D int32 tensor on {off.device}")
+    if val is not None:
+        if val.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{what} is instantiated for float32 and float64 only, got {val.dtype}")
+        if val.device != off.device or not val.is_contiguous() or val.dim() != 1 or val.numel() != col.numel():
+            raise MspmvError(f"{what}: {name}.values must be a contiguous 1-D tensor of {col.numel()} entries on {off.device}")
+    return col.numel()
+
+
+class CsrAdd:
+    """C = alpha*A + beta*B on the device (mspmv_csr_add_*) with the outputs and the temp storage allocated ONCE, so that `add()` can
+    be captured in a graph and replayed after the addends' tensors were overwritten in place (new values, or a new pattern of the same
+    counts).  a, b: generators.DeviceCsr of the same shape, rows sorted by column without repeated columns; values for both or for
+    neither (structure only).  Holds row_offsets (rows + 1), column_indices and values (nnz_a + nnz_b entries, of which the first
+    `count` -- a one-element int32 CUDA tensor -- are written) and reads nothing back; `trimmed()` waits for the stream the last
+    `add()` ran on, reads the count and returns the DeviceCsr narrowed to it."""
+
+    def __init__(self, a, b, alpha: float = 1.0, beta: float = 1.0, stream=None):
+        import torch
+        self.nnz_a, self.nnz_b = _add_check(a, "a", "csr_add"), _add_check(b, "b", "csr_add")
+        if (int(a.rows), int(a.cols)) != (int(b.rows), int(b.cols)):
+            raise MspmvError(f"csr_add: a is {a.rows} x {a.cols}, b is {b.rows} x {b.cols}")
+        if (a.values is None) != (b.values is None):
+            raise MspmvError("csr_add: values for both matrices or for neither (structure only)")
+        dev = a.row_offsets.device
+        if b.row_offsets.device != dev:
+            raise MspmvError(f"csr_add: b must be on {dev}")
+        if a.values is not None and a.values.dtype != b.values.dtype:
+            raise MspmvError(f"csr_add: a holds {a.values.dtype}, b {b.values.dtype}")
+        self.a, self.b, self.rows, self.cols = a, b, int(a.rows), int(a.cols)
+        self.alpha, self.beta = float(alpha), float(beta)
+        self.dtype = torch.float32 if a.values is None else a.values.dtype
+        lib = load_library()
+        self._fn = lib.mspmv_csr_add_f32 if self.dtype == torch.float32 else lib.mspmv_csr_add_f64
+        self._ct = ctypes.c_float if self.dtype == torch.float32 else ctypes.c_double
+        n = self.nnz_a + self.nnz_b
+        self.row_offsets = torch.empty(self.rows + 1, dtype=torch.int32, device=dev)
+        self.column_indices = torch.empty(n, dtype=torch.int32, device=dev)
+        self.values = None if a.values is None else torch.empty(n, dtype=self.dtype, device=dev)
+        self.count = torch.empty(1, dtype=torch.int32, device=dev)
+        self.temp = None
+        self._stream = None
+        self.add(stream=stream)
+
+    def add(self, stream=None, alpha=None, beta=None):
+        """runs the addition on the addends' tensors as they are now, into the same outputs; asynchronous on `stream`"""
+        a, b = self.a, self.b
+        if _add_check(a, "a", "CsrAdd.add") != self.nnz_a or _add_check(b, "b", "CsrAdd.add") != self.nnz_b:
+            raise MspmvError(f"CsrAdd.add: the addends must keep their {self.nnz_a} and {self.nnz_b} entries")
+        ct = self._ct
+        args = (self.rows, self.cols, ct(self.alpha if alpha is None else alpha), _ptr(a.values), _ptr(a.row_offsets), _ptr(a.column_indices),
+                self.nnz_a, ct(self.beta if beta is None else beta), _ptr(b.values), _ptr(b.row_offsets), _ptr(b.column_indices), self.nnz_b,
+                _ptr(self.values), ctypes.c_void_p(self.row_offsets.data_ptr()), _ptr(self.column_indices),
+                ctypes.c_void_p(self.count.data_ptr()))
+        self.temp = _two_phase(self._fn, "mspmv_csr_add", self.row_offsets.device, stream, args, temp=self.temp)
+        self._stream = stream
+        return self
+
+    def trimmed(self):
+        from .generators import DeviceCsr
+        if self._stream is not None and hasattr(self._stream, "synchronize"):
+            self._stream.synchronize()                           # (the count is read on the current stream: wait for add()'s first)
+        n = int(self.count.item())
+        return DeviceCsr(self.rows, self.cols, self.row_offsets, self.column_indices[:n], None if self.values is None else self.values[:n])
+
+
+def csr_add(a, b, alpha: float = 1.0, beta: float = 1.0, stream=None, trim: bool = False):
+    """C = alpha*A + beta*B for two generators.DeviceCsr of the same shape whose rows are sorted by column without repeated columns
+    (mspmv_csr_add_*): C's pattern is the union of the two patterns whatever the values, its values alpha*a, beta*b or
+    (alpha*a) + (beta*b), each operation rounded on its own.  values None in both: structure only.  Returns (c, count): c a
+    DeviceCsr whose column_indices / values keep nnz_a + nnz_b entries, of which the first `count` (a one-element int32 CUDA tensor)
+    are written.  Asynchronous on `stream`; nothing is read back -- unless trim=True, which reads the count (the ONLY synchronising
+    step) and narrows the arrays to it."""
+    from .generators import DeviceCsr
+    op = CsrAdd(a, b, alpha=alpha, beta=beta, stream=stream)
+    if trim:
+        return op.trimmed(), op.count
+    return DeviceCsr(op.rows, op.cols, op.row_offsets, op.column_indices, op.values), op.count
+
+
+def csr_symmetrize(a, stream=None):
+    """A + A^T of a square DeviceCsr (the undirected graph of an edge list): csr_add(a, csr_transpose(a)), trimmed to its count."""
+    from .generators import DeviceCsr
+    if int(a.rows) != int(a.cols):
+        raise MspmvError(f"csr_symmetrize: the matrix must be square, got {a.rows} x {a.cols}")
+    vt, ot, ct, _ = csr_transpose(a.values, a.row_offsets, a.column_indices, a.cols, stream=stream)
+    return csr_add(a, DeviceCsr(a.cols, a.rows, ot, ct, vt), stream=stream, trim=True)[0]
 
 
 class CsrMVPlan:

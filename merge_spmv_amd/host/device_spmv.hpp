@@ -111,6 +111,32 @@ struct DeviceSpmv {
             num_nonzeros, alpha, beta, (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
     }
 
+    // ---- addition (extension): C = alpha*A + beta*B for two CSR matrices whose rows are sorted by column without repeated columns;
+    //      C's arrays are sized for nnz_a + nnz_b, *d_num_nonzeros_c (device) receives the count of the union; all three value
+    //      pointers nullptr: structure only (mspmv.h: mspmv_csr_add_*)
+    static hipError_t CsrAdd(void *d_temp_storage, size_t &temp_storage_bytes, int num_rows, int num_cols, float alpha, const float *d_values_a,
+                             const int *d_row_offsets_a, const int *d_column_indices_a, int num_nonzeros_a, float beta,
+                             const float *d_values_b, const int *d_row_offsets_b, const int *d_column_indices_b, int num_nonzeros_b,
+                             float *d_values_c, int *d_row_offsets_c, int *d_column_indices_c, int *d_num_nonzeros_c,
+                             hipStream_t stream = 0, bool debug_synchronous = false)
+    {
+        return (hipError_t) mspmv_csr_add_f32(d_temp_storage, &temp_storage_bytes, num_rows, num_cols, alpha, d_values_a, d_row_offsets_a,
+                                              d_column_indices_a, num_nonzeros_a, beta, d_values_b, d_row_offsets_b, d_column_indices_b,
+                                              num_nonzeros_b, d_values_c, d_row_offsets_c, d_column_indices_c, d_num_nonzeros_c,
+                                              (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+    }
+    static hipError_t CsrAdd(void *d_temp_storage, size_t &temp_storage_bytes, int num_rows, int num_cols, double alpha, const double *d_values_a,
+                             const int *d_row_offsets_a, const int *d_column_indices_a, int num_nonzeros_a, double beta,
+                             const double *d_values_b, const int *d_row_offsets_b, const int *d_column_indices_b, int num_nonzeros_b,
+                             double *d_values_c, int *d_row_offsets_c, int *d_column_indices_c, int *d_num_nonzeros_c,
+                             hipStream_t stream = 0, bool debug_synchronous = false)
+    {
+        return (hipError_t) mspmv_csr_add_f64(d_temp_storage, &temp_storage_bytes, num_rows, num_cols, alpha, d_values_a, d_row_offsets_a,
+                                              d_column_indices_a, num_nonzeros_a, beta, d_values_b, d_row_offsets_b, d_column_indices_b,
+                                              num_nonzeros_b, d_values_c, d_row_offsets_c, d_column_indices_c, d_num_nonzeros_c,
+                                              (mspmv_stream_t) stream, debug_synchronous ? 1 : 0);
+    }
+
     // ---- prepared band-major plan (extension, opt-in): build once, multiply many times
     template <typename ValueT>
     static hipError_t PlanSize(int num_rows, int num_cols, int num_nonzeros, int bands, size_t &plan_bytes, int &bands_used)
