@@ -29,7 +29,7 @@ constexpr int INTERP_MIN_ROWS = 10000000;       // coordinate pass: interpolatio
 #ifndef MSPMV_MM_LANE_BLOCK
 #define MSPMV_MM_LANE_BLOCK 256
 #endif
-constexpr int MM_LANE_BLOCK = MSPMV_MM_LANE_BLOCK;      // threads per block of the slot form of SpMM (its tile stays 256 x 7 path items)
+constexpr int MM_LANE_BLOCK = MSPMV_MM_LANE_BLOCK;      // threads per block of the slot form of SpMM (its tile is 256 x MM_LANE_IPT path items, whatever the block)
 constexpr int MM_CHUNK_LOG2 = 6;         // XCD-chunked mapping of the SpMM tiles: 0-3 %
 constexpr int FIX_BLOCK = 256;
 constexpr int FIX_IPT = 2;              // little serial work per thread: the fix-up is latency-bound (256x8: 14 us, 256x2: 9.5 us, 1024x16: 40 us)
@@ -926,7 +926,7 @@ template <typename T, int K> struct MMShape {
 #endif
 constexpr int MM_LANE_IPT = MSPMV_MM_LANE_IPT;
 constexpr int MM_TILES[4] = {256 * 7, 256 * 3, 128 * 3, 256 * MM_LANE_IPT};      // tile sizes in use: index 0 narrow packs, 1: 32-byte packs, 2: 64-byte, 3: the slot form
-// groups of 8 or 16 right-hand sides of at least 32 bytes run the lane-per-column kernel (spmm_lane_kernel) on the 256 x 7 tiles
+// groups of 8 or 16 right-hand sides of at least 32 bytes run the lane-per-column kernel (spmm_lane_kernel) on tiles of 256 x 11 path items
 // right-hand sides per lane of the slot form: four lanes per slot, at most 16 bytes per lane (32 bytes per lane, two lanes per slot:
 // 146-158 registers, 20-70 % slower on every matrix tried)
 template <typename T, int K> constexpr int mm_lane_vec() { return K / 4 * (int) sizeof(T) <= 16 ? K / 4 : 16 / (int) sizeof(T); }

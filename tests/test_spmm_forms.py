@@ -1,0 +1,297 @@
+"""Every kernel form of mspmv_csrmm_f32 / _f64 on the device, exact, with the form that ran pinned by the launch log.
+
+For every row of spmm_forms.CASES: the `mspmv: <kernel><<<grid, block>>>` lines of a debug_synchronous call must equal the launches
+the restated dispatch rule (tests/spmm_forms.py) expects -- the kernel name gives the form, grid and block the tile size -- and Y
+must equal an int64 reference bit for bit: matrix values (nonzero integers in [-8, 8], +-1 on the giant row), X (+-1 .. 3),
+Y0 (+-1 .. 8), alpha in {1, -2} and beta in {0, 3} are integers with |alpha| sum |a x| + |beta| |y0| <= 2^24 (fp32; 2^53 in fp64) on
+every row and column, which the test asserts on the reference's own sums first: every partial sum in any association order is then
+an integer the format holds, and a dropped, doubled or misplaced product changes Y.  No row or column is left out.  X and Y are
+views inside wider buffers; the other columns of X hold NaN, those of Y a sentinel that must survive.  Y is NaN before a call with
+beta = 0.  A second call gives the same bits.
+
+The log names the kernel, grid.x and block of every launch: that pins the form and the tile size.  Which AXPBY / NT instantiation
+ran, the width of a pack launch among those sharing a tile size, and the fix-up's grid.y (groups) are not printed; the coverage
+table's axpby and nt columns are what the restated rule says of the call's alpha, beta and stream size, not an observation.  A wrong
+width or group count does show in the exact comparison (columns left unwritten stay NaN or Y0).
+
+The matrices (spmm_forms.structure) are built once each and freed before the next.
+
+Measured on one MI355X: the 30 tests of this file take 5.3 s (7 s with the interpreter's start), beside 203 s for the other 1802
+GPU tests.  Sensitivity, each a one-line change of mspmv_spmm.hpp tried against this file, every failure the exact comparison:
+the slot form's before() stopping one slot early fails the 10 big_slots / big_slot_groups / huge_slots_nt cases; its carries
+indexed without g * num_tiles the 4 cases with two groups of 16 (big_slot_groups, huge_slots_nt_plain); the pack kernel without
+its nz_tail store every case that runs a pack (24 tests: the last row, in the pack widths' columns); the fix-up without its
+look-ahead sum all 26 tests off the row-wise kernel (the giant row).  Writing the pack kernel's select `in ? val * xv : 0` as a
+product with 0 / 1 changes nothing in Y: the positions it zeroes lie outside the tile's own nonzeros in LDS, where no row sum,
+carry or scan result that is used reads -- with X[0, :] = NaN those positions hold NaN and Y is still the clean run's, which is
+what test_nan_and_inf_stay_where_they_are asserts.
+"""
+import re
+
+import pytest
+
+import spmm_forms as F
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+TDT = {"f32": torch.float32, "f64": torch.float64}
+EXACT = {"f32": 1 << 24, "f64": 1 << 53}
+SENTINEL = 777.0
+ROW_CHUNK = 1 << 21
+MAT_ORDER = {"tiny": 0, "mid": 1, "big": 2, "huge": 3}
+ORDERED = sorted(F.CASES, key=lambda c: MAT_ORDER[c.mat])
+LAUNCH = re.compile(r"^mspmv: (\w+)<<<(\d+), (\d+)>>>$", re.M)
+
+
+def _hash(seed, idx):
+    from merge_spmv_amd.generators import splitmix64
+    return splitmix64(seed, idx) & ((1 << 63) - 1)
+
+
+def _pm(seed, idx, m):
+    """nonzero integers in [-m, m]"""
+    t = _hash(seed, idx) % (2 * m)
+    return t - m + (t >= m).to(torch.int64)
+
+
+class Mat:
+    """one structure on the device: int64 values, row offsets per trim, column indices per column count"""
+
+    def __init__(self, name):
+        self.name, self.s = name, F.structure(name)
+        s = self.s
+        self.rows, self.nnz_full = s.rows, s.nnz()
+        k = torch.arange(self.nnz_full, dtype=torch.int64, device="cuda")
+        self.vals64 = _pm(0x5F0001, k, 8)
+        if s.giant:
+            off = s.offsets()
+            g = int(s.lens.argmax())
+            self.giant_row, self.giant_lo, self.giant_hi = g, int(off[g]), int(off[g + 1])
+            self.vals64[self.giant_lo:self.giant_hi] = torch.sign(self.vals64[self.giant_lo:self.giant_hi])     # the giant row: +-1
+        self._off, self._cols, self._vals = {}, {}, {}
+
+    def off(self, trim):
+        if trim not in self._off:
+            self._off[trim] = torch.from_numpy(self.s.offsets(trim)).cuda()
+        return self._off[trim]
+
+    def cols(self, n):
+        """column indices in [1, n): column 0 is never referenced"""
+        if n not in self._cols:
+            k = torch.arange(self.nnz_full, dtype=torch.int64, device="cuda")
+            c = 1 + _hash(0x5F0002 + n, k) % (n - 1)
+            self._cols = {n: c}                        # (one at a time)
+        return self._cols[n]
+
+    def vals(self, prec):
+        if prec not in self._vals:
+            self._vals = {prec: self.vals64.to(TDT[prec])}
+        return self._vals[prec]
+
+
+@pytest.fixture(scope="module")
+def M():
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU: torch.cuda.is_available() is False")
+    import merge_spmv_amd as M_
+    M_.load_library()          # raises if the HIP extension is missing: no fallback
+    return M_
+
+
+@pytest.fixture(scope="module")
+def mats():
+    """the matrix of the current case; the tests come ordered by matrix, so each is built once"""
+    held = {}
+
+    def get(name):
+        if name not in held:
+            held.clear()
+            torch.cuda.empty_cache()
+            held[name] = Mat(name)
+        return held[name]
+    yield get
+    held.clear()
+    torch.cuda.empty_cache()
+
+
+TARGET_MEMORY = 250 << 30               # an MI355X reports 288 GB: on such a card every case fits, and one that does not is a failure
+
+
+def _room(need, what):
+    """`need`: X's buffer, three int64 columns of X for the reference, the chunk temporaries of X's generator, Y's buffer three times,
+    six int64 [rows, k] arrays (Y0, reference, sums, comparisons), eight int64 arrays of nnz entries, 2 GiB of slack.  Only a card
+    smaller than the target may skip: a skipped case could be the only cover of a form."""
+    torch.cuda.empty_cache()
+    free, total = torch.cuda.mem_get_info()
+    assert free >= need or total < TARGET_MEMORY, f"{what}: needs {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB free of {total / 2**30:.1f}"
+    if free < need:
+        pytest.skip(f"{what}: needs {need / 2**30:.1f} GiB of device memory, {free / 2**30:.1f} GiB free of {total / 2**30:.1f}")
+
+
+class Call:
+    """the device arrays of one case: the CSR views, X inside its NaN-filled buffer, Y0, the exact reference"""
+
+    def __init__(self, mat, c):
+        self.c, self.mat = c, mat
+        dt, eb = TDT[c.prec], F.ELEM[c.prec]
+        rows, cols, nnz = c.dims()
+        self.rows, self.cols, self.nnz, self.dt = rows, cols, nnz, dt
+        _room(cols * c.xw * eb + cols * 8 * 3 + ROW_CHUNK * c.k * 8 * 6 + rows * (c.yw * eb * 3 + c.k * 8 * 6) + nnz * 8 * 8 + (2 << 30), c.name)
+        self.off64 = mat.off(c.trim)
+        self.off = self.off64.to(torch.int32)
+        self.cidx = mat.cols(cols)[:nnz].clone()
+        self.cidx[-1] = cols - 1                   # the last nonzero sits in the last column (its neighbours keep theirs: the tail's
+                                                   # products then differ from column to column of X)
+        v, ci = mat.vals(c.prec)[:nnz], self.cidx.to(torch.int32)
+        if c.pad:
+            vp = torch.empty(nnz + c.pad, dtype=dt, device="cuda")[c.pad:]; vp.copy_(v); v = vp
+            cp = torch.empty(nnz + c.pad, dtype=torch.int32, device="cuda")[c.pad:]; cp.copy_(ci); ci = cp
+            assert v.data_ptr() % 16 != 0 and ci.data_ptr() % 16 != 0
+        else:
+            assert v.data_ptr() % 16 == 0 and ci.data_ptr() % 16 == 0 and self.off.data_ptr() % 16 == 0
+        self.vals, self.ci = v, ci
+        self.vals64 = mat.vals64[:nnz]
+        # X: the view holds integers, every other column of the buffer NaN
+        self.Xw = torch.full((cols, c.xw), float("nan"), dtype=dt, device="cuda")
+        self.X = self.Xw[:, c.x_off:c.x_off + c.k]
+        j = torch.arange(c.k, dtype=torch.int64, device="cuda")
+        for lo in range(0, cols, ROW_CHUNK):
+            hi = min(lo + ROW_CHUNK, cols)
+            r = torch.arange(lo, hi, dtype=torch.int64, device="cuda")
+            self.X[lo:hi] = _pm(0x5F0003, r[:, None] * 64 + j[None, :], 3).to(dt)
+        assert self.Xw.data_ptr() % 256 == 0
+        r = torch.arange(rows, dtype=torch.int64, device="cuda")
+        self.y0 = _pm(0x5F0004, r[:, None] * 64 + j[None, :], 8)
+        self.y_ref, self.s = self.reference(self.vals64, self.X)
+
+    def reference(self, vals64, X):
+        """int64 [rows, k]: the segmented sums of a * X[col] and of |a * X[col]|, from running sums (exact, no atomics)"""
+        a, b = self.off64[:-1], self.off64[1:]
+        y = torch.empty(self.rows, self.c.k, dtype=torch.int64, device="cuda")
+        s = torch.empty_like(y)
+        for jj in range(self.c.k):
+            p = vals64 * X[:, jj].to(torch.int64)[self.cidx]
+            cp = torch.nn.functional.pad(torch.cumsum(p, 0), (1, 0))
+            y[:, jj] = cp[b] - cp[a]
+            cp = torch.nn.functional.pad(torch.cumsum(p.abs(), 0), (1, 0))
+            s[:, jj] = cp[b] - cp[a]
+        return y, s
+
+    def want(self, alpha=None, beta=None):
+        c = self.c
+        alpha, beta = c.alpha if alpha is None else alpha, c.beta if beta is None else beta
+        return alpha * self.y_ref + (beta * self.y0 if beta else 0)
+
+    def fresh_y(self, beta=None, y0=None):
+        """(buffer, view): the view holds Y0 -- NaN when beta == 0 --, the other columns the sentinel"""
+        c = self.c
+        beta = c.beta if beta is None else beta
+        Yw = torch.full((self.rows, c.yw), SENTINEL, dtype=self.dt, device="cuda")
+        Y = Yw[:, c.y_off:c.y_off + c.k]
+        if beta == 0:
+            Y.fill_(float("nan"))
+        else:
+            Y.copy_((self.y0 if y0 is None else y0).to(self.dt))
+        assert Yw.data_ptr() % 256 == 0
+        return Yw, Y
+
+    def run(self, M, vals=None, alpha=None, beta=None, debug=False):
+        c = self.c
+        alpha, beta = c.alpha if alpha is None else alpha, c.beta if beta is None else beta
+        Yw, Y = self.fresh_y(beta)
+        M.csrmm(self.vals if vals is None else vals, self.off, self.ci, self.X, Y=Y, alpha=float(alpha), beta=float(beta),
+                debug_synchronous=debug)
+        torch.cuda.synchronize()
+        c0, c1 = c.y_off, c.y_off + c.k
+        assert bool((Yw[:, :c0] == SENTINEL).all()) and bool((Yw[:, c1:] == SENTINEL).all()), f"{c.name}: a column of the buffer outside Y was written"
+        return Y
+
+
+def _assert_exact(name, Y, want, off64, what=""):
+    got, ref = Y.to(torch.float64), want.to(torch.float64)
+    if torch.equal(got, ref):
+        return
+    bad = (got != ref) | torch.isnan(got)
+    at = torch.nonzero(bad)
+    r, j = int(at[0, 0]), int(at[0, 1])
+    pytest.fail(f"{name} {what}: {int(bad.sum())} of {bad.numel()} entries differ from the exact reference, in {int(bad.any(1).sum())} rows and "
+                f"columns {sorted(set(at[:, 1].tolist()))[:48]}; first: row {r} (nonzeros {int(off64[r])}..{int(off64[r + 1])}) column {j}: "
+                f"got {float(got[r, j])!r}, want {float(ref[r, j])!r}")
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+
+
+@pytest.mark.parametrize("case", ORDERED, ids=lambda c: c.name)
+def test_form_runs_and_is_exact(M, mats, capfd, case):
+    c = case
+    call = Call(mats(c.mat), c)
+    # the condition under which every association order is exact, on the reference's own sums
+    worst = int((abs(c.alpha) * call.s + abs(c.beta) * call.y0.abs()).max())
+    assert worst <= EXACT[c.prec], f"{c.name}: |alpha| sum |a x| + |beta| |y0| reaches {worst}"
+    assert int(call.s.min()) >= 0 and int(call.cidx.min()) >= 1 and int(call.cidx.max()) == call.cols - 1
+    capfd.readouterr()
+    Y = call.run(M, debug=True)
+    log = [(n, int(g), int(b)) for n, g, b in LAUNCH.findall(capfd.readouterr().out)]
+    expect = c.launches()
+    assert log == [e[:3] for e in expect], f"{c.name}: the call launched {log}, the dispatch rule says {expect}"
+    _assert_exact(c.name, Y, call.want(), call.off64)
+    Y2 = call.run(M)
+    assert torch.equal(_bits(Y), _bits(Y2)), f"{c.name}: a second call gives other bits"
+
+
+@pytest.mark.parametrize("case", sorted(F.CONTAINMENT, key=lambda c: MAT_ORDER[c.mat]), ids=lambda c: c.name)
+def test_nan_and_inf_stay_where_they_are(M, mats, case):
+    """NaN in X[0, :] (the row the masked dummy gathers read; no nonzero references column 0) reaches nothing; a NaN matrix value
+    poisons all k columns of its row only -- on a short row, a row of exactly one tile and the giant row, whose sums travel through
+    the carries and the fix-up --; an Inf in X[c, j] column j of the rows that reference c only; NaN in Y0 is never read with
+    beta = 0.  Everything else is bit for bit the clean run."""
+    c = case
+    mat = mats(c.mat)
+    call = Call(mat, c)
+    clean = call.run(M)
+    _assert_exact(c.name, clean, call.want(), call.off64, "clean run")
+    k, rows = c.k, call.rows
+
+    def compare(Y, mask, what):
+        assert torch.equal(_bits(Y)[~mask], _bits(clean)[~mask]), f"{c.name}: {what}: entries outside the poisoned ones differ from the clean run"
+        assert not bool(torch.isfinite(Y[mask]).any()), f"{c.name}: {what}: a poisoned entry is finite"
+
+    none = torch.zeros(rows, k, dtype=torch.bool, device="cuda")
+    # 1. NaN in row 0 of X (the whole buffer row)
+    keep = call.Xw[0].clone()
+    call.Xw[0] = float("nan")
+    compare(call.run(M), none, "NaN in X[0, :]")
+    call.Xw[0] = keep
+    # 2. NaN matrix values
+    lens = torch.from_numpy(mat.s.lens).cuda()
+    T = c.groups()[0].tile
+    picks = [int(torch.nonzero(lens == 5)[0]), int(torch.nonzero(lens == T - 1)[0]), mat.giant_row]
+    vals = call.vals.clone()
+    mask = none.clone()
+    for r in picks:
+        lo, hi = int(call.off64[r]), int(call.off64[r + 1])
+        vals[(lo + hi) // 2] = float("nan")
+        mask[r, :] = True
+    compare(call.run(M, vals=vals), mask, f"NaN values in rows {picks}")
+    del vals
+    # 3. Inf in X[c1, 0] and X[c2, k - 1]
+    mask = none.clone()
+    q = int(call.off64[picks[0]])
+    spots = [(int(call.cidx[q]), 0), (int(call.cidx[q + 1]) if int(call.cidx[q + 1]) != int(call.cidx[q]) else int(call.cidx[q + 2]), k - 1)]
+    kept = []
+    for col, j in spots:
+        at = torch.nonzero(call.cidx == col)[:, 0]
+        hit = torch.unique(torch.searchsorted(call.off64, at, right=True) - 1)
+        assert hit.numel() >= 1
+        mask[hit, j] = True
+        kept.append(float(call.X[col, j]))
+        call.X[col, j] = float("inf")
+    compare(call.run(M), mask, f"Inf in X at {spots}")
+    for (col, j), v in zip(spots, kept):
+        call.X[col, j] = v
+    # 4. beta = 0: Y0 = NaN is never read (alpha = -2)
+    Y = call.run(M, alpha=c.alpha, beta=0)
+    _assert_exact(c.name, Y, call.want(c.alpha, 0), call.off64, "beta = 0 over a NaN Y")

@@ -192,13 +192,19 @@ def main():
             else:                                      # SpMM
                 k = int(rng.integers(1, 40)); padx, pady = int(rng.integers(0, 3)), int(rng.integers(0, 3))
                 Xw = (torch.rand(cols, k + padx, device="cuda", dtype=torch.float64) * 2 - 1).to(tdt); X = Xw[:, padx:]
-                Yw = torch.zeros(rows, k + pady, dtype=tdt, device="cuda"); Y = Yw[:, pady:]
-                M.csrmm(val_v, off_v, col_v, X, Y=Y)
+                plain = rng.random() < 0.5
+                alpha, beta = (1.0, 0.0) if plain else (float(rng.uniform(-2, 2)), float(rng.choice([0.0, 0.5, -1.0])))
+                Y0 = (torch.rand(rows, k, device="cuda", dtype=torch.float64) * 2 - 1).to(tdt)
+                Yw = torch.zeros(rows, k + pady, dtype=tdt, device="cuda"); Y = Yw[:, pady:]; Y.copy_(Y0)
+                M.csrmm(val_v, off_v, col_v, X, Y=Y, alpha=alpha, beta=beta)
                 prod = val.double()[:, None] * X.double()[col.long()]
                 g = segsum(prod)
                 s = segsum(prod.abs())
-                err = (Y.double() - g).abs(); tol = cfac[:, None] * eps * s
-                bad = (err > tol) | ((lens_t == 0)[:, None] & (Y != 0))
+                want = alpha * g + beta * Y0.double()
+                tol = cfac[:, None] * eps * (abs(alpha) * s + abs(beta) * Y0.double().abs()) + (0 if plain else 4 * eps * want.abs())
+                err = (Y.double() - want).abs()
+                bad = err > tol
+                if plain: bad |= (lens_t == 0)[:, None] & (Y != 0)
                 if pady: bad = bad | (Yw[:, :pady] != 0).any(dim=1, keepdim=True)
                 ratio = float((err / (tol + 1e-300)).max()) if rows else 0.0
             if bool(bad.any()):
