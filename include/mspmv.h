@@ -55,7 +55,7 @@ extern "C" {
  * no HIP headers (NULL = the default stream). */
 typedef void *mspmv_stream_t;
 
-#define MSPMV_VERSION 102 /* (the matrix addition mspmv_csr_add_*, the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, and the mixed-precision ones, mspmv_csrmv_mixed_* / mspmv_csrmv_mixed_prepared_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
+#define MSPMV_VERSION 102 /* (the accessors of the band-major plan's stacked matrix, mspmv_csrmv_plan_row_offsets / _columns / _values, the matrix addition mspmv_csr_add_*, the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, and the mixed-precision ones, mspmv_csrmv_mixed_* / mspmv_csrmv_mixed_prepared_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
 int mspmv_version(void);
 
 /* hipGetErrorString for codes returned by this library. */
@@ -226,6 +226,16 @@ int mspmv_csrmv_plan_apply_f32(void *d_plan, size_t plan_bytes, const float *d_x
 int mspmv_csrmv_plan_apply_f64(void *d_plan, size_t plan_bytes, const double *d_x, double *d_y,
                                int32_t rows, int32_t cols, int32_t nnz, int32_t bands,
                                double alpha, double beta, mspmv_stream_t stream, int debug_sync);
+/* The plan's pieces, for callers that want the stacked matrix itself and for the tests: A' = [A_0; A_1; ...; A_{bands-1}] as an
+ * ordinary CSR matrix of bands * rows rows -- its bands * rows + 1 row offsets, its nnz column indices (absolute, as in A) and its
+ * nnz values of value_bytes each.  band_width = max(1, ceil(cols / bands)); entry j of row r of A lies in stacked row
+ * (column / band_width) * rows + r; inside a stacked row the entries keep the order they have in A when every row of A has its
+ * columns in non-decreasing order (rows in another order: some order, the same entries).  Device pointers into d_plan, valid after
+ * _build has completed on its stream; `bands` is the count passed to _build (0 = the automatic one); NULL for a NULL plan or sizes
+ * mspmv_csrmv_plan_size refuses.  Nothing is launched, nothing is read from the device. */
+const int32_t *mspmv_csrmv_plan_row_offsets(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t bands);
+const int32_t *mspmv_csrmv_plan_columns(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t bands);
+const void *mspmv_csrmv_plan_values(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t bands);
 
 /* ---- extension: HOT-COLUMN PLAN for a matrix whose x is far larger than the caches and whose columns are referenced
  * very unevenly (scale-free graphs: BASELINE config 5; opt-in, the stateless calls never use it).  Such a CsrMV runs at

@@ -159,6 +159,9 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "mspmv_csrmv_plan_apply_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, ctypes.c_size_t, vp, vp, i32, i32, i32, i32, ct, ct, vp, ctypes.c_int]
+    for name in ("mspmv_csrmv_plan_row_offsets", "mspmv_csrmv_plan_columns", "mspmv_csrmv_plan_values"):
+        getattr(lib, name).restype = vp
+        getattr(lib, name).argtypes = [vp, i32, i32, i32, i32, i32]
     for name, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
         fn = getattr(lib, "mspmv_csr_transpose_" + name)
         fn.restype = ctypes.c_int
@@ -185,6 +188,8 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "mspmv_csr_add_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, sz_p, i32, i32, ct, vp, vp, vp, i32, ct, vp, vp, vp, i32, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.mspmv_csrmv_hotcols_skew.restype = ctypes.c_int
+    lib.mspmv_csrmv_hotcols_skew.argtypes = [vp, i32, i32, i32, vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.mspmv_csrmv_hotcols_size.restype = ctypes.c_int
     lib.mspmv_csrmv_hotcols_size.argtypes = [i32, i32, i32, i32, sz_p]
     lib.mspmv_csrmv_hotcols_build.restype = ctypes.c_int
@@ -900,9 +905,12 @@ def csr_symmetrize(a, stream=None):
 class CsrMVPlan:
     """The opt-in prepared plan (mspmv_csrmv_plan_*): a band-major copy of the matrix made once, so that every
     XCD gathers from an L2-sized slice of x.  For a matrix that is multiplied many times and whose x does not
-    fit an XCD's 4 MiB L2; the stateless `csrmv` never uses it.  `plan(x, y)` computes y = alpha*A*x + beta*y."""
+    fit an XCD's 4 MiB L2; the stateless `csrmv` never uses it.  `plan(x, y)` computes y = alpha*A*x + beta*y.
+    `storage`: a caller-provided uint8 tensor on the matrix's device of at least `bytes` bytes (mspmv_csrmv_plan_size) that the
+    plan is built into, whatever it held before; by default the plan allocates its own.  `debug_synchronous`: the build prints
+    its launch lines and synchronises after each, as the same argument of `plan(x, y)` does for an apply."""
 
-    def __init__(self, values, row_offsets, column_indices, num_cols: int, bands: int = 0, stream=None):
+    def __init__(self, values, row_offsets, column_indices, num_cols: int, bands: int = 0, stream=None, storage=None, debug_synchronous: bool = False):
         import torch
         self.rows, self.cols, self.nnz = row_offsets.numel() - 1, int(num_cols), values.numel()
         y_probe = torch.empty(0, dtype=values.dtype, device=values.device)
@@ -914,10 +922,32 @@ class CsrMVPlan:
         _check(load_library().mspmv_csrmv_plan_size(self.rows, self.cols, self.nnz, self.vb, int(bands), ctypes.byref(size),
                                                     ctypes.byref(used)), "mspmv_csrmv_plan_size")
         self.bytes, self.bands = int(size.value), int(used.value)
-        self.storage = torch.empty(max(self.bytes, 1), dtype=torch.uint8, device=values.device)
+        if storage is None:
+            storage = torch.empty(max(self.bytes, 1), dtype=torch.uint8, device=values.device)
+        elif storage.dtype != torch.uint8 or storage.device != values.device or storage.dim() != 1 or not storage.is_contiguous() \
+                or storage.numel() < self.bytes or storage.data_ptr() % 16:
+            raise MspmvError(f"CsrMVPlan: storage must be a contiguous 16-byte aligned uint8 tensor on {values.device} of at least {self.bytes} bytes")
+        self.storage = storage
         fn = load_library().mspmv_csrmv_plan_build_f32 if self.vb == 4 else load_library().mspmv_csrmv_plan_build_f64
         _check(fn(ctypes.c_void_p(self.storage.data_ptr()), self.bytes, _ptr(values), _ptr(row_offsets), _ptr(column_indices),
-                  self.rows, self.cols, self.nnz, self.bands, _stream_handle(stream), 0), "mspmv_csrmv_plan_build")
+                  self.rows, self.cols, self.nnz, self.bands, _stream_handle(stream), int(bool(debug_synchronous))), "mspmv_csrmv_plan_build")
+
+    def _view(self, fn, count, dtype):
+        import torch
+        ptr = fn(ctypes.c_void_p(self.storage.data_ptr()), self.rows, self.cols, self.nnz, self.vb, self.bands)
+        if not ptr or count == 0:
+            return torch.empty(0, dtype=dtype, device=self.storage.device)
+        off = int(ptr) - self.storage.data_ptr()
+        return self.storage[off: off + count * torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+    def stacked(self):
+        """(row_offsets, column_indices, values) of the stacked matrix A' = [A_0; ...; A_{bands-1}] (mspmv_csrmv_plan_row_offsets /
+        _columns / _values): views of the plan's storage -- bands * rows + 1 offsets, nnz absolute column indices, nnz values"""
+        import torch
+        lib = load_library()
+        return (self._view(lib.mspmv_csrmv_plan_row_offsets, self.bands * self.rows + 1, torch.int32),
+                self._view(lib.mspmv_csrmv_plan_columns, self.nnz, torch.int32),
+                self._view(lib.mspmv_csrmv_plan_values, self.nnz, self.dtype))
 
     def __call__(self, x, y=None, alpha: float = 1.0, beta: float = 0.0, stream=None, debug_synchronous: bool = False):
         import torch

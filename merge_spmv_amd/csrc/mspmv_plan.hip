@@ -144,6 +144,8 @@ __global__ __launch_bounds__(256) void plan_scatter_kernel(const int *__restrict
 
 // y[r] = alpha * (y'[r] + y'[rows + r] + ...) + beta * y[r], bands added in order.  VEC: a thread folds one 16-byte unit
 // of rows per band (rows a multiple of the unit and y 16-byte aligned, so every band's row block is aligned too).
+// beta == 0: alpha * s + 0, as the stateless call's alpha / beta form writes it -- a row without entries gets +0.0 for a
+// negative alpha too (alpha * s alone gave -0.0 there, where one band and the stateless call give +0.0).
 template <typename V, bool VEC>
 __global__ __launch_bounds__(256) void plan_combine_kernel(const V *__restrict__ ypart, V *__restrict__ y, int rows, int bands, V alpha,
                                                            V beta)
@@ -156,11 +158,11 @@ __global__ __launch_bounds__(256) void plan_combine_kernel(const V *__restrict__
         vec_t s = *reinterpret_cast<const vec_t *>(ypart + r);
         for (int b = 1; b < bands; ++b) s += __builtin_nontemporal_load(reinterpret_cast<const vec_t *>(ypart + (size_t) b * rows + r));
         vec_t *out = reinterpret_cast<vec_t *>(y + r);
-        *out = beta == (V) 0 ? alpha * s : alpha * s + beta * *out;
+        *out = beta == (V) 0 ? alpha * s + (V) 0 : alpha * s + beta * *out;
     } else {
         V s = ypart[r];
         for (int b = 1; b < bands; ++b) s += __builtin_nontemporal_load(ypart + (size_t) b * rows + r);
-        y[r] = beta == (V) 0 ? alpha * s : alpha * s + beta * y[r];
+        y[r] = beta == (V) 0 ? alpha * s + (V) 0 : alpha * s + beta * y[r];
     }
 }
 
@@ -250,6 +252,15 @@ int plan_apply(void *d_plan, size_t plan_bytes, const V *d_x, V *d_y, int32_t ro
     return launched(stream, debug_sync, "plan_combine_kernel", grid);
 }
 
+// one region of the plan's storage (the accessors of the stacked matrix): NULL for no plan or sizes the layout refuses
+const void *plan_piece(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t bands, uint64_t PlanLayout::*off)
+{
+    PlanLayout L;
+    if (!d_plan || rows < 0 || cols < 0 || nnz < 0 || (value_bytes != 4 && value_bytes != 8) || bands < 0 ||
+        !make_layout(rows, cols, nnz, value_bytes, bands, L)) return nullptr;
+    return static_cast<const char *>(d_plan) + L.*off;
+}
+
 }  // namespace
 
 extern "C" {
@@ -290,6 +301,21 @@ int mspmv_csrmv_plan_apply_f64(void *d_plan, size_t plan_bytes, const double *d_
 {
     return plan_apply<double>(d_plan, plan_bytes, d_x, d_y, rows, cols, nnz, bands, alpha, beta, reinterpret_cast<hipStream_t>(stream),
                               debug_sync);
+}
+
+/* the plan's pieces, for callers that want the stacked matrix A' itself and for the tests: its bands * rows + 1 row offsets, its
+ * column indices (nnz int32, absolute) and its values (nnz of value_bytes).  Pointers into d_plan; nothing is launched. */
+const int32_t *mspmv_csrmv_plan_row_offsets(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t bands)
+{
+    return static_cast<const int32_t *>(plan_piece(d_plan, rows, cols, nnz, value_bytes, bands, &PlanLayout::offsets_off));
+}
+const int32_t *mspmv_csrmv_plan_columns(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t bands)
+{
+    return static_cast<const int32_t *>(plan_piece(d_plan, rows, cols, nnz, value_bytes, bands, &PlanLayout::cols_off));
+}
+const void *mspmv_csrmv_plan_values(const void *d_plan, int32_t rows, int32_t cols, int32_t nnz, int32_t value_bytes, int32_t bands)
+{
+    return plan_piece(d_plan, rows, cols, nnz, value_bytes, bands, &PlanLayout::values_off);
 }
 
 }  // extern "C"

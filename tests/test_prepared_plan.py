@@ -1,6 +1,7 @@
 """The opt-in prepared band-major plan (include/mspmv.h: mspmv_csrmv_plan_*): size query conventions on the CPU;
 on the GPU, parity of plan SpMV with the oracle for every band count, sorted and unsorted rows, degenerate
-shapes, alpha/beta, and bitwise reproducibility."""
+shapes, alpha/beta, and bitwise reproducibility.
+The stacked matrix itself, y on the bits and the launches are pinned in tests/test_plan_exact.py."""
 import ctypes
 
 import numpy as np
