@@ -449,6 +449,63 @@ int mspmv_csr_add_f64(void *d_temp, size_t *temp_bytes, int32_t rows, int32_t co
                       double *d_values_c, int32_t *d_row_offsets_c /* [rows + 1] */, int32_t *d_column_indices_c, int32_t *d_nnz_c,
                       mspmv_stream_t stream, int debug_sync);
 
+/* ---- extension: MATRIX PRODUCT  C = A * B  of two CSR matrices on the device (csrc/mspmv_gemm.hip; what csrgemm is in rocSPARSE /
+ * cuSPARSE): the Galerkin product R A P of a multigrid set-up, A A^T and A^T A, the two-hop neighbourhoods of a graph.
+ * INPUTS: A is rows x inner, B is inner x cols, each as three CSR arrays.  ANY valid CSR is accepted: rows need not be sorted and
+ * a column may repeat.  Column indices of A lie in [0, inner), those of B in [0, cols) (not checked, as everywhere).  A and B may be
+ * the same arrays; outputs must not alias inputs.
+ * mspmv_csr_gemm_products writes ONE int64 on the device: the sum over A's entries e of the length of B's row column_indices_a[e],
+ * the number of scalar products a * b.  The sum is 64-bit and exact (per-block sums, then one block adds them; no atomics).  The
+ * host does not learn it inside the call: the caller reads it (one 8-byte copy) and states it as `products` below.
+ * mspmv_csr_gemm_*: `products` is the caller's statement of that count.  The host sizes every launch and the temp storage from it
+ * and never reads device memory, so the call launches the same kernels whatever the data and can be captured in a graph.  The
+ * device VERIFIES it (the same 64-bit sum): if the true count differs, the call writes *d_nnz_c = -1 and leaves C unspecified, and
+ * still reads and writes nothing outside the arrays; it terminates whatever the inputs and whatever `products` says.
+ * OUTPUT: C in canonical form (rows sorted by column, no column twice).  Its pattern is the STRUCTURAL product: an entry whose value
+ * cancels to 0 stays.  d_row_offsets_c (rows + 1 entries) and *d_nnz_c (one int32 on the device) are always written and right for
+ * empty rows anywhere.  d_column_indices_c / d_values_c hold capacity_c entries: they are written only when nnz_c <= capacity_c,
+ * and then only their first nnz_c entries; otherwise they are left untouched and *d_nnz_c tells how much room a second call needs.
+ * capacity_c = products always suffices; capacity_c = 0 is the "symbolic" phase (count and offsets only).
+ * VALUES, defined bit for bit in the value type: each product a * b rounded on its own (no fused multiply-add), the products of one
+ * entry (i, j) of C added LEFT TO RIGHT in expansion order -- by the position of A's entry in its row, then by the position of B's
+ * entry in its row; the first product starts the sum.  So a lone product of -0.0 stays -0.0 and A * I is the duplicate-merged,
+ * sorted A bit for bit.  There is no alpha / beta: alpha A B + beta D is mspmv_csr_add_* on the result.  All three value pointers
+ * NULL: structure only (either entry point); values for some of the matrices and not for others: hipErrorInvalidValue (the pointer
+ * of a matrix without entries, or of a C without capacity, has no say).
+ * HOW: expand - sort - compress.  (1) len[e] per entry of A, its int32 scan start[], and the 64-bit total compared with `products`;
+ * (2) the list of products is cut into tiles of 2048 whatever the row lengths -- one entry of A that hits a row of B with a million
+ * entries costs what a million short rows cost --, each tile finds its entries of A by a search of start[] and writes its triples
+ * (row, column, a * b) with consecutive stores; (3) the triples are sorted stably by (row, column) with the radix passes of
+ * mspmv_coo_to_csr_*; (4) runs of equal (row, column) are added as in mspmv_csr_sum_duplicates_*; (5) one thread writes the -1.
+ * One thread adds one run, so a run of L products costs L serial adds; L is bounded by the longest row of A.
+ * Same two-phase temp storage (d_temp == NULL -> size, no work), 16-byte alignment, ownership, stream, debug_sync (one line per
+ * launch) and error conventions as mspmv_csr_add_*.  TEMP STORAGE: 8 bytes per entry of A; per product 8 + v bytes of triples, about
+ * 2 x (12 + v) + 4 for the sort, 4 + v for the sorted entries and 8 for the compression -- about 64 bytes per fp32 product, 6.4 GB
+ * for 100 M of them.
+ * LIMITS: rows, inner, cols, nnz_a, nnz_b, products, capacity_c >= 0; rows + products, rows + nnz_a and inner + nnz_b each
+ * <= 2^31 - 65537; entries together with rows == 0, inner == 0 or cols == 0 are refused; products == 0 (nnz_a == 0 included) gives
+ * all-zero offsets and a count of 0 (still verified).  Measured on MI355X against rocSPARSE's csrgemm_buffer_size + csrgemm_nnz +
+ * csrgemm on the same arrays, patterns equal (profiles/gemm_bench.txt; DESIGN.md 4 "Product"), fp32: A A^T of a 5-point grid of
+ * 2000 x 2000 (100 M products) 15.0 ms against 1.5 ms, A A of a uniform matrix of 1 M rows x 8 (64 M) 8.5 against 2.8 ms -- on short
+ * regular rows rocSPARSE's LDS hash accumulator is the faster scheme --; A A^T of an R-MAT graph (246 M products, runs up to 5424)
+ * 28.6 against 164 ms; 8 entries of A into one row of B of 2^24 entries 12.4 against 804 ms. ---- */
+int mspmv_csr_gemm_products(void *d_temp, size_t *temp_bytes,
+                            const int32_t *d_row_offsets_a, const int32_t *d_column_indices_a, int32_t rows, int32_t inner, int32_t nnz_a,
+                            const int32_t *d_row_offsets_b, int32_t nnz_b,
+                            int64_t *d_products, mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_gemm_f32(void *d_temp, size_t *temp_bytes, int32_t rows, int32_t inner, int32_t cols,
+                       const float *d_values_a, const int32_t *d_row_offsets_a, const int32_t *d_column_indices_a, int32_t nnz_a,
+                       const float *d_values_b, const int32_t *d_row_offsets_b, const int32_t *d_column_indices_b, int32_t nnz_b,
+                       int32_t products, int32_t capacity_c,
+                       float *d_values_c, int32_t *d_row_offsets_c /* [rows + 1] */, int32_t *d_column_indices_c, int32_t *d_nnz_c,
+                       mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_gemm_f64(void *d_temp, size_t *temp_bytes, int32_t rows, int32_t inner, int32_t cols,
+                       const double *d_values_a, const int32_t *d_row_offsets_a, const int32_t *d_column_indices_a, int32_t nnz_a,
+                       const double *d_values_b, const int32_t *d_row_offsets_b, const int32_t *d_column_indices_b, int32_t nnz_b,
+                       int32_t products, int32_t capacity_c,
+                       double *d_values_c, int32_t *d_row_offsets_c /* [rows + 1] */, int32_t *d_column_indices_c, int32_t *d_nnz_c,
+                       mspmv_stream_t stream, int debug_sync);
+
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */
 typedef struct mspmv_launch_info {

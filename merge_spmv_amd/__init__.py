@@ -18,7 +18,7 @@ import os
 from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
-           "csr_add", "CsrAdd", "csr_symmetrize",
+           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -188,6 +188,11 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "mspmv_csr_add_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, sz_p, i32, i32, ct, vp, vp, vp, i32, ct, vp, vp, vp, i32, vp, vp, vp, vp, vp, ctypes.c_int]
+        fn = getattr(lib, "mspmv_csr_gemm_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, sz_p, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.mspmv_csr_gemm_products.restype = ctypes.c_int
+    lib.mspmv_csr_gemm_products.argtypes = [vp, sz_p, vp, vp, i32, i32, i32, vp, i32, vp, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_skew.restype = ctypes.c_int
     lib.mspmv_csrmv_hotcols_skew.argtypes = [vp, i32, i32, i32, vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.mspmv_csrmv_hotcols_size.restype = ctypes.c_int
@@ -900,6 +905,110 @@ def csr_symmetrize(a, stream=None):
         raise MspmvError(f"csr_symmetrize: the matrix must be square, got {a.rows} x {a.cols}")
     vt, ot, ct, _ = csr_transpose(a.values, a.row_offsets, a.column_indices, a.cols, stream=stream)
     return csr_add(a, DeviceCsr(a.cols, a.rows, ot, ct, vt), stream=stream, trim=True)[0]
+
+
+_MAX_ITEMS = 2 ** 31 - 1 - 65536
+
+
+def _gemm_check(a, b, what: str):
+    """the checks the C ABI cannot make for the two factors of a product; returns (nnz_a, nnz_b, device)"""
+    nnz_a, nnz_b = _add_check(a, "a", what), _add_check(b, "b", what)
+    if int(a.cols) != int(b.rows):
+        raise MspmvError(f"{what}: a is {a.rows} x {a.cols}, b is {b.rows} x {b.cols}")
+    dev = a.row_offsets.device
+    if b.row_offsets.device != dev:
+        raise MspmvError(f"{what}: b must be on {dev}")
+    if (a.values is None) != (b.values is None):
+        raise MspmvError(f"{what}: values for both matrices or for neither (structure only)")
+    if a.values is not None and a.values.dtype != b.values.dtype:
+        raise MspmvError(f"{what}: a holds {a.values.dtype}, b {b.values.dtype}")
+    return nnz_a, nnz_b, dev
+
+
+def csr_gemm_products(a, b, stream=None) -> int:
+    """The number of scalar products a_ik * b_kj of A * B (mspmv_csr_gemm_products): the sum over A's entries of the length of the
+    row of B they point at, exact in 64 bits.  Reads the count back: it SYNCHRONISES with `stream`."""
+    import torch
+    nnz_a, nnz_b, dev = _gemm_check(a, b, "csr_gemm_products")
+    out = torch.empty(1, dtype=torch.int64, device=dev)
+    args = (_ptr(a.row_offsets), _ptr(a.column_indices), int(a.rows), int(a.cols), nnz_a, _ptr(b.row_offsets), nnz_b,
+            ctypes.c_void_p(out.data_ptr()))
+    _two_phase(load_library().mspmv_csr_gemm_products, "mspmv_csr_gemm_products", dev, stream, args)
+    if stream is not None and hasattr(stream, "synchronize"):
+        stream.synchronize()
+    return int(out.item())
+
+
+class CsrGemm:
+    """C = A * B on the device (mspmv_csr_gemm_*) with the outputs and the temp storage allocated ONCE, so that calling the object
+    again can be captured in a graph and replayed after the factors' tensors were overwritten in place (new values, or new patterns
+    of the same sizes and the same number of products).  a: generators.DeviceCsr of rows x inner, b: of inner x cols, any valid CSR
+    (rows need not be sorted, columns may repeat); values for both or for neither (structure only).  products: the count of
+    csr_gemm_products(a, b), which is called (and synchronises) when it is None.  capacity: the entries column_indices / values
+    hold, `products` by default (always enough); 0 is the symbolic phase.  Holds row_offsets (rows + 1), column_indices, values and
+    `count` (a one-element int32 CUDA tensor: C's entries, -1 when `products` is not the factors' count; above `capacity`, nothing
+    but row_offsets and count was written) and reads nothing back; `trimmed()` waits for the stream of the last call, reads the
+    count and returns the DeviceCsr narrowed to it."""
+
+    def __init__(self, a, b, products: Optional[int] = None, capacity: Optional[int] = None, stream=None):
+        import torch
+        self.nnz_a, self.nnz_b, dev = _gemm_check(a, b, "csr_gemm")
+        self.a, self.b = a, b
+        self.rows, self.inner, self.cols = int(a.rows), int(a.cols), int(b.cols)
+        self.products = csr_gemm_products(a, b, stream=stream) if products is None else int(products)
+        if self.products < 0 or self.rows + self.products > _MAX_ITEMS:
+            raise MspmvError(f"csr_gemm: rows + products = {self.rows} + {self.products} must lie in [0, 2^31 - 65537]")
+        self.capacity = self.products if capacity is None else int(capacity)
+        if self.capacity < 0 or self.capacity > _MAX_ITEMS:
+            raise MspmvError(f"csr_gemm: capacity {self.capacity} must lie in [0, 2^31 - 65537]")
+        self.dtype = torch.float32 if a.values is None else a.values.dtype
+        lib = load_library()
+        self._fn = lib.mspmv_csr_gemm_f32 if self.dtype == torch.float32 else lib.mspmv_csr_gemm_f64
+        self.row_offsets = torch.empty(self.rows + 1, dtype=torch.int32, device=dev)
+        self.column_indices = torch.empty(self.capacity, dtype=torch.int32, device=dev)
+        self.values = None if a.values is None else torch.empty(self.capacity, dtype=self.dtype, device=dev)
+        self.count = torch.empty(1, dtype=torch.int32, device=dev)
+        self.temp = None
+        self._stream = None
+        self(stream=stream)
+
+    def __call__(self, stream=None):
+        """runs the product on the factors' tensors as they are now, into the same outputs; asynchronous on `stream`"""
+        a, b = self.a, self.b
+        if _gemm_check(a, b, "CsrGemm")[:2] != (self.nnz_a, self.nnz_b) or (a.values is None) != (self.values is None):
+            raise MspmvError(f"CsrGemm: the factors must keep their {self.nnz_a} and {self.nnz_b} entries")
+        args = (self.rows, self.inner, self.cols, _ptr(a.values), _ptr(a.row_offsets), _ptr(a.column_indices), self.nnz_a,
+                _ptr(b.values), _ptr(b.row_offsets), _ptr(b.column_indices), self.nnz_b, self.products, self.capacity,
+                _ptr(self.values), ctypes.c_void_p(self.row_offsets.data_ptr()), _ptr(self.column_indices),
+                ctypes.c_void_p(self.count.data_ptr()))
+        self.temp = _two_phase(self._fn, "mspmv_csr_gemm", self.row_offsets.device, stream, args, temp=self.temp)
+        self._stream = stream
+        return self
+
+    def trimmed(self):
+        from .generators import DeviceCsr
+        if self._stream is not None and hasattr(self._stream, "synchronize"):
+            self._stream.synchronize()                           # (the count is read on the current stream: wait for the call's first)
+        n = int(self.count.item())
+        if n < 0:
+            raise MspmvError(f"csr_gemm: the factors do not have the {self.products} products stated")
+        if n > self.capacity:
+            raise MspmvError(f"csr_gemm: C has {n} entries, the outputs hold {self.capacity}")
+        return DeviceCsr(self.rows, self.cols, self.row_offsets, self.column_indices[:n], None if self.values is None else self.values[:n])
+
+
+def csr_gemm(a, b, stream=None, trim: bool = True):
+    """C = A * B for two generators.DeviceCsr, a of rows x inner and b of inner x cols, any valid CSR (mspmv_csr_gemm_*): C in
+    canonical form (rows sorted by column, no column twice), its pattern the structural product, every value the products a * b of
+    its entry, each rounded on its own, added left to right in the order of A's row and, under one entry of A, of B's row.  values
+    None in both: structure only.  Reads the number of products back first (csr_gemm_products: it synchronises).  Returns a DeviceCsr:
+    with trim=True (which reads C's count back too) narrowed to C's entries; with trim=False column_indices / values keep
+    `products` entries, of which the first row_offsets[-1] are written."""
+    from .generators import DeviceCsr
+    op = CsrGemm(a, b, stream=stream)
+    if trim:
+        return op.trimmed()
+    return DeviceCsr(op.rows, op.cols, op.row_offsets, op.column_indices, op.values)
 
 
 class CsrMVPlan:
