@@ -75,7 +75,22 @@ int mspmv_csrmv_f64(void *d_temp, size_t *temp_bytes, const double *d_values,
 /* ---- extension: y = alpha*A*x + beta*y.  The reference
  * parses --alpha/--beta (gpu_spmv.cu:721-722) and carries them in SpmvParams
  * (agent_spmv_orig.cuh:109-110) but its CsrMV forces 1/0.  With beta == 0 the
- * old contents of y are ignored (never read), as in BLAS. ---- */
+ * old contents of y are ignored (never read), as in BLAS.
+ *
+ * The definition (every kernel form and dispatch path; tests/test_axpby_exact.py pins it on the bits):
+ *   * a row that lies within one tile is written once, as
+ *         y[r] = alpha * s + (beta == 0 ? 0 : beta * y[r]),      s = the sum of the row's products, +0.0 for a row without entries;
+ *     the multiply and the add may be fused;
+ *   * of a row that spans tiles, the tile in which it ENDS writes that formula with s = the sum of the products it holds of the
+ *     row, and every other tile's share -- its carry -- arrives as  y[r] = y[r] + alpha * carry  (fix-up kernels), or is added
+ *     into s before the formula is applied (the one-launch kernel).  alpha meets every product exactly once and beta * y[r]
+ *     enters exactly once; a column-band pass after the first adds its share with beta = 1;
+ *   * a row without entries gets alpha * (+0.0) + ..., so with beta == 0 it is +0.0 WHATEVER THE SIGN OF alpha: alpha * 0 alone would
+ *     be -0.0 for alpha < 0, and the "+ 0" of the formula is what turns it into +0.0.  With beta != 0 it is beta * y[r] exactly
+ *     (-0.0 only where that product is -0.0 and alpha * 0 is too).
+ * So on inputs without zeros a zero in y is either the empty sum or an exact cancellation, and both are +0.0; (alpha, beta) =
+ * (1, 0) gives the bits of mspmv_csrmv_*.  Where every intermediate is exactly representable the result does not depend on the
+ * path, the tile shape or the order of the carries (the atomic fix-up included). ---- */
 int mspmv_csrmv_axpby_f32(void *d_temp, size_t *temp_bytes, const float *d_values,
                           const int32_t *d_row_offsets, const int32_t *d_column_indices,
                           const float *d_x, float *d_y, int32_t rows, int32_t cols,

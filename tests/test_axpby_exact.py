@@ -1,0 +1,521 @@
+"""y = alpha*A*x + beta*y on every CsrMV dispatch path, BIT FOR BIT against the int64 model of tests/axpby_model.py.
+
+Every CsrMV kernel is compiled twice (AXPBY = false / true), the fix-up kernels take alpha, the column-band passes rewrite beta per
+pass: a second copy of the hot path.  The inputs here are small non-zero integers and (alpha, beta) dyadic, sized so that every sum
+in every association is exact (axpby_model.model asserts it per row): y is then defined on the bits, whichever kernels compute it,
+and every comparison below is on the bit patterns -- no tolerance anywhere, -0.0 is not +0.0 (include/mspmv.h at
+mspmv_csrmv_axpby_*: a zero of a correct call on such data is an exact cancellation or the empty sum, +0.0).
+
+Forms are forced with the development setters (include/mspmv_dev.h) the way tests/test_gpu_parity.py, test_band_passes.py and
+test_tdm.py force them, and every form a test claims is asserted to have run (launch_info, band_passes, clocked_bands, the launch
+log).  PROBLEMS / USED list every (matrix, pair) of this file: tests/test_axpby_model.py checks the exactness bound on each of them
+on the CPU, so an edited shape cannot silently turn an exact test into a rounding-dependent one.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import axpby_model as A
+from axpby_model import PAIRS
+
+torch = pytest.importorskip("torch")
+import test_gpu_parity as T          # noqa: E402 - PATHS, SHAPES, COMPACT_SHAPES, the M fixture
+import test_tdm as TDM               # noqa: E402 - its SHAPES, _clocked, _reset
+from test_gpu_parity import M        # noqa: E402,F401 - (fixture)
+from test_mixed_precision import off_by_one   # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+DT = {"f32": (np.float32, 4), "f64": (np.float64, 8)}
+PRECS = ["f32", "f64"]
+# beta == 0 with alpha < 0: alpha * (+0) is -0.0, which the "+ 0" of the definition turns into +0.0 on a row without entries (no
+# pair of PAIRS has alpha < 0 with beta == 0, and with beta != 0 the non-zero beta * y0 hides the sign of alpha * 0)
+NEG_ALPHA_ZERO_BETA = (-0.5, 0)
+ALL_PAIRS = PAIRS + [NEG_ALPHA_ZERO_BETA]
+NO_FUSED, TWO_LAUNCH = 16, 0x40000000
+
+
+# ---------------------------------------------------------------------------------------------------------------- the problems
+
+def _tile_grid(ipt):
+    def make(rng):                                  # the matrix of test_gpu_parity.test_every_compiled_tile_shape
+        lens = np.minimum((rng.pareto(1.1, 20000) * 2).astype(np.int64), 50000)
+        lens[7777] = 90000
+        return 20000, 20000, lens
+    return make, 256 * 100 + ipt
+
+
+# fix-up depth (item d): rows + nnz just above FIX_CHUNK (512) tiles of the large-problem shape -- 256 x 11 items in fp32, 256 x 7
+# in fp64 at this size -- so that the multi-level fix-up needs a second level (asserted from launch_info where it is used)
+DEEP_NNZ = {"f32": 1_445_000, "f64": 920_000}
+
+
+def _deep_one_row(nnz):
+    def make(rng):                                  # one row holds nearly everything: every tile carries into the same key
+        lens = np.zeros(4001, np.int64); lens[::100] = 1; lens[2000] = nnz
+        return 4001, 5000, lens
+    return make
+
+
+def _deep_long_rows(nnz):
+    def make(rng):                                  # rows of 3000-6000: a few carries on each row
+        lens = rng.integers(3000, 6001, nnz // 4500)
+        return lens.size, 5000, lens
+    return make
+
+
+def _planted(tile_items):
+    """item f: short rows, a stretch of empty rows wider than a tile, a giant row between two short ones -- and one row made to END
+    exactly on the tile boundary at merge-path diagonal 2 * tile_items (row r ends at diagonal (r + 1) + row_offsets[r + 1])"""
+    def make(rng):
+        rows, g = 12000, 6000
+        lens = rng.integers(0, 7, rows).astype(np.int64)
+        lens[2000:5800] = 0                          # (more than a tile of row ends)
+        lens[g - 1], lens[g], lens[g + 1] = 2, 40000, 3
+        lens[0], lens[rows - 1] = 4, 5
+        ends = np.arange(1, rows + 1) + np.cumsum(lens)
+        d = 2 * tile_items
+        r = int(np.searchsorted(ends, d, side="right")) - 1
+        assert 0 < r < 2000
+        lens[r] += d - ends[r]
+        return rows, 3000, lens
+    return make
+
+
+def planted_rows(csr, tile_items):
+    """label -> row of the rows item f plants a non-finite y0 at"""
+    off = csr.row_offsets.astype(np.int64)
+    ends = np.arange(1, csr.rows + 1) + off[1:]
+    on_boundary = np.flatnonzero(ends == 2 * tile_items)
+    assert on_boundary.size == 1 and off[on_boundary[0] + 1] > off[on_boundary[0]]
+    rows = {"first": 0, "last": csr.rows - 1, "empty": 4000, "before_giant": 5999, "giant": 6000, "after_giant": 6001,
+            "ends_on_tile_boundary": int(on_boundary[0])}
+    assert off[4001] == off[4000] and off[6001] - off[6000] == 40000
+    return rows
+
+
+def _tiny_x(cols, rows, hi):
+    return lambda rng: (rows, cols, rng.integers(0, hi, rows))
+
+
+TINY_COLS = [1, 512, 513, 1024, 1025]               # the LDS copy of x and its edges (test_tiny_x_is_gathered_from_lds)
+TINY_ROWS = [(3001, 9), (50003, 40)]
+PLANTED_TILES = [256 * 7, 256 * 11]                 # the tile sizes the paths of item f run
+
+# label -> (lambda rng: (rows, cols, lens), seed, vmax, xmax)
+PROBLEMS = {}
+for _n, _f in T.COMPACT_SHAPES.items():
+    PROBLEMS["parity:" + _n] = (_f, sum(map(ord, _n)), 2, 3)
+for _ipt in (7, 11):
+    PROBLEMS[f"tile_grid:{_ipt}"] = _tile_grid(_ipt) + (2, 3)
+for _p, _nnz in DEEP_NNZ.items():
+    PROBLEMS[f"deep_one_row:{_p}"] = (_deep_one_row(_nnz), 41, 1, 1)          # (rows longer than 200 000: values and x of +-1)
+    PROBLEMS[f"deep_long_rows:{_p}"] = (_deep_long_rows(_nnz), 42, 1, 1)
+for _n in ("giant_row", "mostly_empty", "ragged_tail"):
+    PROBLEMS["tdm:" + _n] = (TDM.SHAPES[_n], len(_n) * 7, 2, 3)
+for _t in PLANTED_TILES:
+    PROBLEMS[f"planted:{_t}"] = (_planted(_t), 43, 2, 3)
+for _c in TINY_COLS:
+    for _r, _h in TINY_ROWS:
+        PROBLEMS[f"tiny_x:{_c}:{_r}"] = (_tiny_x(_c, _r, _h), _c, 2, 3)
+
+# label -> the pairs some test below runs on it, per precision it runs in (filled in next to each test)
+USED = {}
+
+
+def uses(labels, pairs, precs=PRECS):
+    for label in labels:
+        assert label in PROBLEMS, label
+        for prec in precs:
+            USED.setdefault((label, prec), set()).update(pairs)
+
+
+class Problem:
+    def __init__(self, label, prec):
+        make, seed, vmax, xmax = PROBLEMS[label]
+        rng = np.random.default_rng(seed)
+        rows, cols, lens = make(rng)
+        self.label, self.prec = label, prec
+        self.dtype, self.vb = DT[prec]
+        self.csr, self.x, self.y0 = A.integer_problem(rng, rows, cols, np.asarray(lens, np.int64), self.dtype, vmax=vmax, xmax=xmax)
+        self._want = {}
+
+    def want(self, alpha, beta):
+        """the model's y: computed once per pair, shared by every test on this problem, never written to"""
+        if (alpha, beta) not in self._want:
+            w = A.model(self.csr, self.x, self.y0, alpha, beta)
+            w.setflags(write=False)
+            self._want[(alpha, beta)] = w
+        return self._want[(alpha, beta)]
+
+
+@functools.lru_cache(maxsize=None)
+def problem(label, prec):
+    return Problem(label, prec)
+
+
+# ------------------------------------------------------------------------------------------------------------------ on the GPU
+
+class OnDevice:
+    """a problem's arrays on the device (optionally all one element off a 16-byte boundary) and the calls on them"""
+
+    def __init__(self, Mod, P, shift=False):
+        self.M, self.P = Mod, P
+        self.place = off_by_one if shift else (lambda t: t)
+        self.tdt = torch.float32 if P.vb == 4 else torch.float64
+        c = P.csr
+        self.val, self.off, self.col, self.x = (self.place(torch.from_numpy(np.ascontiguousarray(a)).cuda())
+                                                for a in (c.values, c.row_offsets, c.column_indices, P.x))
+
+    def workspace(self, prepare=False, garbage=False):
+        ws = self.M.CsrMVWorkspace(self.P.csr.rows, self.P.csr.nnz, self.tdt)
+        if garbage:
+            ws.buffer.random_(0, 255)               # (the hints of the one-launch kernel: every byte pattern, as in test_gpu_parity)
+        return ws.prepare(self.off) if prepare else ws
+
+    def axpby(self, ws, alpha, beta, y0=None, **kw):
+        """mspmv_csrmv_axpby_* (on a prepared workspace: mspmv_csrmv_prepared_*) on a copy of y0"""
+        c = self.P.csr
+        y = self.place(torch.from_numpy(np.array(self.P.y0 if y0 is None else y0, copy=True)).cuda())
+        self.M.csrmv(self.val, self.off, self.col, self.x, y=y, num_cols=c.cols, workspace=ws, alpha=float(alpha), beta=float(beta), **kw)
+        torch.cuda.synchronize()
+        return y.cpu().numpy()
+
+    def plain(self, ws):
+        """mspmv_csrmv_* into a y filled with NaN"""
+        c = self.P.csr
+        y = self.place(torch.full((c.rows,), float("nan"), dtype=self.tdt, device="cuda"))
+        self.M.csrmv(self.val, self.off, self.col, self.x, y=y, num_cols=c.cols, workspace=ws)
+        torch.cuda.synchronize()
+        return y.cpu().numpy()
+
+
+def same(got, want, *where):
+    gb, wb = A.bits(got), A.bits(want)
+    if not np.array_equal(gb, wb):
+        bad = np.flatnonzero(gb != wb)
+        raise AssertionError(f"{where}: {bad.size} of {gb.size} rows differ on the bits; first rows {bad[:5].tolist()}: "
+                             f"got {np.asarray(got)[bad[:5]].tolist()}, model {np.asarray(want)[bad[:5]].tolist()}")
+
+
+def both_calls(D, pairs, *where, garbage=False):
+    """every pair: the call on a fresh workspace (no hints: every tile searches) and again on it (hints now right) equal the model"""
+    ws = None
+    for alpha, beta in pairs:
+        ws = D.workspace(garbage=garbage)
+        for call in ("first", "second"):
+            same(D.axpby(ws, alpha, beta), D.P.want(alpha, beta), *where, (alpha, beta), call + " call")
+    return ws
+
+
+# ------------------------------------------------------------------------------------------------- a. every path, every shape
+
+uses(["parity:" + n for n in T.SHAPES], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("shape", sorted(T.SHAPES))
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(T.PATHS))
+def test_every_path_equals_the_model(M, shape, prec, path):
+    """All 17 dispatch paths of test_gpu_parity.PATHS: the alpha/beta call equals the model for every pair, first call and call on
+    hints; (1, 0) through the AXPBY kernels has the bits of the plain call (the two template halves agree).  Exact data make the
+    atomic fix-up order-independent, so it is held to the bits as well."""
+    P = problem("parity:" + shape, prec)
+    try:
+        M.set_tuning(P.vb, 0, 0, T.PATHS[path])
+        assert M.launch_info(P.csr.rows, P.csr.nnz, P.vb)["flags"] == T.PATHS[path]
+        D = OnDevice(M, P)
+        ws = both_calls(D, ALL_PAIRS, shape, prec, path)
+        same(D.plain(D.workspace()), P.want(1, 0), shape, prec, path, "plain call, fresh workspace")
+        plain = D.plain(ws)
+        same(plain, P.want(1, 0), shape, prec, path, "plain call on hints")
+        same(D.axpby(ws, 1, 0), plain, shape, prec, path, "(1, 0) through the AXPBY kernels against the plain call")
+    finally:
+        M.set_tuning(P.vb)
+
+
+uses(["parity:" + n for n in T.COMPACT_SHAPES], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("shape", sorted(T.COMPACT_SHAPES))
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("compact", [0, -1], ids=["compact_front_end", "general_kernel"])
+def test_compact_front_end_and_general_kernel_equal_the_model(M, shape, prec, compact):
+    """The default path of a small problem: behind the compact front end the first call (garbage hints) runs the general body and
+    the second the fast lane -- both under AXPBY --, with set_compact_tiles(-1) the general kernel alone."""
+    P = problem("parity:" + shape, prec)
+    try:
+        M.set_compact_tiles(compact)
+        D = OnDevice(M, P)
+        ws = both_calls(D, ALL_PAIRS, shape, prec, compact, garbage=True)
+        same(D.plain(ws), P.want(1, 0), shape, prec, compact, "plain call on hints")
+    finally:
+        M.set_compact_tiles(0)
+
+
+# --------------------------------------------------------------------------------------------------------- b. prepared calls
+
+PREPARED_SHAPES = ["power_law", "giant_plus_sprinkle", "leading_trailing_empty"]
+PREPARED_FLAGS = {"one_launch_small_shape": 0, "one_launch_large_shape": 16, "classic_small_shape": TWO_LAUNCH, "classic_three_launch": TWO_LAUNCH | 16}
+uses(["parity:" + n for n in PREPARED_SHAPES], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("shape", PREPARED_SHAPES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(PREPARED_FLAGS))
+def test_prepared_calls_equal_the_model(M, shape, prec, path):
+    """CsrMVWorkspace.prepare + mspmv_csrmv_prepared_*: (1, 0) takes the plain kernels, every other pair the AXPBY set"""
+    P = problem("parity:" + shape, prec)
+    try:
+        M.set_tuning(P.vb, 0, 0, PREPARED_FLAGS[path])
+        D = OnDevice(M, P)
+        ws = D.workspace(prepare=True)
+        assert ws.is_prepared_for(D.off, P.csr.rows, P.csr.nnz, D.tdt)          # (csrmv then calls the prepared entry point)
+        for alpha, beta in ALL_PAIRS:
+            for call in ("first", "second"):
+                same(D.axpby(ws, alpha, beta), P.want(alpha, beta), shape, prec, path, (alpha, beta), call + " prepared call")
+    finally:
+        M.set_tuning(P.vb)
+
+
+# -------------------------------------------------------------------------------------------- c. tile shapes and alignment
+
+TILE_PAIRS = [(-1.5, 0.5), (2, 0)]
+TILE_FLAGS = [0, 2, 4, 16, 18, 20, 24, 48, 80, 128, 144, 0xF000010, 0x3000010, 0x20000010, 0x10000010, 0x40000000, 0x40000010, 0x4F000010, 0x60000010]
+uses(["tile_grid:7", "tile_grid:11"], TILE_PAIRS)
+
+
+@pytest.mark.parametrize("vb,block,ipt", [(4, 256, 7), (4, 256, 11), (8, 256, 7), (8, 256, 11)])
+@pytest.mark.parametrize("flags", TILE_FLAGS)
+def test_every_compiled_tile_shape_equals_the_model(M, vb, block, ipt, flags):
+    """the (value bytes, block, items per thread) x flags grid of test_gpu_parity.test_every_compiled_tile_shape"""
+    P = problem(f"tile_grid:{ipt}", "f32" if vb == 4 else "f64")
+    try:
+        M.set_tuning(vb, block, ipt, flags)
+        info = M.launch_info(P.csr.rows, P.csr.nnz, vb)
+        assert (info["block_threads"], info["items_per_thread"], info["flags"]) == (block, ipt, flags)
+        both_calls(OnDevice(M, P), TILE_PAIRS, vb, block, ipt, hex(flags))
+    finally:
+        M.set_tuning(vb)
+
+
+UNALIGNED_PAIRS = [(-1.5, 0.5), (2, 0), (0, -2)]
+uses(["parity:power_law", "parity:one_giant_row"], UNALIGNED_PAIRS)
+
+
+@pytest.mark.parametrize("shape", ["power_law", "one_giant_row"])
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("flags", [0, 16, TWO_LAUNCH | 16])
+def test_unaligned_arrays_equal_the_model(M, shape, prec, flags, capfd):
+    """every array one element off a 16-byte boundary: the dword-per-lane tile_kernel is reached by alignment, not by a flag"""
+    P = problem("parity:" + shape, prec)
+    try:
+        M.set_tuning(P.vb, 0, 0, flags)
+        D = OnDevice(M, P, shift=True)
+        assert all(t.data_ptr() % 16 for t in (D.val, D.off, D.col, D.x))
+        capfd.readouterr()
+        same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, flags, "logged call")
+        log = capfd.readouterr().out
+        assert "tile_kernel<<<" in log and "tile_kernel_vec" not in log and "tile_kernel_snap" not in log, log
+        both_calls(D, UNALIGNED_PAIRS, shape, prec, flags, "unaligned")
+    finally:
+        M.set_tuning(P.vb)
+
+
+# ------------------------------------------------------- d. fix-up of more than one level, many carries into one row
+
+DEEP_PAIRS = [(-1.5, 0.5), (2, 0), (0, -2)]
+DEEP_PATHS = {"multilevel_fix": 0x90, "classic_multilevel_fix": TWO_LAUNCH | 0x90, "onepass_fix": TWO_LAUNCH | 16, "atomic_fix": 0x12,
+              "one_launch_records_taken": 16, "one_launch_records_recomputed": 16}
+for _p in PRECS:
+    uses([f"deep_one_row:{_p}", f"deep_long_rows:{_p}"], DEEP_PAIRS, [_p])
+
+
+@pytest.mark.parametrize("matrix", ["deep_one_row", "deep_long_rows"])
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(DEEP_PATHS))
+def test_deep_fixup_and_many_carries_per_row_equal_the_model(M, matrix, prec, path):
+    """More than FIX_CHUNK = 512 tiles, so the multi-level fix-up runs a second level (alpha must be applied once, not per level) and
+    the one-pass fix-up's blocks look back across chunks; every tile carries into one key, or a few tiles into each.  The
+    one-launch kernel adds the carries itself: taken from the published records, or (set_record_polls(-1)) recomputed."""
+    P = problem(f"{matrix}:{prec}", prec)
+    try:
+        M.set_tuning(P.vb, 0, 0, DEEP_PATHS[path])
+        if path == "one_launch_records_recomputed":
+            M.set_record_polls(-1)
+        info = M.launch_info(P.csr.rows, P.csr.nnz, P.vb)
+        assert info["num_tiles"] > info["fixup_chunk"]
+        if "multilevel" in path:
+            assert info["fixup_levels"] >= 2, info
+            # the smallest such size: one chunk of tiles fewer needs a single level
+            assert M.launch_info(P.csr.rows, P.csr.nnz - info["tile_items"] * 8, P.vb)["fixup_levels"] == 1
+        elif path.startswith("one_launch"):
+            assert info["fixup_levels"] == 0 and info["snap_head_max"] > 0
+        else:
+            assert info["fixup_levels"] == 1
+        D = OnDevice(M, P)
+        both_calls(D, DEEP_PAIRS, matrix, prec, path)
+        if path == "one_launch_records_recomputed":
+            # the episode counter of the workspace (launch_info: diag_offset) moves when a tile computed a sum itself instead of taking
+            # the record, and only then: tests/test_forward_progress.py
+            ws = D.workspace(); ws.buffer.zero_()
+            episodes = lambda: int(ws.buffer[info["diag_offset"] + 4: info["diag_offset"] + 8].view(torch.int32).item())
+            before = episodes()
+            for alpha, beta in DEEP_PAIRS:
+                same(D.axpby(ws, alpha, beta), P.want(alpha, beta), matrix, prec, path, (alpha, beta), "counted call")
+            assert episodes() != before, "no tile recomputed a partial sum: the form this case is about did not run"
+    finally:
+        M.set_tuning(P.vb); M.set_record_polls(0)
+
+
+# ---------------------------------------------------------------- e. column-band passes and the clocked form
+
+BAND_SHAPES = ["giant_row", "mostly_empty", "ragged_tail"]
+uses(["tdm:" + n for n in BAND_SHAPES], ALL_PAIRS)
+
+
+def _only_tile_kernel_vec(log):
+    names = [line.split("<<<")[0].replace("mspmv: ", "") for line in log.splitlines() if line.startswith("mspmv: ")]
+    return "tile_kernel_vec" in names and "tile_kernel_snap" not in names and "tile_kernel" not in names
+
+
+@pytest.mark.parametrize("shape", BAND_SHAPES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("passes", [2, 3, 8])
+def test_forced_band_passes_equal_the_model(M, shape, prec, passes, capfd):
+    """run_band_passes: pass 0 applies the caller's beta, every later pass adds with beta = 1 (p.beta = b == 0 ? s_beta0 : 1)"""
+    P = problem("tdm:" + shape, prec)
+    c = P.csr
+    try:
+        M.set_tuning(P.vb, 256, 11, NO_FUSED); M.set_tdm(P.vb, -1); M.set_band_passes(P.vb, passes)       # test_band_passes.forced_shape
+        assert M.band_passes(c.rows, c.cols, c.nnz, P.vb) == passes and M.clocked_bands(c.rows, c.cols, c.nnz, P.vb) == (0, 0)
+        D = OnDevice(M, P)
+        capfd.readouterr()
+        same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, passes, "logged call")
+        assert _only_tile_kernel_vec(capfd.readouterr().out)
+        both_calls(D, ALL_PAIRS, shape, prec, passes, "band passes")
+    finally:
+        TDM._reset()
+
+
+@pytest.mark.parametrize("shape", BAND_SHAPES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("clock", [(0, 0, 0), (1, 1, 13)], ids=["default_clock", "fast_clock_narrow_bands"])
+def test_clocked_bands_equal_the_model(M, shape, prec, clock, capfd):
+    """the clock-scheduled form (csrc/mspmv_tdm.hpp) with alpha and beta, against an oracle"""
+    P = problem("tdm:" + shape, prec)
+    c = P.csr
+    try:
+        TDM._clocked(P.vb, 11, *clock)
+        assert M.band_passes(c.rows, c.cols, c.nnz, P.vb) == 3
+        bands, band_cols = M.clocked_bands(c.rows, c.cols, c.nnz, P.vb)
+        assert bands >= 1 and band_cols >= 1, "not a candidate for the clocked form: nothing here would test it"
+        if clock[2]:
+            assert band_cols == 1 << clock[2]
+        D = OnDevice(M, P)
+        capfd.readouterr()
+        same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, clock, "logged call")
+        assert _only_tile_kernel_vec(capfd.readouterr().out)
+        both_calls(D, ALL_PAIRS, shape, prec, clock, "clocked bands")
+    finally:
+        TDM._reset()
+
+
+# -------------------------------------------------------------------------- f. what y may and may not be read for
+
+def _forced_passes_3(Mod, vb):
+    Mod.set_tuning(vb, 256, 11, NO_FUSED); Mod.set_tdm(vb, -1); Mod.set_band_passes(vb, 3)
+
+
+Y_PATHS = {name: (lambda Mod, vb, f=T.PATHS[name]: Mod.set_tuning(vb, 0, 0, f))
+           for name in ("one_launch_small_shape", "one_launch_large_shape", "classic_three_launch", "classic_atomic_fix", "classic_multilevel_fix", "reference_walk")}
+Y_PATHS["forced_passes_3"] = _forced_passes_3
+
+BETA0_PAIRS = [(1, 0), (2, 0), NEG_ALPHA_ZERO_BETA]
+# rows without entries in every position: inside tiles of short rows, as whole tile ranges, around a giant row, and nnz == 0
+BETA0_SHAPES = ["power_law", "all_empty", "leading_trailing_empty", "giant_row_between_empties", "giant_plus_sprinkle"]
+uses(["parity:" + n for n in BETA0_SHAPES], BETA0_PAIRS)
+
+
+def poisoned(n, dtype):
+    """NaN, +Inf, -Inf, -0.0, 1e38, repeating: whatever reads it shows in the result"""
+    return np.resize(np.array([np.nan, np.inf, -np.inf, -0.0, 1e38], dtype), n)
+
+
+@pytest.mark.parametrize("shape", BETA0_SHAPES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(Y_PATHS))
+def test_beta_zero_never_reads_y(M, shape, prec, path):
+    """beta == 0: y is written, not read -- rows without entries, a matrix without nonzeros and the carries' rows included -- and a
+    row without entries is +0.0 whatever the sign of alpha"""
+    P = problem("parity:" + shape, prec)
+    try:
+        Y_PATHS[path](M, P.vb)
+        D = OnDevice(M, P)
+        for alpha, beta in BETA0_PAIRS:
+            ws = D.workspace()
+            for call in ("first", "second"):
+                same(D.axpby(ws, alpha, beta, y0=poisoned(P.csr.rows, P.dtype)), P.want(alpha, beta), shape, prec, path, (alpha, beta), call + " call")
+    finally:
+        TDM._reset()
+
+
+PLANTED_PAIRS = [p for p in PAIRS if p[1] != 0]
+uses([f"planted:{t}" for t in PLANTED_TILES], PLANTED_PAIRS)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(Y_PATHS))
+def test_beta_nonzero_reads_exactly_its_own_row_of_y(M, prec, path):
+    """beta != 0: NaN / +Inf / -Inf planted in y0 at an empty row, the rows around a giant row and the giant row, the first and last
+    row and a row that ends exactly on a tile boundary come out non-finite at exactly those rows -- NaN as NaN, an infinity as
+    beta * itself --; every other row equals the model on the bits"""
+    vb = DT[prec][1]
+    try:
+        Y_PATHS[path](M, vb)
+        tile_items = M.launch_info(12000, 70000, vb)["tile_items"]
+        assert tile_items in PLANTED_TILES, tile_items
+        P = problem(f"planted:{tile_items}", prec)
+        assert M.launch_info(P.csr.rows, P.csr.nnz, vb)["tile_items"] == tile_items
+        rows = planted_rows(P.csr, tile_items)
+        y0 = P.y0.copy()
+        for k, r in enumerate(sorted(rows.values())):
+            y0[r] = (np.nan, np.inf, -np.inf)[k % 3]
+        at = np.zeros(P.csr.rows, bool); at[list(rows.values())] = True
+        D = OnDevice(M, P)
+        for alpha, beta in PLANTED_PAIRS:
+            ws = D.workspace()
+            for call in ("first", "second"):
+                y = D.axpby(ws, alpha, beta, y0=y0)
+                assert np.array_equal(~np.isfinite(y), at), (prec, path, (alpha, beta), call, np.flatnonzero(~np.isfinite(y) != at)[:8].tolist(), rows)
+                assert np.array_equal(np.isnan(y), np.isnan(y0))
+                inf = np.isinf(y0)
+                same(y[inf], (P.dtype(beta) * y0[inf]).astype(P.dtype), prec, path, (alpha, beta), call, "planted infinities")
+                same(y[~at], P.want(alpha, beta)[~at], prec, path, (alpha, beta), call + " call, rows nothing was planted at")
+    finally:
+        TDM._reset()
+
+
+# ------------------------------------------------------------------------------------------------------------- g. tiny x
+
+TINY_PAIRS = [(-1.5, 0.5), (2, 0)]
+uses([f"tiny_x:{c}:{r}" for c in TINY_COLS for r, _ in TINY_ROWS], TINY_PAIRS)
+
+
+@pytest.mark.parametrize("cols", TINY_COLS)
+@pytest.mark.parametrize("prec", PRECS)
+def test_tiny_x_equals_the_model(M, cols, prec):
+    """x of at most 4 KB is gathered from an LDS copy (and from memory with MSPMV_TUNE_NO_XLDS = 0x80000, or behind the compact front
+    end): cols at the copy's edges, small- and large-problem kernel, as in test_gpu_parity.test_tiny_x_is_gathered_from_lds"""
+    vb = DT[prec][1]
+    for rows, _ in TINY_ROWS:
+        P = problem(f"tiny_x:{cols}:{rows}", prec)
+        D = OnDevice(M, P)
+        for flags in ("compact", 0, 0x80000, 16, 16 | 0x80000):
+            try:
+                M.set_compact_tiles(0 if flags == "compact" else -1)
+                M.set_tuning(vb, 0, 0, 0 if flags == "compact" else flags)
+                both_calls(D, TINY_PAIRS, cols, rows, prec, flags)
+            finally:
+                M.set_tuning(vb); M.set_compact_tiles(0)

@@ -108,6 +108,16 @@ def test_clocked_bands_are_bitwise_the_classic_one_sweep(shape, prec, ipt):
         g, s = O.spmv_gold_acc64(csr, x)
         ok, worst = O.strict_check(csr, ref.cpu().numpy(), g, s, items_per_thread=M.serial_sum_depth(csr.rows, csr.cols, csr.nnz, vb))
         assert ok, worst
+        # ... and so is the alpha / beta reference everything below is compared with: the strict bound on alpha * g + beta * y0 with
+        # the scale |alpha| s + |beta y0| (the sum's error times |alpha|, one rounding for alpha * sum, one for the final add -- inside
+        # the bound's constant of 8; beta = 0.5 multiplies exactly); a row without entries is beta * y0 on the bits
+        got_ab = ref_ab.cpu().numpy()
+        rlen = np.diff(csr.row_offsets.astype(np.int64))
+        y0w = y0.astype(np.float64)
+        bound = 2.0 * (np.ceil(np.log2(rlen + 1.0)) + M.serial_sum_depth(csr.rows, csr.cols, csr.nnz, vb) + 8) * (np.finfo(dtype).eps / 2) * (1.5 * s + 0.5 * np.abs(y0w))
+        err = np.abs(got_ab.astype(np.float64) - (-1.5 * g + 0.5 * y0w))
+        assert np.all(err[rlen > 0] <= bound[rlen > 0]), float((err[rlen > 0] / bound[rlen > 0]).max())
+        assert np.array_equal(got_ab[rlen == 0], (dtype(0.5) * y0)[rlen == 0])
         for slot, look, shift in CLOCKS:
             _clocked(vb, ipt, slot, look, shift)
             taken = M.band_passes(rows, cols, csr.nnz, vb) == 3           # (fewer than 3 columns, 4 nonzeros, 3 rows: the ordinary path)
