@@ -693,6 +693,16 @@ int mspmv_mg_apply_carries(void *d_y_local, const void *d_carries,
  * mspmv_mg_allgather_rows (square matrices): x <- y on every replica -- PEER: each part
  * pushes its owned rows into every replica (direct peer writes, unpadded); RCCL: grouped ncclBroadcast.
  * Results are deterministic (carries are added in part order) and within the CsrMV tolerance.
+ * ON THE BITS: y of a plan = the prepared single-GPU call per part + the fold in part order.  That is: every part's local y
+ * (owned rows, then the open row) is what mspmv_csrmv_prepared_f32 / _f64 (alpha 1, beta 0, default tuning) returns on the
+ * part's own arrays -- values, local row offsets, column indices as attached, the replica of x, num_cols = cols -- with their
+ * alignment (arrays that are not 16-byte aligned run the dword-per-lane classic launches on the coordinates found when the part
+ * was attached); then a part that owns at least one row replaces its first entry by (((y[0] + c_s1) + c_s2) + ...), one add in
+ * the value type per source, over the earlier parts s1 < s2 < ... whose open row is that row (row_split[s+1] == row_split[id]),
+ * c_s being part s's open-row entry.  Parts that own no row take nothing; their open-row entry is their share of the row and
+ * stays in mspmv_mg_plan_y.  The same two exceptions as for the hot-column and mixed calls: a part never takes the small tile
+ * shape of a large fp64 matrix of short rows over a tiny x (mspmv_get_launch_info_cols), and with a hot-column plan never the
+ * column-band passes (tests/test_mg_exact.py holds every backend that one device can run to this).
  * Returns 0 or a hipError_t; hipErrorNotSupported = librccl could not be loaded, hipErrorUnknown = an
  * RCCL call failed (message on stderr). ---- */
 typedef struct mspmv_mg_plan mspmv_mg_plan_t;

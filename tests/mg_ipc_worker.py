@@ -2,7 +2,9 @@
 every rank drives ONE part of the same matrix on cuda:0 through the C operator's IPC backend -- carries written into the
 owner's mailbox through hipIpc-opened memory, step tags instead of collectives -- for several steps with the SAME x (the
 producer may run ahead: exercises the two-slot credit), then iterated SpMV with the row all-gather.  Rank 0 checks every
-row against the oracle and prints IPC-OK."""
+row against the oracle and prints IPC-OK.  Kind `exact`: integer data (tests/axpby_model.py), a giant row spanning every rank plus
+ordinary rows (4 ranks: the two middle ones own nothing); rank 0 also compares the gathered y of the repeated steps with the int64
+model ON THE BITS."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -23,6 +25,8 @@ if kind == "giant":                                     # one row spanning every
     lens = rng.integers(0, 4, rows); lens[rows // 2] = 900000
 elif kind == "short":
     lens = rng.integers(0, 12, rows)
+elif kind == "exact":                                   # longest row 200 000: sum |v x| <= 1.2e6 < 2^24, exact in fp32 too
+    lens = rng.integers(0, 4, rows); lens[rows // 2] = 200000
 else:                                                   # empty parts in the middle of a giant row + ordinary rows
     lens = np.zeros(rows, np.int64); lens[10] = 700000; lens[rows - 5:] = 7
 off = np.zeros(rows + 1, np.int64); np.cumsum(lens, out=off[1:])
@@ -30,8 +34,18 @@ nnz = int(off[-1])
 col = rng.integers(0, rows, nnz).astype(np.int32)
 val = (rng.uniform(-1, 1, nnz) * 0.05).astype(dtype)
 x0 = rng.uniform(-1, 1, rows).astype(dtype)
+exact = None
+if kind == "exact":
+    import axpby_model as AM                            # (tests/ is this script's directory: first on sys.path)
+    ic, x0, _ = AM.integer_problem(rng, rows, rows, lens, dtype)
+    col, val = ic.column_indices, ic.values
+    exact = AM.model(ic, x0, None, 1, 0)                # asserts the exactness bound
 csr = O.Csr(rows, rows, off.astype(np.int32), col, val)
 row_split, nz_split = MG.partition(off, world)
+if kind == "exact":
+    owned = np.diff(row_split)
+    assert world < 4 or (owned[1:-1] == 0).all(), owned    # the middle ranks sit inside the giant row
+    assert owned[0] > 0 and owned[-1] > 0
 plan = MG.MgPlan(row_split, nz_split, rows, tdt, [rank], [0], exchange=MG.EXCHANGE_IPC)
 lo = MG.local_offsets(off, row_split[rank], row_split[rank + 1], nz_split[rank], nz_split[rank + 1])
 a, b = int(nz_split[rank]), int(nz_split[rank + 1])
@@ -60,6 +74,8 @@ for step in range(6):                                   # same x: nothing but th
         assert ok, (kind, prec, step, worst)
         first = y if first is None else first
         assert np.array_equal(y, first)                 # bitwise repeatable
+        if exact is not None and rank == 0:
+            assert y.dtype == exact.dtype and np.array_equal(AM.bits(y), AM.bits(exact)), (kind, prec, step, int((AM.bits(y) != AM.bits(exact)).sum()))
 plan.synchronize()
 # iterated SpMV: x <- y through the peers' opened replicas
 xh = x0.copy()
