@@ -85,12 +85,23 @@ int mspmv_csrmv_f64(void *d_temp, size_t *temp_bytes, const double *d_values,
  *     row, and every other tile's share -- its carry -- arrives as  y[r] = y[r] + alpha * carry  (fix-up kernels), or is added
  *     into s before the formula is applied (the one-launch kernel).  alpha meets every product exactly once and beta * y[r]
  *     enters exactly once; a column-band pass after the first adds its share with beta = 1;
- *   * a row without entries gets alpha * (+0.0) + ..., so with beta == 0 it is +0.0 WHATEVER THE SIGN OF alpha: alpha * 0 alone would
- *     be -0.0 for alpha < 0, and the "+ 0" of the formula is what turns it into +0.0.  With beta != 0 it is beta * y[r] exactly
- *     (-0.0 only where that product is -0.0 and alpha * 0 is too).
- * So on inputs without zeros a zero in y is either the empty sum or an exact cancellation, and both are +0.0; (alpha, beta) =
- * (1, 0) gives the bits of mspmv_csrmv_*.  Where every intermediate is exactly representable the result does not depend on the
- * path, the tile shape or the order of the carries (the atomic fix-up included). ---- */
+ *   * THE SIGN OF A ZERO.  A row's sum s, and every partial sum that becomes a carry, STARTS FROM +0.0 (the reference's sequential
+ *     definition: partial = 0.0; partial += v * x).  A sum of IEEE numbers that starts from +0.0 is never -0.0, so s and every
+ *     carry are never -0.0, whatever the products are -- stored zeros and zeros in x of either sign are ordinary inputs.  With
+ *     t = (beta == 0 ? +0.0 : beta * y[r]) the row is y[r] = alpha * s_end + t, and every carry c arrives as y[r] + alpha * c or is
+ *     added into s first.  Hence, where every intermediate is exactly representable:
+ *       - with beta == 0, or whenever t is not -0.0, a zero result is +0.0 -- for mspmv_csrmv_* too, WHATEVER THE SIGN OF alpha,
+ *         the path, the tile shape, the band form or the order of the carries: alpha * 0 alone would be -0.0 for alpha < 0, and the
+ *         "+ 0" of the formula is what turns it into +0.0;
+ *       - where t is -0.0 and every product of the row is zero (or the row has no entries), the result is alpha * (+0.0) + (-0.0):
+ *         -0.0 if alpha is negative, +0.0 otherwise;
+ *       - where t is -0.0 and the row has non-zero products that cancel to zero, the sign depends on where tiles cut the row
+ *         ((+x) + (-x) is +0.0, but alpha * c of a zero carry is -0.0 for alpha < 0): that one corner is UNDEFINED.
+ * (alpha, beta) = (1, 0) gives the bits of mspmv_csrmv_*.  Where every intermediate is exactly representable -- subnormal products,
+ * sums and carries included: nothing is flushed to zero -- the result does not depend on the path, the tile shape or the order of
+ * the carries (the atomic fix-up included).  mspmv_csrmm_*, the mixed calls, the prepared calls, the plans (mspmv_csrmv_plan_*,
+ * mspmv_csrmv_hotcols_*), the transposed call and mspmv_coomv_* follow this definition; tests/test_axpby_exact.py,
+ * test_spmm_forms.py, test_plan_exact.py and test_mixed_precision.py pin it on the bits. ---- */
 int mspmv_csrmv_axpby_f32(void *d_temp, size_t *temp_bytes, const float *d_values,
                           const int32_t *d_row_offsets, const int32_t *d_column_indices,
                           const float *d_x, float *d_y, int32_t rows, int32_t cols,
@@ -113,7 +124,10 @@ int mspmv_csrmv_axpby_f64(void *d_temp, size_t *temp_bytes, const double *d_valu
  * nonzero share of a tile walked by four or eight lanes holding 16 bytes of right-hand sides each, rows written from registers);
  * ONE right-hand side stored as a plain vector (k = ldx = ldy = 1) is the CsrMV call.  Same two-phase temp storage, ownership, stream and error
  * conventions as mspmv_csrmv_*; with beta == 0 the old Y is never read.  Results per column are
- * within the same tolerance as CsrMV and bitwise reproducible.  No reference counterpart (the
+ * within the same tolerance as CsrMV and bitwise reproducible.  THE SIGN OF A ZERO is that of mspmv_csrmv_axpby_* in every kernel
+ * form (row-wise, packs, slot form, fix-up): sums and carries start from +0.0 and Y = alpha * s + (beta == 0 ? +0.0 : beta * Y), so
+ * with beta == 0, or wherever beta * Y is not -0.0, a row without entries and a row whose products are zeros or cancel give +0.0,
+ * for a negative alpha too; the same corner is undefined (beta * Y = -0.0 over non-zero products that cancel).  No reference counterpart (the
  * reference ships CsrMV only). ---- */
 int mspmv_csrmm_f32(void *d_temp, size_t *temp_bytes, const float *d_values,
                     const int32_t *d_row_offsets, const int32_t *d_column_indices,

@@ -321,8 +321,10 @@ __global__ __launch_bounds__(BLOCK) void spmm_tile_kernel(MMParams<T> p, const C
             P sum = e > e0 ? lds_load_pack<P, NPT>(s_units, pshift + e - 1) : P((T) 0);
             T *dst = yg + (size_t) r * (unsigned) p.ldy;
             if (AXPBY) {
+                // alpha * sum + (beta == 0 ? +0 : beta * Y): the "+ 0" makes a zero sum +0.0 for a negative alpha too (include/mspmv.h)
                 sum = p.alpha * sum;
                 if (p.beta != (T) 0) sum += p.beta * load_pack<T, K>(dst, p.y_vec != 0);
+                else sum += P((T) 0);
             }
             store_pack<T, K>(dst, sum, p.y_vec != 0);
         }
@@ -442,7 +444,8 @@ __global__ __launch_bounds__(BLOCK) void spmm_lane_kernel(MMParams<T> p, const C
         T *__restrict__ yg = p.y + (size_t) g * SW + c + (size_t) c0.x * ldy;
         auto put = [&](int row, vecT sum) {
             T *dst = yg + (size_t) row * ldy;
-            if (AXPBY) { sum = p.alpha * sum; if (p.beta != (T) 0) sum += p.beta * ldv(dst, yv); }
+            // (the "+ 0" with beta == 0: a zero sum is +0.0 for a negative alpha too, as the pack kernel and CsrMV write it)
+            if (AXPBY) { sum = p.alpha * sum; if (p.beta != (T) 0) sum += p.beta * ldv(dst, yv); else sum += (T) 0; }
             stv(dst, sum, yv);
         };
         int r = r0;
@@ -512,7 +515,7 @@ __global__ __launch_bounds__(BLOCK) void spmm_lane_kernel(MMParams<T> p, const C
                 const int rr = idx / SW, cc = idx % SW;
                 if (s_end[rr] == (rr > 0 ? s_end[rr - 1] : 0)) {
                     T *dst = p.y + (size_t) g * SW + cc + (size_t) (c0.x + rr) * ldy;
-                    *dst = (AXPBY && p.beta != (T) 0) ? p.beta * *dst : (T) 0;
+                    *dst = (AXPBY && p.beta != (T) 0) ? p.alpha * (T) 0 + p.beta * *dst : (T) 0;      // (alpha * s + beta * Y with s = +0.0)
                 }
             }
         }

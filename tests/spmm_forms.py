@@ -306,6 +306,7 @@ class Case:
     beta: int = 0
     trim: int = 0            # nonzeros taken off the last row: nnz % 4 = 3 - trim
     pad: int = 0             # > 0: values and column indices start `pad` elements into their allocations (unaligned arrays)
+    zeros: bool = False      # the zero-laden data of tests/test_spmm_forms.py (same structure, same launches)
 
     def dims(self):
         s = structure(self.mat)
@@ -368,8 +369,25 @@ def _cases():
 
 
 CASES = _cases()
+
+
+def _zero_cases():
+    """the tiny, mid and big cases again on zero-laden data -- row-wise, every pack width, slot form, groups, fix-up --, and the slot
+    form with alpha < 0 and beta == 0, which no case of CASES has.  The huge cases run the same arithmetic with non-temporal loads
+    and keep their non-zero data."""
+    import dataclasses
+    out = [dataclasses.replace(c, name=c.name + "_zeros", zeros=True) for c in CASES if c.mat != "huge"]
+    for c in CASES:
+        if c.name.startswith("big_slots_axpby"):
+            out.append(dataclasses.replace(c, name=f"big_slots_negative_alpha_beta_0_{c.prec}_zeros", zeros=True, beta=0))
+    return out
+
+
+ZERO_CASES = _zero_cases()
 # NaN / Inf containment: one pack case and one slot case per precision
 CONTAINMENT = [c for c in CASES if c.name.startswith(("mid_packs_axpby", "big_slots_axpby"))]
+# the same four run scaled to both ends of the exponent range and with -0.0 in Y0
+SCALED = CONTAINMENT
 
 
 def coverage(cases):

@@ -1,15 +1,35 @@
 """y = alpha*A*x + beta*y on every CsrMV dispatch path, BIT FOR BIT against the int64 model of tests/axpby_model.py.
 
 Every CsrMV kernel is compiled twice (AXPBY = false / true), the fix-up kernels take alpha, the column-band passes rewrite beta per
-pass: a second copy of the hot path.  The inputs here are small non-zero integers and (alpha, beta) dyadic, sized so that every sum
+pass: a second copy of the hot path.  The inputs here are small integers and (alpha, beta) dyadic, sized so that every sum
 in every association is exact (axpby_model.model asserts it per row): y is then defined on the bits, whichever kernels compute it,
-and every comparison below is on the bit patterns -- no tolerance anywhere, -0.0 is not +0.0 (include/mspmv.h at
-mspmv_csrmv_axpby_*: a zero of a correct call on such data is an exact cancellation or the empty sum, +0.0).
+and every comparison below is on the bit patterns -- no tolerance anywhere, no row left out, -0.0 is not +0.0.
+
+Every problem comes in two draws: without a zero anywhere (a zero of y is then an exact cancellation or the empty sum, +0.0), and
+ZERO-LADEN (axpby_model.zero_problem: stored zeros and zeros in x of both signs, zeros in y0, rows whose products are all -0.0, all
+zeros, or cancel), where the sign of every zero result is what include/mspmv.h defines at mspmv_csrmv_axpby_*: sums and carries
+start from +0.0.  The zero-laden draw also runs SCALED to the two ends of the exponent range (axpby_model.scale_exponents): the
+granule at the smallest subnormal -- once with normal values and x, once with the stored values themselves subnormal -- and at
+2^(emax - mantissa bits); the scaled arrays are built on the host.  A flush to zero or a sum started from its first product in any
+one instantiation fails here.
+
+Sensitivity of the zero-laden tests, each a one-line change of csrc/mspmv_kernels.hpp tried against this file on one MI355X
+(counted over this file, test_mixed_precision.py and test_plan_exact.py; the unchanged library passes all of them):
+  * consume_tile_flags' `s[k] += lead ? carry_in : (V) 0` made conditional (`if (lead) s[k] += carry_in`): 362 of the zero-laden tests
+    of this file and of test_mixed_precision.py fail (every path test of the flags reduction, 68 tile shapes, the planted rows on all
+    6 paths that run it, band passes, clocked bands, prepared calls, the deep fix-ups, tiny x, the three other calls), and 2 of
+    test_plan_exact.py now that it masks no sign;
+  * the `+ 0` dropped from the beta == 0 write of consume_tile_rows (`beta == 0 ? alpha * acc : alpha * acc + beta * y`): 185
+    zero-laden tests fail -- and 176 of the draws without zeros, which reach it through their rows without entries;
+  * a lean row sum started from its first product (consume_tile_rows' `acc` entered as -0.0 where the row has entries, which is the
+    same arithmetic): 198 zero-laden tests fail (the compact front end and the general kernel on 64 of 68 shapes, 69 path tests,
+    32 tile shapes, the planted rows, prepared calls, tiny x, the deep fix-ups, the mixed calls) and 2 of test_plan_exact.py.
 
 Forms are forced with the development setters (include/mspmv_dev.h) the way tests/test_gpu_parity.py, test_band_passes.py and
 test_tdm.py force them, and every form a test claims is asserted to have run (launch_info, band_passes, clocked_bands, the launch
 log).  PROBLEMS / USED list every (matrix, pair) of this file: tests/test_axpby_model.py checks the exactness bound on each of them
-on the CPU, so an edited shape cannot silently turn an exact test into a rounding-dependent one.
+on the CPU, so an edited shape cannot silently turn an exact test into a rounding-dependent one; ZUSED lists the zero-laden ones, for
+which it also checks the census of planted rows and the domain of the sign rule.
 """
 import functools
 
@@ -83,6 +103,29 @@ def _planted(tile_items):
     return make
 
 
+def kind_ii_lengths(tile_items):
+    """the lengths of the kind-(ii) rows planted for a tile of 256 x IPT items (NPT = the products a thread stages): inside one
+    thread, across two threads of a wave, across waves, across tiles"""
+    npt = (tile_items // 256 // 4 + 1) * 4
+    return [1, 2, npt - 1, 2 * npt + 1, 64 * npt + 3, tile_items + 5]
+
+
+PLANTED_ZERO_ROWS = [6100 + 37 * j for j in range(18)]      # (behind the giant row: the row made to end on a tile boundary stays)
+
+
+def _planted_zero(tile_items):
+    """_planted with rows whose products are all -0.0 (kind (ii)) of every length of kind_ii_lengths, three of each"""
+    base = _planted(tile_items)
+
+    def make(rng):
+        rows, cols, lens = base(rng)
+        want = kind_ii_lengths(tile_items)
+        for j, r in enumerate(PLANTED_ZERO_ROWS):
+            lens[r] = want[j % len(want)]
+        return rows, cols, lens, {r: A.KIND_II for r in PLANTED_ZERO_ROWS}
+    return make
+
+
 def planted_rows(csr, tile_items):
     """label -> row of the rows item f plants a non-finite y0 at"""
     off = csr.row_offsets.astype(np.int64)
@@ -116,6 +159,7 @@ for _n in ("giant_row", "mostly_empty", "ragged_tail"):
     PROBLEMS["tdm:" + _n] = (TDM.SHAPES[_n], len(_n) * 7, 2, 3)
 for _t in PLANTED_TILES:
     PROBLEMS[f"planted:{_t}"] = (_planted(_t), 43, 2, 3)
+    PROBLEMS[f"planted_zero:{_t}"] = (_planted_zero(_t), 44, 2, 3)
 for _c in TINY_COLS:
     for _r, _h in TINY_ROWS:
         PROBLEMS[f"tiny_x:{_c}:{_r}"] = (_tiny_x(_c, _r, _h), _c, 2, 3)
@@ -131,28 +175,58 @@ def uses(labels, pairs, precs=PRECS):
             USED.setdefault((label, prec), set()).update(pairs)
 
 
+# the zero-laden draw and its scalings (axpby_model.scale_exponents)
+ZEROS, SCALED = "zeros", ["zeros@bottom", "zeros@bottom_stored", "zeros@top"]
+# label, precision, data -> the pairs the zero-laden tests run (tests/test_axpby_model.py: census, domain, bound)
+ZUSED = {}
+# what the census of a problem must count besides what every shape must hold (label prefix -> keys; {tile}: the label's tile size)
+CENSUS_MUST = {"planted_zero:": ["kind_ii_crosses:{tile}"], "deep_long_rows:": ["kind_iii_crosses:1792", "kind_iii_crosses:2816"],
+               "deep_one_row:": ["kind_ii_crosses:1792", "kind_ii_crosses:2816"]}
+
+
+def zuses(labels, pairs, precs=PRECS, data=(ZEROS,)):
+    for label in labels:
+        assert label in PROBLEMS, label
+        for prec in precs:
+            for d in data:
+                ZUSED.setdefault((label, prec, d), set()).update(pairs)
+
+
 class Problem:
-    def __init__(self, label, prec):
+    def __init__(self, label, prec, data="nonzero"):
         make, seed, vmax, xmax = PROBLEMS[label]
         rng = np.random.default_rng(seed)
-        rows, cols, lens = make(rng)
-        self.label, self.prec = label, prec
+        shape = make(rng)
+        rows, cols, lens = shape[:3]
+        self.label, self.prec, self.data = label, prec, data
         self.dtype, self.vb = DT[prec]
-        self.csr, self.x, self.y0 = A.integer_problem(rng, rows, cols, np.asarray(lens, np.int64), self.dtype, vmax=vmax, xmax=xmax)
+        self.scale = 0
+        if data == "nonzero":
+            self.base = A.integer_problem(rng, rows, cols, np.asarray(lens, np.int64), self.dtype, vmax=vmax, xmax=xmax)
+            self.csr, self.x, self.y0 = self.base
+        else:
+            # base: the unscaled integers and zeros the model computes on; csr, x, y0: what the device gets
+            self.base = A.zero_problem(rng, rows, cols, np.asarray(lens, np.int64), self.dtype, vmax=vmax, xmax=xmax,
+                                       forced=shape[3] if len(shape) > 3 else None)
+            zeros, _, which = data.partition("@")
+            assert zeros == ZEROS
+            ev, ex = A.scale_exponents(self.dtype, which) if which else (0, 0)
+            self.csr, self.x, self.y0 = A.scaled(self.base, ev, ex)
+            self.scale = ev + ex
         self._want = {}
 
     def want(self, alpha, beta):
         """the model's y: computed once per pair, shared by every test on this problem, never written to"""
         if (alpha, beta) not in self._want:
-            w = A.model(self.csr, self.x, self.y0, alpha, beta)
+            w = A.model(*self.base, alpha, beta, scale=self.scale)
             w.setflags(write=False)
             self._want[(alpha, beta)] = w
         return self._want[(alpha, beta)]
 
 
 @functools.lru_cache(maxsize=None)
-def problem(label, prec):
-    return Problem(label, prec)
+def problem(label, prec, data="nonzero"):
+    return Problem(label, prec, data)
 
 
 # ------------------------------------------------------------------------------------------------------------------ on the GPU
@@ -206,6 +280,15 @@ def both_calls(D, pairs, *where, garbage=False):
         ws = D.workspace(garbage=garbage)
         for call in ("first", "second"):
             same(D.axpby(ws, alpha, beta), D.P.want(alpha, beta), *where, (alpha, beta), call + " call")
+    return ws
+
+
+def zero_calls(D, pairs, *where, garbage=False):
+    """both_calls, and the plain entry point (the AXPBY = false instantiations) on a fresh workspace and on the hints"""
+    P = D.P
+    ws = both_calls(D, pairs, *where, P.data, garbage=garbage)
+    same(D.plain(D.workspace(garbage=garbage)), P.want(1, 0), *where, P.data, "plain call, fresh workspace")
+    same(D.plain(ws), P.want(1, 0), *where, P.data, "plain call on hints")
     return ws
 
 
@@ -519,3 +602,259 @@ def test_tiny_x_equals_the_model(M, cols, prec):
                 both_calls(D, TINY_PAIRS, cols, rows, prec, flags)
             finally:
                 M.set_tuning(vb); M.set_compact_tiles(0)
+
+
+# ------------------------------------------------------------------------------------------------- z. the zero-laden draws
+# The tests above again on axpby_model.zero_problem's data (same shapes, same forced forms, the same assertions that the form
+# ran), plain and alpha / beta entry points, and -- every path, the deep fix-ups -- at both ends of the exponent range.
+
+zuses(["parity:" + n for n in T.SHAPES], ALL_PAIRS)
+zuses(["parity:" + n for n in T.SHAPES], A.SCALE_PAIRS, data=SCALED)
+
+
+@pytest.mark.parametrize("shape", sorted(T.SHAPES))
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(T.PATHS))
+def test_every_path_equals_the_model_on_zeros_and_at_both_ends_of_the_range(M, shape, prec, path):
+    """all 17 dispatch paths x shapes: the zero-laden draw with every pair, then scaled to subnormal products and sums (values and x
+    normal), to subnormal stored values, and to the top of the range, with the pairs (1, 0), (-1.5, 0.5), (3, -5)"""
+    try:
+        vb = DT[prec][1]
+        M.set_tuning(vb, 0, 0, T.PATHS[path])
+        for data in [ZEROS] + SCALED:
+            P = problem("parity:" + shape, prec, data)
+            assert M.launch_info(P.csr.rows, P.csr.nnz, P.vb)["flags"] == T.PATHS[path]
+            zero_calls(OnDevice(M, P), ALL_PAIRS if data == ZEROS else A.SCALE_PAIRS, shape, prec, path)
+    finally:
+        M.set_tuning(vb)
+
+
+zuses(["parity:" + n for n in T.COMPACT_SHAPES], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("shape", sorted(T.COMPACT_SHAPES))
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("compact", [0, -1], ids=["compact_front_end", "general_kernel"])
+def test_compact_front_end_and_general_kernel_equal_the_model_on_zeros(M, shape, prec, compact):
+    P = problem("parity:" + shape, prec, ZEROS)
+    try:
+        M.set_compact_tiles(compact)
+        zero_calls(OnDevice(M, P), ALL_PAIRS, shape, prec, compact, garbage=True)
+    finally:
+        M.set_compact_tiles(0)
+
+
+zuses(["parity:" + n for n in PREPARED_SHAPES], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("shape", PREPARED_SHAPES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(PREPARED_FLAGS))
+def test_prepared_calls_equal_the_model_on_zeros(M, shape, prec, path):
+    P = problem("parity:" + shape, prec, ZEROS)
+    try:
+        M.set_tuning(P.vb, 0, 0, PREPARED_FLAGS[path])
+        D = OnDevice(M, P)
+        ws = D.workspace(prepare=True)
+        assert ws.is_prepared_for(D.off, P.csr.rows, P.csr.nnz, D.tdt)
+        for alpha, beta in ALL_PAIRS:
+            for call in ("first", "second"):
+                same(D.axpby(ws, alpha, beta), P.want(alpha, beta), shape, prec, path, (alpha, beta), call + " prepared call")
+        same(D.plain(ws), P.want(1, 0), shape, prec, path, "plain prepared call")
+    finally:
+        M.set_tuning(P.vb)
+
+
+TILE_ZERO_PAIRS = TILE_PAIRS + [NEG_ALPHA_ZERO_BETA]
+zuses(["tile_grid:7", "tile_grid:11"], TILE_ZERO_PAIRS + [(1, 0)])
+
+
+@pytest.mark.parametrize("vb,block,ipt", [(4, 256, 7), (4, 256, 11), (8, 256, 7), (8, 256, 11)])
+@pytest.mark.parametrize("flags", TILE_FLAGS)
+def test_every_compiled_tile_shape_equals_the_model_on_zeros(M, vb, block, ipt, flags):
+    P = problem(f"tile_grid:{ipt}", "f32" if vb == 4 else "f64", ZEROS)
+    try:
+        M.set_tuning(vb, block, ipt, flags)
+        info = M.launch_info(P.csr.rows, P.csr.nnz, vb)
+        assert (info["block_threads"], info["items_per_thread"], info["flags"]) == (block, ipt, flags)
+        zero_calls(OnDevice(M, P), TILE_ZERO_PAIRS, vb, block, ipt, hex(flags))
+    finally:
+        M.set_tuning(vb)
+
+
+UNALIGNED_ZERO_PAIRS = UNALIGNED_PAIRS + [NEG_ALPHA_ZERO_BETA]
+zuses(["parity:power_law", "parity:one_giant_row"], UNALIGNED_ZERO_PAIRS + [(1, 0)])
+
+
+@pytest.mark.parametrize("shape", ["power_law", "one_giant_row"])
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("flags", [0, 16, TWO_LAUNCH | 16])
+def test_unaligned_arrays_equal_the_model_on_zeros(M, shape, prec, flags, capfd):
+    P = problem("parity:" + shape, prec, ZEROS)
+    try:
+        M.set_tuning(P.vb, 0, 0, flags)
+        D = OnDevice(M, P, shift=True)
+        assert all(t.data_ptr() % 16 for t in (D.val, D.off, D.col, D.x))
+        capfd.readouterr()
+        same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, flags, "logged call")
+        log = capfd.readouterr().out
+        assert "tile_kernel<<<" in log and "tile_kernel_vec" not in log and "tile_kernel_snap" not in log, log
+        zero_calls(D, UNALIGNED_ZERO_PAIRS, shape, prec, flags, "unaligned")
+    finally:
+        M.set_tuning(P.vb)
+
+
+# deep_one_row: the giant row is the longest row, which zero_problem makes of kind (ii) -- every carry, record and group record of
+# it is a zero; deep_long_rows: about a tenth of its rows are of kind (iii), cut by tiles (CENSUS_MUST)
+DEEP_ZERO_PAIRS = DEEP_PAIRS + [NEG_ALPHA_ZERO_BETA]
+DEEP_ZERO_PATHS = dict(DEEP_PATHS, one_launch_records_one_look=16)
+for _p in PRECS:
+    zuses([f"deep_one_row:{_p}", f"deep_long_rows:{_p}"], DEEP_ZERO_PAIRS + [(1, 0)], [_p])
+    zuses([f"deep_one_row:{_p}", f"deep_long_rows:{_p}"], A.SCALE_PAIRS, [_p], data=SCALED)
+
+
+@pytest.mark.parametrize("matrix", ["deep_one_row", "deep_long_rows"])
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(DEEP_ZERO_PATHS))
+def test_deep_fixup_and_many_carries_per_row_equal_the_model_on_zeros_and_at_both_ends_of_the_range(M, matrix, prec, path):
+    """the fix-up of more than one level, the one-pass and the atomic fix-up, the one-launch kernel's records taken, looked for once
+    (set_record_polls(1)) and recomputed (-1: recompute_row_head): zero carries of a kind-(ii) giant row, kind-(iii) rows cut by
+    tiles, subnormal carries and carries at the top of the range"""
+    try:
+        vb = DT[prec][1]
+        M.set_tuning(vb, 0, 0, DEEP_ZERO_PATHS[path])
+        M.set_record_polls({"one_launch_records_recomputed": -1, "one_launch_records_one_look": 1}.get(path, 0))
+        for data in [ZEROS] + SCALED:
+            P = problem(f"{matrix}:{prec}", prec, data)
+            info = M.launch_info(P.csr.rows, P.csr.nnz, P.vb)
+            assert info["num_tiles"] > info["fixup_chunk"]
+            if "multilevel" in path:
+                assert info["fixup_levels"] >= 2, info
+            elif path.startswith("one_launch"):
+                assert info["fixup_levels"] == 0 and info["snap_head_max"] > 0
+            else:
+                assert info["fixup_levels"] == 1
+            zero_calls(OnDevice(M, P), DEEP_ZERO_PAIRS if data == ZEROS else A.SCALE_PAIRS, matrix, prec, path)
+    finally:
+        M.set_tuning(vb); M.set_record_polls(0)
+
+
+zuses(["tdm:" + n for n in BAND_SHAPES], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("shape", BAND_SHAPES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("passes", [2, 3, 8])
+def test_forced_band_passes_equal_the_model_on_zeros(M, shape, prec, passes, capfd):
+    """a band without a non-zero product of a row adds +0.0 with beta = 1: nothing a later pass adds may turn the sign round"""
+    P = problem("tdm:" + shape, prec, ZEROS)
+    c = P.csr
+    try:
+        M.set_tuning(P.vb, 256, 11, NO_FUSED); M.set_tdm(P.vb, -1); M.set_band_passes(P.vb, passes)
+        assert M.band_passes(c.rows, c.cols, c.nnz, P.vb) == passes and M.clocked_bands(c.rows, c.cols, c.nnz, P.vb) == (0, 0)
+        D = OnDevice(M, P)
+        capfd.readouterr()
+        same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, passes, "logged call")
+        assert _only_tile_kernel_vec(capfd.readouterr().out)
+        zero_calls(D, ALL_PAIRS, shape, prec, passes, "band passes")
+    finally:
+        TDM._reset()
+
+
+@pytest.mark.parametrize("shape", BAND_SHAPES)
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("clock", [(0, 0, 0), (1, 1, 13)], ids=["default_clock", "fast_clock_narrow_bands"])
+def test_clocked_bands_equal_the_model_on_zeros(M, shape, prec, clock, capfd):
+    P = problem("tdm:" + shape, prec, ZEROS)
+    c = P.csr
+    try:
+        TDM._clocked(P.vb, 11, *clock)
+        assert M.band_passes(c.rows, c.cols, c.nnz, P.vb) == 3
+        bands, band_cols = M.clocked_bands(c.rows, c.cols, c.nnz, P.vb)
+        assert bands >= 1 and band_cols >= 1, "not a candidate for the clocked form: nothing here would test it"
+        D = OnDevice(M, P)
+        capfd.readouterr()
+        same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, clock, "logged call")
+        assert _only_tile_kernel_vec(capfd.readouterr().out)
+        zero_calls(D, ALL_PAIRS, shape, prec, clock, "clocked bands")
+    finally:
+        TDM._reset()
+
+
+zuses([f"planted_zero:{t}" for t in PLANTED_TILES], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("path", sorted(Y_PATHS))
+def test_planted_rows_of_negative_zero_products_equal_the_model(M, prec, path):
+    """rows whose products are all -0.0, of 1, 2, NPT - 1, 2 NPT + 1, 64 NPT + 3 and tile + 5 products: inside one thread, across two
+    threads of a wave, across waves, across tiles -- +0.0 (-0.0 only under t = -0.0 and a negative alpha), on every path"""
+    vb = DT[prec][1]
+    try:
+        Y_PATHS[path](M, vb)
+        for t in PLANTED_TILES:
+            P = problem(f"planted_zero:{t}", prec, ZEROS)
+            if M.launch_info(P.csr.rows, P.csr.nnz, vb)["tile_items"] == t:
+                break
+        else:
+            pytest.fail(f"{path}: runs neither tile size of {PLANTED_TILES}")
+        lens = np.diff(P.csr.row_offsets)[PLANTED_ZERO_ROWS]
+        assert sorted(set(lens.tolist())) == sorted(kind_ii_lengths(t))
+        zero_calls(OnDevice(M, P), ALL_PAIRS, prec, path, t)
+    finally:
+        TDM._reset()
+
+
+zuses([f"tiny_x:{c}:{r}" for c in TINY_COLS for r, _ in TINY_ROWS], TINY_PAIRS + [NEG_ALPHA_ZERO_BETA, (1, 0)])
+
+
+@pytest.mark.parametrize("cols", TINY_COLS)
+@pytest.mark.parametrize("prec", PRECS)
+def test_tiny_x_equals_the_model_on_zeros(M, cols, prec):
+    vb = DT[prec][1]
+    for rows, _ in TINY_ROWS:
+        P = problem(f"tiny_x:{cols}:{rows}", prec, ZEROS)
+        D = OnDevice(M, P)
+        for flags in ("compact", 0, 0x80000, 16, 16 | 0x80000):
+            try:
+                M.set_compact_tiles(0 if flags == "compact" else -1)
+                M.set_tuning(vb, 0, 0, 0 if flags == "compact" else flags)
+                zero_calls(D, TINY_PAIRS + [NEG_ALPHA_ZERO_BETA], cols, rows, prec, flags)
+            finally:
+                M.set_tuning(vb); M.set_compact_tiles(0)
+
+
+# ------------------------------------------------------------------------- the calls that are tested against the stateless call
+# The hot-column plan, the transposed call and coomv are compared with mspmv_csrmv_* elsewhere: an error they share with it passes
+# there.  One zero-laden problem each against the model.
+
+OTHER_CALLS = ["hot_column_plan", "transposed", "coomv"]
+zuses(["parity:power_law"], ALL_PAIRS)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("call", OTHER_CALLS)
+def test_hot_column_plan_transposed_call_and_coomv_equal_the_model_on_zeros(M, prec, call):
+    P = problem("parity:power_law", prec, ZEROS)
+    c = P.csr
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    xd = d(P.x)
+    if call == "hot_column_plan":
+        plan = M.CsrMVHotColumns(d(c.values), d(c.row_offsets), d(c.column_indices), c.cols)
+        run = lambda y, alpha, beta: plan(xd, y, alpha=float(alpha), beta=float(beta))
+    elif call == "transposed":
+        # A = B^T for the problem's matrix B (stable by row: A's rows hold their columns in ascending order), so that A^T x = B x
+        rowid = np.repeat(np.arange(c.rows, dtype=np.int32), np.diff(c.row_offsets))
+        order = np.argsort(c.column_indices, kind="stable")
+        off = np.zeros(c.cols + 1, np.int32); np.cumsum(np.bincount(c.column_indices, minlength=c.cols), out=off[1:])
+        av, ao, ac = d(c.values[order]), d(off), d(rowid[order])
+        run = lambda y, alpha, beta: M.csrmv(av, ao, ac, xd, y=y, num_cols=c.rows, alpha=float(alpha), beta=float(beta), transpose=True)
+    else:
+        rowid = np.repeat(np.arange(c.rows, dtype=np.int32), np.diff(c.row_offsets))
+        order = np.random.default_rng(7).permutation(c.nnz)          # unsorted triples (repeated columns of a row: duplicates, which add)
+        cv, cr, cc = d(c.values[order]), d(rowid[order]), d(c.column_indices[order])
+        run = lambda y, alpha, beta: M.coomv(cv, cr, cc, xd, y=y, num_rows=c.rows, num_cols=c.cols, alpha=float(alpha), beta=float(beta))
+    for alpha, beta in ALL_PAIRS:
+        y = run(d(P.y0.copy()), alpha, beta)
+        torch.cuda.synchronize()
+        same(y.cpu().numpy(), P.want(alpha, beta), call, prec, (alpha, beta))

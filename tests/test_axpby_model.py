@@ -106,10 +106,13 @@ def _gpu_file():
 
 def test_every_gpu_problem_and_pair_is_within_the_bound():
     E = _gpu_file()
-    assert set(label for label, _ in E.USED) == set(E.PROBLEMS), "a problem no test uses, or a test on an unlisted problem"
+    zero_only = {label for label in E.PROBLEMS if label.startswith("planted_zero:")}           # (shapes made for the zero-laden tests alone)
+    assert set(label for label, _ in E.USED) == set(E.PROBLEMS) - zero_only, "a problem no test uses, or a test on an unlisted problem"
+    assert zero_only <= set(label for label, _, _ in E.ZUSED) <= set(E.PROBLEMS)
     for (label, prec), pairs in sorted(E.USED.items()):
         P = E.problem(label, prec)
         limit = A.LIMIT[np.dtype(P.dtype)]
+        # (the draws without a zero; the zero-laden ones: test_every_zero_laden_gpu_problem_has_its_rows_and_is_in_the_domain)
         assert not (P.csr.values == 0).any() and not (P.x == 0).any() and not (P.y0 == 0).any()
         for alpha, beta in sorted(pairs):
             assert A.quotient(P.csr, P.x, P.y0, alpha, beta) < limit, (label, prec, alpha, beta)
@@ -129,3 +132,191 @@ def test_the_planted_problem_has_the_rows_the_gpu_test_plants_at():
         assert (r + 1 + off[r + 1]) % tile_items == 0 and off[r + 1] > off[r]
         assert len(set(rows.values())) == len(rows)
         assert not np.diff(off)[2000:5800].any() and 5800 - 2000 > tile_items
+
+
+# ------------------------------------------------------------------------------------------------ zeros and their signs
+
+def test_the_zero_sign_rule_by_hand():
+    # x = [+0, -0, 1, -1];  row 0: kind (ii) -2 * +0, -0 * 1;  row 1: kind (i);  row 2: 1 - 1 cancels;  row 3: empty;  row 4: 2 * 1
+    off = np.array([0, 2, 4, 6, 6, 7], np.int32)
+    col = np.array([0, 2, 2, 3, 2, 2, 2], np.int32)
+    for dtype in (np.float32, np.float64):
+        val = np.array([-2, -0.0, 0.0, -0.0, 1, -1, 2], dtype)
+        x = np.array([0.0, -0.0, 1, -1], dtype)
+        csr = A.Csr(5, 4, off, col, val)
+        c = A.census(csr, x, np.zeros(5, dtype), [(1, 1)], [4])
+        assert (c["kind_i"], c["kind_ii"], c["kind_iii"], c["empty"]) == (1, 1, 1, 1) and c["kind_i_mixed_signs"] == 1
+        y0 = np.array([-0.0, 0.0, 5, -0.0, -0.0], dtype)
+        neg, pos = A.bits(np.array([-0.0], dtype))[0], 0
+        two = A.bits(np.array([2], dtype))[0]
+        # beta == 0: every zero is +0.0, whatever the sign of alpha
+        for alpha in (1, -0.5, 2):
+            assert A.bits(A.model(csr, x, y0, alpha, 0)).tolist()[:4] == [pos] * 4
+        # t = 1 * -0.0 on rows 0 and 3: alpha * (+0.0) + (-0.0) is -0.0 for a negative alpha only; row 1: t = +0.0
+        assert A.bits(A.model(csr, x, y0, 1, 1)).tolist() == [pos, pos, A.bits(np.array([5], dtype))[0], pos, two]
+        assert A.bits(A.model(csr, x, y0, -0.5, 3)).tolist()[:2] == [neg, pos] and A.bits(A.model(csr, x, y0, -0.5, 3))[3] == neg
+        # a negative beta turns the signs round: now row 1 (y0 = +0.0) has t = -0.0
+        assert A.bits(A.model(csr, x, y0, -1.5, -1)).tolist()[:2] == [pos, neg]
+        assert A.bits(A.model(csr, x, y0, 0, -2)).tolist()[:2] == [pos, pos]           # alpha == 0: 0 * (+0.0) is +0.0
+        # the undefined corner is refused: t = -0.0 on the row whose non-zero products cancel
+        bad = y0.copy(); bad[2] = -0.0
+        with pytest.raises(AssertionError, match="outside the definition"):
+            A.model(csr, x, bad, 1, 1)
+        A.model(csr, x, bad, 1, -1)                                                     # (t = +0.0 there: defined, +0.0)
+        bad = y0.copy(); bad[4] = 0.0                                                   # alpha == 0 leaves a zero result under t = -0.0
+        with pytest.raises(AssertionError, match="outside the definition"):
+            A.model(csr, x, bad, 0, -2)
+
+
+def test_zero_problem_draws_what_it_says():
+    rng = np.random.default_rng(5)
+    lens = rng.integers(0, 9, 800); lens[11] = 5000; lens[12] = 301; lens[13] = 300
+    for dtype in (np.float32, np.float64):
+        csr, x, y0 = A.zero_problem(rng, 800, 50, lens, dtype, forced={20: A.KIND_II, 21: A.KIND_III})
+        assert np.array_equal(np.diff(csr.row_offsets), lens)
+        assert set(np.unique(np.abs(csr.values))) == {0, 1, 2} and set(np.unique(np.abs(x))) == {0, 1, 2, 3}
+        c = A.census(csr, x, y0, A.PAIRS, [256 * 7, 256 * 11])
+        for key in ("kind_i", "kind_ii", "kind_iii", "kind_i_mixed_signs", "kind_ii_crosses:1792", "kind_ii_crosses:2816", "zero_results_under_negative_zero_t",
+                    "values:+0", "values:-0", "x:+0", "x:-0", "y0:+0", "y0:-0"):
+            assert c[key] > 0, (key, c)
+        assert c["longest_kind_ii"] == 5000
+        off = csr.row_offsets
+        for r in range(800):
+            cc = csr.column_indices[off[r]:off[r + 1]]
+            assert np.all(np.diff(cc) >= 0) and np.all((cc >= 0) & (cc < 50))
+        prod = csr.values * x[csr.column_indices]
+        for r in (11, 20):                                       # kind (ii): every product -0.0
+            pr = prod[off[r]:off[r + 1]]
+            assert pr.size and np.all(pr == 0) and np.all(np.signbit(pr))
+        for r in (12, 21):                                       # kind (iii): non-zero products that cancel
+            pr = prod[off[r]:off[r + 1]]
+            assert pr.any() and pr.sum() == 0
+        assert not csr.values[off[13]:off[14]].any()             # kind (i)
+        for alpha, beta in A.PAIRS + [(-0.5, 0)]:
+            A.model(csr, x, y0, alpha, beta)                     # (the domain: no zero result under t = -0.0 with non-zero products)
+
+
+def _fma(a, b, c, dtype):
+    """a * b + c rounded once: exact in long double for the numbers of this model (alpha has a few bits, s at most 53)"""
+    L = np.longdouble
+    return dtype(L(a) * L(b) + L(c))
+
+
+def _piece_sum(rng, prods, dtype, first_product_start=False):
+    """one tile's share of a row in a random association: cut into runs, each summed left to right FROM +0.0 (a thread's running
+    sum, a lane's partial), the runs folded in a random order of adjacent pairs (the scans, the group folds)"""
+    n = len(prods)
+    cuts = sorted(set(rng.integers(1, n, rng.integers(0, 3)).tolist())) if n > 1 else []
+    runs = []
+    for a, b in zip([0] + cuts, cuts + [n]):
+        if first_product_start:
+            acc = prods[a]
+            for p in prods[a + 1:b]:
+                acc = dtype(acc + p)
+        else:
+            acc = dtype(0.0)
+            for p in prods[a:b]:
+                acc = dtype(acc + p)
+        runs.append(acc)
+    while len(runs) > 1:
+        i = int(rng.integers(0, len(runs) - 1))
+        runs[i:i + 2] = [dtype(runs[i] + runs[i + 1])]
+    return runs[0]
+
+
+def _any_path(rng, prods, y0, alpha, beta, dtype, first_product_start=False):
+    """y of one row as some path may compute it: tile cuts anywhere, the last piece's sum enters alpha * s + t (fused or not), every
+    other piece is a carry that is added into s first or arrives as y + alpha * c (fused or not), in a random order"""
+    alpha, beta = dtype(alpha), dtype(beta)
+    n = len(prods)
+    cuts = sorted(set(rng.integers(0, n + 1, rng.integers(0, 4)).tolist())) if n else []    # (a cut at 0 or n: an empty piece, as a
+    bounds = [0] + cuts + [n]                                                                #  tile that begins at the row's end)
+    pieces = [_piece_sum(rng, prods[a:b], dtype, first_product_start) if b > a else dtype(0.0) for a, b in zip(bounds[:-1], bounds[1:])]
+    s, carries = pieces[-1], pieces[:-1]
+    later = []
+    for k in rng.permutation(len(carries)):
+        if rng.integers(0, 2):
+            s = dtype(s + carries[k])
+        else:
+            later.append(carries[k])
+    t = dtype(0.0) if beta == 0 else dtype(beta * y0)
+    y = _fma(alpha, s, t, dtype) if rng.integers(0, 2) else dtype(dtype(alpha * s) + t)
+    for c in later:
+        y = _fma(alpha, c, y, dtype) if rng.integers(0, 2) else dtype(y + dtype(alpha * c))
+    return y
+
+
+@pytest.mark.parametrize("which", ["plain", "bottom", "bottom_stored", "top"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_the_definition_is_association_free(dtype, which):
+    """Rows of up to 6 products from {+-2, +-1, +-0} x {+-3 .. +-0}, planted kinds included, computed in the compute type with numpy
+    scalars under random tile cuts, random association inside each piece, carries folded into s or into y in random order, fused and
+    unfused: with every piece started from +0.0 the bits are model()'s on every row -- no mask is needed --, at the plain scale and
+    with the granule at the smallest subnormal and at 2^(emax - mantissa bits) (so numpy's own arithmetic is shown exact there).
+    Started from the first product instead, rows differ: the test can tell the two behaviours apart."""
+    assert np.finfo(np.longdouble).nmant >= 63
+    rng = np.random.default_rng(77)
+    rows = 1500
+    lens = rng.integers(0, 7, rows)
+    pairs = A.PAIRS + [(-0.5, 0)] if which == "plain" else A.SCALE_PAIRS
+    base = A.zero_problem(rng, rows, 12, lens, dtype)
+    ev, ex = (0, 0) if which == "plain" else A.scale_exponents(dtype, which, pairs)
+    csr, x, y0 = A.scaled(base, ev, ex)
+    off = csr.row_offsets
+    tiny = np.finfo(dtype).tiny
+    wrong_from_first = 0
+    with np.errstate(under="ignore"):
+        prod = [dtype(v * x[c]) for v, c in zip(csr.values, csr.column_indices)]
+        if which.startswith("bottom"):
+            assert all(abs(p) < 64 * tiny for p in prod) and any(0 < abs(p) < tiny for p in prod)
+        for alpha, beta in pairs:
+            want = A.model(*base, alpha, beta, scale=ev + ex)
+            if which == "top":
+                assert np.isfinite(want).all() and np.abs(want).max() >= 2.0 ** A.TOP[np.dtype(dtype)]
+            wb = A.bits(want)
+            for r in range(rows):
+                pr = prod[off[r]:off[r + 1]]
+                for _ in range(3):
+                    got = _any_path(rng, pr, y0[r], alpha, beta, dtype)
+                    assert A.bits(np.array([got], dtype))[0] == wb[r], (r, alpha, beta, got, want[r], pr, y0[r])
+                wrong_from_first += A.bits(np.array([_any_path(rng, pr, y0[r], alpha, beta, dtype, True)], dtype))[0] != wb[r]
+    assert wrong_from_first > 0
+
+
+def test_every_zero_laden_gpu_problem_has_its_rows_and_is_in_the_domain():
+    """every (matrix, data variant, pair) of the zero-laden GPU tests: the bound, the domain of the sign rule (model() asserts both), that
+    the scaled arrays are representable, and the census -- each kind of row present wherever the shape can hold it, a kind-(ii) row
+    across a tile boundary of every tile size wherever a row is longer than a tile, zero results under t = -0.0"""
+    E = _gpu_file()
+    assert E.ZUSED, "no zero-laden problem is registered"
+    seen = set()
+    for (label, prec, data), pairs in sorted(E.ZUSED.items()):
+        P = E.problem(label, prec, data)
+        for alpha, beta in sorted(pairs):
+            P.want(alpha, beta)
+        if (label, prec) in seen:
+            continue
+        seen.add((label, prec))
+        csr, x, y0 = P.base
+        c = A.census(csr, x, y0, sorted(pairs), E.PLANTED_TILES)
+        lens = np.diff(csr.row_offsets.astype(np.int64))
+        with_entries = int((lens > 0).sum())
+        if with_entries >= 1:
+            assert c["kind_ii"] > 0 and c["longest_kind_ii"] == c["longest"], (label, prec, c)
+        if with_entries >= 3:
+            assert c["kind_i"] > 0, (label, prec, c)
+        if int((lens >= 2).sum()) >= 2 and (x != 0).any():
+            assert c["kind_iii"] > 0, (label, prec, c)
+        for T in E.PLANTED_TILES:
+            if c["longest"] > T:
+                assert c[f"kind_ii_crosses:{T}"] > 0, (label, prec, T, c)
+        if csr.rows >= 1000 and any(b != 0 for _, b in pairs):
+            assert c["zero_results_under_negative_zero_t"] > 0, (label, prec, c)
+        if csr.nnz >= 1000:
+            assert c["values:+0"] > 0 and c["values:-0"] > 0, (label, prec, c)
+        if csr.cols >= 4:
+            assert c["x:+0"] > 0 and c["x:-0"] > 0, (label, prec, c)
+        for want_label, keys in E.CENSUS_MUST.items():
+            if label.startswith(want_label):
+                for key in keys:
+                    assert c[key.format(tile=label.split(":")[-1])] > 0, (label, prec, key, c)

@@ -33,7 +33,34 @@ def narrow(pair, a):
     return t, t.to(cdt).numpy()
 
 
+def narrow_exact(pair, a):
+    """narrow() for values the stored type holds exactly, made from the bit patterns on the host (no conversion routine that might
+    round or flush a subnormal, and -0.0 keeps its sign: bf16 -0.0 is 0x8000)"""
+    sdt, cdt, npdt, _, _ = PAIRS[pair]
+    a = np.ascontiguousarray(a, dtype=npdt)
+    if pair == "bf16_f32":
+        u = a.view(np.uint32)
+        assert not (u & 0xFFFF).any(), "not a bf16"
+        t = torch.from_numpy((u >> 16).astype(np.uint16).view(np.int16)).view(torch.bfloat16)
+    else:
+        n = a.astype(np.float32)
+        assert np.array_equal(n.astype(np.float64).view(np.int64), a.view(np.int64)), "not an fp32"
+        t = torch.from_numpy(n)
+    return t, a
+
+
 # ------------------------------------------------------------------------------------------------------------------ CPU
+
+def test_narrow_exact_keeps_signed_zeros_and_subnormals():
+    t, w = narrow_exact("bf16_f32", np.array([-0.0, 0.0, 2.0 ** -133, -2.0 ** -132, 1.0], np.float32))
+    assert t.view(torch.int16).tolist() == [-0x8000, 0, 1, -0x8000 + 2, 0x3F80] and t.dtype == torch.bfloat16
+    t, w = narrow_exact("f32_f64", np.array([-0.0, 0.0, 2.0 ** -149, -2.0 ** -148], np.float64))
+    assert t.view(torch.int32).tolist() == [-2 ** 31, 0, 1, -2 ** 31 + 2]
+    with pytest.raises(AssertionError):
+        narrow_exact("bf16_f32", np.array([1.0 + 2.0 ** -10], np.float32))
+    with pytest.raises(AssertionError):
+        narrow_exact("f32_f64", np.array([2.0 ** -150], np.float64))
+
 
 @pytest.mark.parametrize("kind", ["product", "dev"])
 def test_the_four_entry_points_are_exported_and_declared(kind):
@@ -121,10 +148,10 @@ def off_by_one(t):
 class Problem:
     """a CSR matrix whose values were drawn in the stored type (the widened matrix IS the matrix), on the device in both forms"""
 
-    def __init__(self, pair, rows, cols, offsets, col, val, x, shift=False):
+    def __init__(self, pair, rows, cols, offsets, col, val, x, shift=False, exact=False):
         sdt, cdt, npdt, vb, _ = PAIRS[pair]
         self.pair, self.vb, self.cdt, self.rows, self.cols, self.nnz = pair, vb, cdt, int(rows), int(cols), int(len(col))
-        v_narrow, v_wide = narrow(pair, val)
+        v_narrow, v_wide = (narrow_exact if exact else narrow)(pair, val)
         self.csr = O.Csr(self.rows, self.cols, np.asarray(offsets, np.int32), np.asarray(col, np.int32), v_wide)
         self.x = np.asarray(x, npdt)
         place = off_by_one if shift else (lambda t: t)
@@ -198,6 +225,77 @@ def test_bitwise_equal_to_the_wide_call_on_the_widened_values(G, shape, pair, pa
                             assert same_bits(yw, ym), where
             if not shift:
                 T.check_strict(Mod, P.csr, P.x, P.mixed(P.workspace()).cpu().numpy())
+    finally:
+        Mod.set_tuning(vb)
+
+
+def mixed_e_values(pair, which, total):
+    """e_values of axpby_model.scale_exponents for a mixed pair, from the STORED type's own range: "bottom_stored" puts one unit of
+    the values at the stored type's smallest subnormal (2^-133 for bf16, 2^-149 for fp32); "bottom" and "top" split the total evenly
+    between values and x, moved just far enough that the values (1 and 2 units) stay normal and finite in the stored type"""
+    fi = torch.finfo(PAIRS[pair][0])
+    emin = int(np.log2(fi.tiny))                                   # the smallest normal: 2^emin
+    mant = int(round(-np.log2(fi.eps)))
+    emax = int(np.floor(np.log2(fi.max)))
+    if which == "bottom_stored":
+        return emin - mant
+    return min(max(total // 2, emin), emax - 2)
+
+
+def test_mixed_e_values_follow_the_stored_type():
+    assert [mixed_e_values("bf16_f32", w, t) for w, t in (("bottom", -148), ("bottom_stored", -148), ("top", 104))] == [-74, -133, 52]
+    assert [mixed_e_values("f32_f64", w, t) for w, t in (("bottom", -1073), ("bottom_stored", -1073), ("top", 971))] == [-126, -149, 125]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair", sorted(PAIRS))
+@pytest.mark.parametrize("path", sorted(T.PATHS))
+def test_zero_laden_and_scaled_values_equal_the_wide_call_and_the_model(G, pair, path):
+    """A zero-laden problem (tests/axpby_model.zero_problem: stored zeros of both signs -- widening keeps the sign --, zeros in x and
+    y0, rows whose products are all -0.0) through the loop of test_bitwise_equal_to_the_wide_call_on_the_widened_values -- every
+    dispatch path, stateless and prepared, aligned arrays and arrays one element off, first call and call on hints --, and the same
+    problem scaled to both ends of the exponent range (subnormal bf16 / fp32 stored values through the widening included): the
+    mixed call equals the wide call AND the int64 model on the bits -- the model directly, because an error the two calls share
+    passes the first comparison.  The atomic fix-up too: on exact data it is order-independent."""
+    import axpby_model as AM
+    sdt, cdt, npdt, vb, _ = PAIRS[pair]
+    rng = np.random.default_rng(99)
+    rows, cols, lens = T.SHAPES["power_law"](rng)
+    base = AM.zero_problem(rng, rows, cols, np.asarray(lens, np.int64), npdt)
+    try:
+        Mod.set_tuning(vb, 0, 0, T.PATHS[path])
+        for which in ("plain", "bottom", "bottom_stored", "top"):
+            pairs = AM.PAIRS + [(-0.5, 0)] if which == "plain" else AM.SCALE_PAIRS
+            ev, ex = 0, 0
+            if which != "plain":
+                total = sum(AM.scale_exponents(npdt, which))
+                ev, ex = AM.scale_exponents(npdt, which, e_values=mixed_e_values(pair, which, total))
+            csr, x, y0 = AM.scaled(base, ev, ex)
+            mag = np.abs(csr.values[csr.values != 0]).astype(np.float64)          # (on the host: nothing here can flush)
+            tiny = float(torch.finfo(sdt).tiny)
+            if which == "bottom_stored":
+                assert 0 < mag.min() and mag.max() < tiny
+            elif which != "plain":
+                assert tiny <= mag.min() and mag.max() <= float(torch.finfo(sdt).max)
+            want = {(a, b): torch.from_numpy(AM.model(*base, a, b, scale=ev + ex)) for a, b in pairs + [(1, 0)]}
+            for shift in (False, True):
+                P = Problem(pair, rows, cols, csr.row_offsets, csr.column_indices, csr.values, x, shift=shift, exact=True)
+                stored = P.d_narrow.cpu()
+                assert np.array_equal(stored.view(torch.int16 if pair == "bf16_f32" else torch.int32).numpy(), narrow_exact(pair, csr.values)[0].view(
+                    torch.int16 if pair == "bf16_f32" else torch.int32).numpy()), "the stored values on the device are not the host's bit patterns"
+                assert Mod.band_passes(P.rows, P.cols, P.nnz, vb) <= 1
+                yin = torch.from_numpy(y0).cuda()
+                for prepared in (False, True):
+                    for alpha, beta in pairs:
+                        ws_w, ws_m = P.workspace(prepared), P.workspace(prepared)
+                        for call in ("first", "on hints"):
+                            kw = {"alpha": float(alpha), "beta": float(beta)}
+                            yw, ym = P.wide(ws_w, yin, **kw), P.mixed(ws_m, yin, **kw)
+                            torch.cuda.synchronize()
+                            where = (pair, path, which, shift, prepared, alpha, beta, call)
+                            assert same_bits(ym.cpu(), want[(alpha, beta)]), (where, "mixed call against the model")
+                            assert same_bits(yw, ym), (where, "wide call against the mixed call")
+                    assert same_bits(P.mixed(P.workspace(prepared)).cpu(), want[(1, 0)]), (pair, path, which, shift, prepared, "plain mixed call")
     finally:
         Mod.set_tuning(vb)
 

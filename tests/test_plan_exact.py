@@ -172,11 +172,10 @@ def device_x(case, prec, x=None):
 
 def assert_exact_y(plan, case, prec, alpha, beta, offset, xd, label, want=None, skip_rows=None):
     """y = alpha A x + beta y0 on the bits, y a view of a buffer of sentinels at an aligned (offset 0) or misaligned (offset 1)
-    address; beta == 0: y starts as NaN.  The one thing an association can change in these cases is the SIGN of a sum that is
-    zero ((-0) + (-0) = -0, (+0) + (-0) = +0; x holds zeros, so products are +-0): a zero result of a row that has entries may
-    carry either sign; a row without entries must hold +0.0 or exactly beta * y0.  (That is meant to cover rows whose products are all
-    +-0 as well: the stateless call's plain form may write -0.0 there, and with one band the plan is that call.  The sign the
-    fold itself writes is pinned where it is defined: on rows without entries, here and in test_no_rows_and_no_nonzeros.)"""
+    address; beta == 0: y starts as NaN.  x holds zeros (+0.0), so products are +-0.0 and whole rows sum zeros: the sign of every
+    zero result is DEFINED (include/mspmv.h at mspmv_csrmv_axpby_*: every sum, every band's partial sum and every carry starts from
+    +0.0; beta is never negative here and y0 holds no -0.0, so t = beta * y0 is never -0.0) -- it is +0.0, for every band count, and
+    no row is masked."""
     npdt, udt, _ = PREC[prec]
     rows = case.a.rows
     y0 = case.y0.astype(np.float64) if beta != 0.0 else np.full(rows, np.nan)
@@ -188,8 +187,6 @@ def assert_exact_y(plan, case, prec, alpha, beta, offset, xd, label, want=None, 
     sentinel = np.full(1, SENTINEL, npdt).view(udt)[0]
     assert np.all(front.view(udt) == sentinel) and np.all(back.view(udt) == sentinel), (label, "y written outside its rows", front, back)
     want = (case.want(alpha, beta) if want is None else want).astype(npdt)
-    has_entries = np.diff(case.a.row_offsets) > 0
-    body[(want == 0) & (body == 0) & has_entries] = 0.0
     if skip_rows is not None:
         body[skip_rows], want = 0.0, np.where(skip_rows, 0.0, want).astype(npdt)
     bad = np.flatnonzero(body.view(udt) != want.view(udt))

@@ -2,12 +2,23 @@
 
 For every row of spmm_forms.CASES: the `mspmv: <kernel><<<grid, block>>>` lines of a debug_synchronous call must equal the launches
 the restated dispatch rule (tests/spmm_forms.py) expects -- the kernel name gives the form, grid and block the tile size -- and Y
-must equal an int64 reference bit for bit: matrix values (nonzero integers in [-8, 8], +-1 on the giant row), X (+-1 .. 3),
+must equal an int64 reference BIT FOR BIT (the bit patterns are compared: -0.0 is not +0.0): matrix values (nonzero integers in [-8, 8], +-1 on the giant row), X (+-1 .. 3),
 Y0 (+-1 .. 8), alpha in {1, -2} and beta in {0, 3} are integers with |alpha| sum |a x| + |beta| |y0| <= 2^24 (fp32; 2^53 in fp64) on
 every row and column, which the test asserts on the reference's own sums first: every partial sum in any association order is then
 an integer the format holds, and a dropped, doubled or misplaced product changes Y.  No row or column is left out.  X and Y are
 views inside wider buffers; the other columns of X hold NaN, those of Y a sentinel that must survive.  Y is NaN before a call with
 beta = 0.  A second call gives the same bits.
+
+ZEROS.  Y0 is never zero here, so t = beta * Y0 is never -0.0 and every zero of Y is defined as +0.0 (include/mspmv.h at
+mspmv_csrmm_*: sums start from +0.0, Y = alpha * s + (beta == 0 ? +0.0 : beta * Y0)), which is what the int64 reference converts
+to.  The cases with alpha < 0 and beta == 0 are asserted to hold rows without entries and zero sums of rows with entries.
+spmm_forms.ZERO_CASES run the tiny, mid and big cases again on ZERO-LADEN data: a quarter of the matrix values and of X zeros of
+both signs, and planted rows -- every value a zero of mixed sign; every product exactly -0.0 in every column of X (or in every
+second one); pairs v, -v on one column that cancel wherever X is not zero there.  The huge cases run the same arithmetic with
+non-temporal loads and keep their non-zero data.  spmm_forms.SCALED (one pack and one slot case per precision) run with the
+integers scaled so that one unit of the reference is the smallest subnormal (values and X normal; the stored values subnormal)
+and 2^(emax - mantissa bits); the scaled arrays are made on the host.  test_negative_zero_in_y0_on_rows_without_entries is the one
+place where t is -0.0: on rows without entries, where the definition gives alpha * (+0.0) + (-0.0).
 
 The log names the kernel, grid.x and block of every launch: that pins the form and the tile size.  Which AXPBY / NT instantiation
 ran, the width of a pack launch among those sharing a tile size, and the fix-up's grid.y (groups) are not printed; the coverage
@@ -16,18 +27,22 @@ width or group count does show in the exact comparison (columns left unwritten s
 
 The matrices (spmm_forms.structure) are built once each and freed before the next.
 
-Measured on one MI355X: the 30 tests of this file take 5.3 s (7 s with the interpreter's start), beside 203 s for the other 1802
-GPU tests.  Sensitivity, each a one-line change of mspmv_spmm.hpp tried against this file, every failure the exact comparison:
+Measured on one MI355X: the 62 tests of this file take 8.6 s (the 30 before the zero-laden and scaled cases: 5.3 s), beside some
+four minutes for the other GPU tests.  Sensitivity, each a one-line change of mspmv_spmm.hpp tried against this file, every failure the exact comparison:
 the slot form's before() stopping one slot early fails the 10 big_slots / big_slot_groups / huge_slots_nt cases; its carries
 indexed without g * num_tiles the 4 cases with two groups of 16 (big_slot_groups, huge_slots_nt_plain); the pack kernel without
 its nz_tail store every case that runs a pack (24 tests: the last row, in the pack widths' columns); the fix-up without its
 look-ahead sum all 26 tests off the row-wise kernel (the giant row).  Writing the pack kernel's select `in ? val * xv : 0` as a
 product with 0 / 1 changes nothing in Y: the positions it zeroes lie outside the tile's own nonzeros in LDS, where no row sum,
 carry or scan result that is used reads -- with X[0, :] = NaN those positions hold NaN and Y is still the clean run's, which is
-what test_nan_and_inf_stay_where_they_are asserts.
+what test_nan_and_inf_stay_where_they_are asserts.  The "+ 0" of the beta == 0 write taken out again (pack kernel's row phase and
+the slot form's put, the state before the sign of a zero sum was pinned): 10 tests fail, all on the sign of a zero -- mid_wide_groups_* (alpha = -2, beta = 0) with
+and without zeros, big_slots_negative_alpha_beta_0_*_zeros, and step 4 of test_nan_and_inf_stay_where_they_are on the pack and the
+slot case of both precisions.
 """
 import re
 
+import numpy as np
 import pytest
 
 import spmm_forms as F
@@ -40,8 +55,15 @@ EXACT = {"f32": 1 << 24, "f64": 1 << 53}
 SENTINEL = 777.0
 ROW_CHUNK = 1 << 21
 MAT_ORDER = {"tiny": 0, "mid": 1, "big": 2, "huge": 3}
-ORDERED = sorted(F.CASES, key=lambda c: MAT_ORDER[c.mat])
+ORDERED = sorted(F.CASES + F.ZERO_CASES, key=lambda c: MAT_ORDER[c.mat])
+BOTTOM, TOP = {"f32": -149, "f64": -1074}, {"f32": 127 - 24, "f64": 1023 - 53}        # the smallest subnormal; 2^(emax - mantissa bits)
+KIND_I, KIND_II, KIND_III, KIND_II_EVEN = 3, 7, 11, 13      # row % 16 of the planted rows of the zero-laden data
+ZERO_COL, POS_COL, NEG_ZERO_COL, NEG_COL, EVEN_COL = 1, 2, 3, 4, 5
 LAUNCH = re.compile(r"^mspmv: (\w+)<<<(\d+), (\d+)>>>$", re.M)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
 
 
 def _hash(seed, idx):
@@ -143,7 +165,11 @@ class Call:
         self.cidx = mat.cols(cols)[:nnz].clone()
         self.cidx[-1] = cols - 1                   # the last nonzero sits in the last column (its neighbours keep theirs: the tail's
                                                    # products then differ from column to column of X)
-        v, ci = mat.vals(c.prec)[:nnz], self.cidx.to(torch.int32)
+        self.vals64 = mat.vals64[:nnz]
+        v = mat.vals(c.prec)[:nnz]
+        if c.zeros:
+            v = self.plant_zeros()
+        ci = self.cidx.to(torch.int32)
         if c.pad:
             vp = torch.empty(nnz + c.pad, dtype=dt, device="cuda")[c.pad:]; vp.copy_(v); v = vp
             cp = torch.empty(nnz + c.pad, dtype=torch.int32, device="cuda")[c.pad:]; cp.copy_(ci); ci = cp
@@ -151,7 +177,6 @@ class Call:
         else:
             assert v.data_ptr() % 16 == 0 and ci.data_ptr() % 16 == 0 and self.off.data_ptr() % 16 == 0
         self.vals, self.ci = v, ci
-        self.vals64 = mat.vals64[:nnz]
         # X: the view holds integers, every other column of the buffer NaN
         self.Xw = torch.full((cols, c.xw), float("nan"), dtype=dt, device="cuda")
         self.X = self.Xw[:, c.x_off:c.x_off + c.k]
@@ -160,10 +185,67 @@ class Call:
             hi = min(lo + ROW_CHUNK, cols)
             r = torch.arange(lo, hi, dtype=torch.int64, device="cuda")
             self.X[lo:hi] = _pm(0x5F0003, r[:, None] * 64 + j[None, :], 3).to(dt)
+            if c.zeros:                                # a quarter zeros, of both signs
+                h = _hash(0x5F0013, r[:, None] * 64 + j[None, :]) % 8
+                self.X[lo:hi] = torch.where(h == 0, 0.0, torch.where(h == 1, -0.0, self.X[lo:hi].to(torch.float64))).to(dt)
+        if c.zeros:
+            # the columns a planted row refers to: X all +0.0, all positive, all -0.0, all negative, +0.0 in every second column
+            self.X[ZERO_COL], self.X[cols - 1] = 0.0, 0.0
+            self.X[POS_COL], self.X[NEG_ZERO_COL], self.X[NEG_COL] = self.X[POS_COL].abs().clamp(min=1), -0.0, -self.X[NEG_COL].abs().clamp(min=1)
+            self.X[EVEN_COL] = torch.where(j % 2 == 0, 0.0, 2.0).to(dt)
+            xb = _bits(self.X)
+            assert bool((xb == 0).any()) and bool((xb == _bits(torch.tensor([-0.0], dtype=dt, device="cuda"))).any())
         assert self.Xw.data_ptr() % 256 == 0
         r = torch.arange(rows, dtype=torch.int64, device="cuda")
         self.y0 = _pm(0x5F0004, r[:, None] * 64 + j[None, :], 8)
         self.y_ref, self.s = self.reference(self.vals64, self.X)
+
+    def plant_zeros(self):
+        """the zero-laden values (and column indices) of this case; returns the float values, leaves their integers in vals64"""
+        c, nnz, dt = self.c, self.nnz, self.dt
+        k = torch.arange(nnz, dtype=torch.int64, device="cuda")
+        row = torch.searchsorted(self.off64, k, right=True) - 1
+        pos, length = k - self.off64[row], (self.off64[1:] - self.off64[:-1])[row]
+        kind = row % 16
+        v = self.vals64.clone()
+        h = _hash(0x5F0011, k) % 8
+        v[h < 2] = 0
+        negz = h == 1                                                       # the zeros that are -0.0
+        if self.cols > EVEN_COL + 1:
+            # (ii): every product exactly -0.0, whatever the column of X: negative * +0.0, -0.0 * positive, positive * -0.0, +0.0 * negative
+            m = kind == KIND_II
+            to = 1 + _hash(0x5F0012, k) % 4
+            self.cidx = torch.where(m, to, self.cidx)
+            mag = self.vals64.abs()
+            v = torch.where(m & (to == ZERO_COL), -mag, torch.where(m & (to == NEG_ZERO_COL), mag, torch.where(m, 0, v)))
+            negz = torch.where(m, to == POS_COL, negz)
+            # (ii) in every second column of X, a negative sum in the others
+            m = kind == KIND_II_EVEN
+            self.cidx = torch.where(m, EVEN_COL, self.cidx)
+            v = torch.where(m, -mag, v)
+            # (iii): pairs v, -v on one column; the last value of a row of odd length is a zero
+            m = kind == KIND_III
+            head = m & (pos % 2 == 0)
+            v = torch.where(head & (v == 0), 1, v)
+            tail = (m & (pos % 2 == 1)).nonzero()[:, 0]
+            v[tail] = -v[tail - 1]
+            self.cidx[tail] = self.cidx[tail - 1]
+            v = torch.where(head & (pos == length - 1), 0, v)
+        # (i): every value a zero, the signs alternating
+        m = kind == KIND_I
+        v = torch.where(m, 0, v)
+        negz = torch.where(m, (pos + row // 16) % 2 == 1, negz)
+        # the last nonzero meets X[cols - 1, :] = +0.0 with a negative value
+        self.cidx[-1] = self.cols - 1
+        v[-1] = -1
+        if nnz < 64:                                                        # (the tiny case: a stored -0.0 whatever the hash drew)
+            v[0], negz[0] = 0, True
+        self.vals64 = v
+        f = v.to(torch.float64)
+        f = torch.where((v == 0) & negz, -0.0, f).to(dt)
+        fb = _bits(f)
+        assert bool((fb == _bits(torch.tensor([-0.0], dtype=dt, device="cuda"))).any()) and (nnz < 64 or bool((fb == 0).any()))
+        return f
 
     def reference(self, vals64, X):
         """int64 [rows, k]: the segmented sums of a * X[col] and of |a * X[col]|, from running sums (exact, no atomics)"""
@@ -209,10 +291,13 @@ class Call:
 
 
 def _assert_exact(name, Y, want, off64, what=""):
-    got, ref = Y.to(torch.float64), want.to(torch.float64)
-    if torch.equal(got, ref):
+    """the bit patterns: an int64 zero of the reference is +0.0, and a -0.0 in Y differs from it"""
+    ref = want.to(Y.dtype) if want.dtype == torch.int64 else want
+    assert bool((ref.to(torch.float64) == want.to(torch.float64)).all()), f"{name}: the reference is not representable"
+    bad = _bits(Y) != _bits(ref)
+    if not bool(bad.any()):
         return
-    bad = (got != ref) | torch.isnan(got)
+    got, ref = Y.to(torch.float64), ref.to(torch.float64)
     at = torch.nonzero(bad)
     r, j = int(at[0, 0]), int(at[0, 1])
     pytest.fail(f"{name} {what}: {int(bad.sum())} of {bad.numel()} entries differ from the exact reference, in {int(bad.any(1).sum())} rows and "
@@ -220,8 +305,12 @@ def _assert_exact(name, Y, want, off64, what=""):
                 f"got {float(got[r, j])!r}, want {float(ref[r, j])!r}")
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+def _assert_zero_rows(call):
+    """a case with alpha < 0 and beta == 0 is about the sign of a zero: it must hold rows without entries and zero sums of rows with
+    entries (on the reference, before the call)"""
+    lens = call.off64[1:] - call.off64[:-1]
+    assert bool((lens == 0).any()), f"{call.c.name}: no row without entries"
+    assert bool(((call.y_ref == 0) & (lens > 0)[:, None]).any()), f"{call.c.name}: no zero result on a row with entries"
 
 
 @pytest.mark.parametrize("case", ORDERED, ids=lambda c: c.name)
@@ -232,6 +321,12 @@ def test_form_runs_and_is_exact(M, mats, capfd, case):
     worst = int((abs(c.alpha) * call.s + abs(c.beta) * call.y0.abs()).max())
     assert worst <= EXACT[c.prec], f"{c.name}: |alpha| sum |a x| + |beta| |y0| reaches {worst}"
     assert int(call.s.min()) >= 0 and int(call.cidx.min()) >= 1 and int(call.cidx.max()) == call.cols - 1
+    if c.alpha < 0 and c.beta == 0:
+        _assert_zero_rows(call)
+    if c.zeros and c.mat != "tiny":
+        # per column of X: zero sums of rows whose products are all zero, and of rows whose non-zero products cancel
+        lens = (call.off64[1:] - call.off64[:-1])[:, None]
+        assert bool(((call.s == 0) & (lens > 0)).any(0).all()) and bool(((call.s > 0) & (call.y_ref == 0)).any(0).all())
     capfd.readouterr()
     Y = call.run(M, debug=True)
     log = [(n, int(g), int(b)) for n, g, b in LAUNCH.findall(capfd.readouterr().out)]
@@ -292,6 +387,75 @@ def test_nan_and_inf_stay_where_they_are(M, mats, case):
     compare(call.run(M), mask, f"Inf in X at {spots}")
     for (col, j), v in zip(spots, kept):
         call.X[col, j] = v
-    # 4. beta = 0: Y0 = NaN is never read (alpha = -2)
+    # 4. beta = 0: Y0 = NaN is never read (alpha = -2), and a zero sum under a negative alpha is +0.0
+    _assert_zero_rows(call)
     Y = call.run(M, alpha=c.alpha, beta=0)
     _assert_exact(c.name, Y, call.want(c.alpha, 0), call.off64, "beta = 0 over a NaN Y")
+
+
+@pytest.mark.parametrize("which", ["bottom", "bottom_stored", "top"])
+@pytest.mark.parametrize("case", sorted(F.SCALED, key=lambda c: MAT_ORDER[c.mat]), ids=lambda c: c.name)
+def test_both_ends_of_the_exponent_range(M, mats, case, which):
+    """The case's integers times powers of two: one unit of the reference is the smallest subnormal -- values and X both normal, only
+    products and sums subnormal (bottom), or the stored values themselves subnormal and X small integers (bottom_stored) -- or
+    2^(emax - mantissa bits) (top: at most 2^24 | 2^53 units in any association, so nothing may overflow).  Every intermediate
+    stays an exact multiple of the unit; a flush to zero anywhere changes Y.  Scaled on the host: numpy's ldexp is exact."""
+    c = case
+    call = Call(mats(c.mat), c)
+    assert int((abs(c.alpha) * call.s + abs(c.beta) * call.y0.abs()).max()) <= EXACT[c.prec]
+    total = TOP[c.prec] if which == "top" else BOTTOM[c.prec]
+    ev = total if which == "bottom_stored" else total // 2
+    ex = total - ev
+    ndt = np.float32 if c.prec == "f32" else np.float64
+
+    def scaled(t, e):
+        a = t.cpu().numpy().astype(np.float64)
+        w = np.ldexp(a, e)
+        out = w.astype(ndt)
+        assert np.array_equal(out.astype(np.float64)[~np.isnan(a)], w[~np.isnan(a)]), "a scaled input is not representable"
+        host[len(host):] = [out]
+        return torch.from_numpy(out).cuda()
+    host = []
+    vals = scaled(call.vals64, ev)
+    if c.pad:
+        vp = torch.empty(call.nnz + c.pad, dtype=call.dt, device="cuda")[c.pad:]; vp.copy_(vals); vals = vp
+    tiny = float(np.finfo(ndt).tiny)
+    mag = np.abs(host[0])                                      # (the host copy: a device op that flushed would hide what it checks)
+    if which == "bottom_stored":
+        assert 0 < mag.min() and mag.max() < tiny
+    keep = call.Xw.clone()
+    try:
+        call.Xw.copy_(scaled(call.Xw, ex))
+        if which == "bottom":
+            xh = np.abs(host[1][:, c.x_off:c.x_off + c.k])
+            assert mag.min() >= tiny and xh.min() >= tiny
+        want = scaled(call.want(), total)
+        Yw, Y = call.fresh_y()
+        Y.copy_(scaled(call.y0, total))
+        M.csrmm(vals, call.off, call.ci, call.X, Y=Y, alpha=float(c.alpha), beta=float(c.beta))
+        torch.cuda.synchronize()
+        assert bool((Yw[:, :c.y_off] == SENTINEL).all()) and bool((Yw[:, c.y_off + c.k:] == SENTINEL).all())
+        _assert_exact(c.name, Y, want, call.off64, which)
+    finally:
+        call.Xw.copy_(keep)
+
+
+@pytest.mark.parametrize("alpha", [2, -2])
+@pytest.mark.parametrize("case", sorted(F.CONTAINMENT, key=lambda c: MAT_ORDER[c.mat]), ids=lambda c: c.name)
+def test_negative_zero_in_y0_on_rows_without_entries(M, mats, case, alpha):
+    """t = beta * Y0 = -0.0 on every row without entries (beta = 3): such a row is alpha * (+0.0) + (-0.0) -- +0.0 for a positive
+    alpha, -0.0 for a negative one -- in the pack kernel and in the slot form, whose rows without entries are written by a loop of
+    their own (writing beta * Y alone there gives -0.0 for alpha = 2).  Rows with entries keep their non-zero Y0: a zero sum of
+    non-zero products under t = -0.0 is the undefined corner."""
+    c = case
+    call = Call(mats(c.mat), c)
+    empty = (call.off64[1:] == call.off64[:-1])
+    assert int(empty.sum()) > F.TILE_SLOT
+    Yw, Y = call.fresh_y(beta=3)
+    Y[empty] = -0.0
+    assert bool((_bits(Y[empty]) != 0).all())
+    M.csrmm(call.vals, call.off, call.ci, call.X, Y=Y, alpha=float(alpha), beta=3.0)
+    torch.cuda.synchronize()
+    want = call.want(alpha, 3).to(call.dt)
+    want[empty] = -0.0 if alpha < 0 else 0.0
+    _assert_exact(c.name, Y, want, call.off64, f"alpha = {alpha}, Y0 = -0.0 on rows without entries")
