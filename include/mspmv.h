@@ -535,6 +535,55 @@ int mspmv_csr_gemm_f64(void *d_temp, size_t *temp_bytes, int32_t rows, int32_t i
                        double *d_values_c, int32_t *d_row_offsets_c /* [rows + 1] */, int32_t *d_column_indices_c, int32_t *d_nnz_c,
                        mspmv_stream_t stream, int debug_sync);
 
+/* ---- extension: SDDMM, the sampled dense-dense product  C = alpha * (U V^T sampled at a CSR pattern) + beta * C  on the device
+ * (csrc/mspmv_sddmm.hip; what rocsparse_sddmm is in rocSPARSE): the gradient of SpMM with respect to the matrix values,
+ * dA = pattern(A) (.) (dY X^T), with U = dY and V = X laid out exactly as mspmv_csrmm_* lays out Y and X -- no copies --; edge scores
+ * and attention logits on a graph (U = V = H); the sampled residual of a low-rank factorisation.
+ * INPUTS: the pattern (d_row_offsets, d_column_indices; rows x cols, nnz entries) of ANY valid CSR: rows need not be sorted, a
+ * repeated column gives the same value twice, empty rows may sit anywhere.  U is rows x k, V is cols x k, both row-major with
+ * leading dimensions ldu, ldv >= k in elements.  U and V may be the same array; C must not alias U or V.  The pattern, U and V are
+ * not modified.  C is the VALUES array alone (nnz entries).
+ * VALUES, defined bit for bit in the compute type, for every stored entry e in row r with c = d_column_indices[e]:
+ *     s = +0.0;  for t = 0 .. k-1:  s = s + U[r*ldu + t] * V[c*ldv + t]      (left to right)
+ *     C[e] = alpha * s + (beta == 0 ? +0.0 : beta * C[e])
+ * every multiply and every add rounded on its own (no fused multiply-add), nothing flushed to zero.  So C[e] is a function of U's
+ * row, V's row, k, alpha, beta and the old C[e] alone -- not of where the entry sits in a tile, of nnz, of the alignment or of the
+ * code path that ran.  s is never -0.0; with beta == 0 a zero result is +0.0, for negative alpha too, and the old C is never read
+ * (it may hold NaN).  k == 0 gives alpha * (+0.0) + the beta term.
+ * mspmv_sddmm_bf16_f32: U and V are STORED as bf16 -- the upper 16 bits of an fp32, the convention of mspmv_csrmv_mixed_bf16_f32 --
+ * and widened in registers; products, sums, alpha, beta and C are fp32.  Widening is exact: the result is bit for bit that of
+ * mspmv_sddmm_f32 on the widened U and V.  The gathers of V are the cost of this operation, and bf16 halves them.
+ * HOW: every entry costs the same k, so the entries are cut into tiles of 512 whatever the row lengths -- one row holding every
+ * entry costs what a million short ones cost.  A tile finds its rows by searching the row offsets inside the kernel (NO temp
+ * storage, as for mspmv_csr_transpose_values_*); one lane owns one entry's sum; V is read in chunks of 128 bytes of k, 8
+ * neighbouring lanes loading one entry's slice as consecutive 16-byte words into LDS, from where each lane reads its own entry's
+ * slice back (rows of V shorter than 64 bytes are read by their lane directly: measured faster).  That path needs d_u and d_v
+ * 16-byte aligned and ldu, ldv multiples of 16 bytes; anything else runs an element-wise kernel with the same bits.  One launch, no atomics, no workgroup waits on another; the host reads no device memory and launches
+ * the same kernel whatever the data: the call can be captured in a graph.
+ * The caller owns every buffer; asynchronous on `stream`; debug_sync prints one line per launch and waits for it; returns 0 or a
+ * hipError_t; nothing outside the arrays is read or written (column indices lie in [0, cols), not checked, as everywhere).
+ * LIMITS: rows, cols, nnz, k >= 0; ldu, ldv >= k; rows + nnz <= 2^31 - 65537; entries together with rows == 0 or cols == 0 are
+ * refused; nnz == 0 succeeds and launches nothing (every pointer may be NULL); with k == 0, d_u and d_v may be NULL.  r*ldu + t and
+ * c*ldv + t are formed in 64 bits: U and V may be larger than 4 GB.
+ * Measured on MI355X against rocsparse_sddmm (default algorithm, preprocess outside the timing) on the same arrays
+ * (profiles/sddmm_bench.txt; DESIGN.md 4 "SDDMM"): config 2's pattern (3.1 M x 3.1 M, 100 M
+ * entries) at k = 16 / 64 / 128: fp32 1.99 / 3.72 / 7.50 ms against 4.61 / 11.6 / 21.4 ms, fp64 2.21 / 7.65 / 16.7 against 6.04 / 18.0 /
+ * 32.9 ms, bf16 1.91 / 2.23 / 4.02 ms (this rocSPARSE build's dense descriptors refuse bf16); a 5-point grid of 2000 x 2000, fp32:
+ * 0.43 / 0.70 / 1.18 against 0.55 / 1.65 / 3.30 ms; an R-MAT graph of scale 22 (67 M entries), fp32: 1.23 / 2.65 / 6.01 against 149 / 275 /
+ * 489 ms; 2^24 entries in ONE row, fp32: 0.27 / 0.72 / 1.45 ms against 13.3 / 28.3 / 48.2 s.  rocSPARSE was faster in no case measured. ---- */
+int mspmv_sddmm_f32(const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                    const float *d_u, int32_t ldu, const float *d_v, int32_t ldv, float *d_values_c,
+                    int32_t rows, int32_t cols, int32_t nnz, int32_t k,
+                    float alpha, float beta, mspmv_stream_t stream, int debug_sync);
+int mspmv_sddmm_f64(const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                    const double *d_u, int32_t ldu, const double *d_v, int32_t ldv, double *d_values_c,
+                    int32_t rows, int32_t cols, int32_t nnz, int32_t k,
+                    double alpha, double beta, mspmv_stream_t stream, int debug_sync);
+int mspmv_sddmm_bf16_f32(const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                         const uint16_t *d_u, int32_t ldu, const uint16_t *d_v, int32_t ldv, float *d_values_c,
+                         int32_t rows, int32_t cols, int32_t nnz, int32_t k,
+                         float alpha, float beta, mspmv_stream_t stream, int debug_sync);
+
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */
 typedef struct mspmv_launch_info {

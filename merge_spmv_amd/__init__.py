@@ -18,7 +18,7 @@ import os
 from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
-           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products",
+           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -191,6 +191,10 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "mspmv_csr_gemm_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, sz_p, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_int]
+    for name, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double), ("bf16_f32", ctypes.c_float)):
+        fn = getattr(lib, "mspmv_sddmm_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, ct, ct, vp, ctypes.c_int]
     lib.mspmv_csr_gemm_products.restype = ctypes.c_int
     lib.mspmv_csr_gemm_products.argtypes = [vp, sz_p, vp, vp, i32, i32, i32, vp, i32, vp, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_skew.restype = ctypes.c_int
@@ -1009,6 +1013,60 @@ def csr_gemm(a, b, stream=None, trim: bool = True):
     if trim:
         return op.trimmed()
     return DeviceCsr(op.rows, op.cols, op.row_offsets, op.column_indices, op.values)
+
+
+def sddmm(row_offsets, column_indices, U, V, out=None, alpha: float = 1.0, beta: float = 0.0, stream=None,
+          debug_synchronous: bool = False):
+    """The sampled dense-dense product (mspmv_sddmm_*): for every stored entry e of the CSR pattern, in row r and column c,
+    out[e] = alpha * (U[r, :] . V[c, :]) + beta * out[e], the dot product added left to right, every operation rounded on its own
+    (include/mspmv.h states the bits).  U: [rows, k], V: [cols, k] CUDA tensors with unit stride along k (leading dimensions from
+    stride(0)), both float32, both float64, or both bfloat16 with a float32 `out`.  `out`: the nnz values, required when
+    beta != 0; with beta == 0 it is never read.  U = dY, V = X gives the gradient of csrmm with respect to the matrix values.
+    Asynchronous on `stream`; one launch, no temp storage.  Returns out."""
+    import torch
+    for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices"), (U, "U"), (V, "V")):
+        if not isinstance(t, torch.Tensor):
+            raise MspmvError(f"sddmm: {name} must be a tensor")
+    if not (row_offsets.is_cuda and column_indices.is_cuda and U.is_cuda and V.is_cuda):
+        raise MspmvError("sddmm needs CUDA (HIP) tensors: the kernels only run on the GPU")
+    if row_offsets.dtype != torch.int32 or column_indices.dtype != torch.int32:
+        raise TypeError("sddmm: row_offsets / column_indices must be int32")
+    dev = U.device
+    if U.dtype != V.dtype:
+        raise TypeError(f"sddmm: U holds {U.dtype}, V {V.dtype}")
+    if U.dtype not in (torch.float32, torch.float64, torch.bfloat16):
+        raise TypeError(f"sddmm is instantiated for float32, float64 and bfloat16 (with float32 out), got {U.dtype}")
+    out_dtype = torch.float32 if U.dtype == torch.bfloat16 else U.dtype
+    for t, name in ((U, "U"), (V, "V")):
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise MspmvError(f"sddmm: {name} must be 2-D with unit stride along k (row-major)")
+    if row_offsets.dim() != 1 or row_offsets.numel() < 1 or not row_offsets.is_contiguous() or column_indices.dim() != 1 \
+            or not column_indices.is_contiguous():
+        raise MspmvError("sddmm: row_offsets (rows + 1 entries) and column_indices must be contiguous 1-D tensors")
+    rows, cols, nnz, k = row_offsets.numel() - 1, V.shape[0], column_indices.numel(), U.shape[1]
+    if U.shape[0] != rows or V.shape[1] != k:
+        raise MspmvError(f"sddmm: U must be [{rows}, k] and V [cols, k] with the same k, got {tuple(U.shape)} and {tuple(V.shape)}")
+    ldu = U.stride(0) if rows > 1 else max(k, 1)
+    ldv = V.stride(0) if cols > 1 else max(k, 1)
+    if ldu < k or ldv < k:
+        raise MspmvError("sddmm: leading dimensions must be at least k (no overlapping / broadcast rows)")
+    if out is None:
+        if beta != 0:
+            raise MspmvError("sddmm: beta != 0 needs `out`, the values it scales")
+        out = torch.empty(nnz, dtype=out_dtype, device=dev)
+    if not isinstance(out, torch.Tensor) or out.dtype != out_dtype:
+        raise TypeError(f"sddmm: out must be a {out_dtype} tensor for {U.dtype} U and V")
+    if out.dim() != 1 or out.numel() != nnz or not out.is_contiguous():
+        raise MspmvError(f"sddmm: out must be a contiguous 1-D tensor of {nnz} entries")
+    for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices"), (V, "V"), (out, "out")):
+        if t.device != dev:
+            raise MspmvError(f"sddmm: {name} must be on {dev}")
+    lib = load_library()
+    fn, ct = {torch.float32: (lib.mspmv_sddmm_f32, ctypes.c_float), torch.float64: (lib.mspmv_sddmm_f64, ctypes.c_double),
+              torch.bfloat16: (lib.mspmv_sddmm_bf16_f32, ctypes.c_float)}[U.dtype]
+    _check(int(fn(_ptr(row_offsets), _ptr(column_indices), _ptr(U), int(ldu), _ptr(V), int(ldv), _ptr(out), rows, cols, nnz, k,
+                  ct(alpha), ct(beta), _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_sddmm")
+    return out
 
 
 class CsrMVPlan:
