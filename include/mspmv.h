@@ -584,6 +584,76 @@ int mspmv_sddmm_bf16_f32(const int32_t *d_row_offsets, const int32_t *d_column_i
                          int32_t rows, int32_t cols, int32_t nnz, int32_t k,
                          float alpha, float beta, mspmv_stream_t stream, int debug_sync);
 
+/* ---- extension: the sparse triangular solve  op(A) x = alpha * b  for one right-hand side, level-scheduled (csrc/mspmv_csrsv.hip;
+ * what rocsparse_csrsv / rocsparse_spsv is in rocSPARSE): L x = b and U x = b for ILU and IC factors, the forward and backward
+ * sweeps of Gauss-Seidel and SOR on A itself.
+ * INPUTS: A is rows x rows in CSR.  uplo chooses the triangle, diag the diagonal.  Entries of the other triangle are IGNORED: a full
+ * matrix may be passed and swept with its lower and its upper part, nothing extracted.  With MSPMV_CSRSV_UNIT stored diagonal
+ * entries are ignored too.  Rows need not be sorted; a column repeated inside the strict triangle is simply two products; empty rows
+ * may sit anywhere.  L^T x = b is mspmv_csr_transpose_* followed by an UPPER solve.
+ * THE PLAN is an opaque handle that OWNS ITS STORAGE (like mspmv_mg_plan_t, the one other place where the library allocates): the
+ * host must know a launch schedule that depends on the pattern.  mspmv_csrsv_plan_create ALLOCATES (hipMalloc: scratch for the
+ * analysis, freed before it returns; order[] and level_offsets[], kept until mspmv_csrsv_plan_destroy), is SYNCHRONOUS, and reads
+ * a few bytes back from the device per step, as mspmv_csrmv_hotcols_skew does.  It depends on the PATTERN ALONE: new values on the
+ * same pattern (a refactorisation) need no new plan.  It computes, for the chosen triangle,
+ *     level[r] = 0 for a row without strict-triangle entries, else 1 + max(level[c]) over them,
+ * order[] = the rows sorted stably by level (ascending row inside a level, for UPPER too) and level_offsets[] (levels + 1 entries):
+ * both functions of the pattern alone.  bad_diagonal_row is found here (NON_UNIT: the smallest row with no or with more than one
+ * stored diagonal entry; a solve on such a plan is refused).  A numerically zero diagonal is NOT detected: the division yields
+ * the IEEE inf or NaN.
+ * VALUES, defined bit for bit in the value type, for row r:
+ *     s = +0.0;  for every stored entry e of row r in stored order whose column c is in the strict triangle:  s = s + a[e] * x[c]
+ *     t = alpha * b[r]
+ *     x[r] = (t - s) / d     (NON_UNIT; d = the row's one stored diagonal value)          x[r] = t - s     (UNIT)
+ * every multiply, add and the correctly rounded division rounded on its own (no fused multiply-add), nothing flushed to zero.  So
+ * x[r] is a function of the row's entries, the x of its dependencies, alpha and b[r] alone -- not of levels, segment cuts,
+ * alignment or the kernel that ran.  ONE LANE adds one row's sum: a row of L strict entries costs L serial multiply-adds (as in
+ * mspmv_csr_sum_duplicates_*); factors and sweeps have rows of tens of entries.
+ * SCHEDULE: a level of at most W = info.narrow_rows rows is narrow.  A maximal run of consecutive narrow levels is one segment: ONE
+ * launch of ONE workgroup that walks its levels with a workgroup barrier between them.  Every other level is a segment of its own:
+ * one launch of as many workgroups as its rows need.  info.launches is the number of segments, a function of the pattern alone.
+ * Nothing else orders two levels: no flags, no spinning, no cooperative launch, no workgroup that depends on another's progress.
+ * A solve allocates nothing, reads nothing back, launches the same kernels whatever the values and can be captured in a graph.
+ * d_x == d_b (in place) is allowed; any other overlap is not.  The matrix arrays and b are not modified.  The arrays passed to a
+ * solve hold the pattern the plan was made from.
+ * Asynchronous on `stream` (the solve); debug_sync prints one line per launch and waits for it; returns 0 or a hipError_t; column
+ * indices lie in [0, rows), not checked, as everywhere.
+ * LIMITS, refused before anything is launched: rows, nnz >= 0; rows + nnz <= 2^31 - 65537; uplo, diag in {0, 1}; NULL arrays with
+ * nnz > 0; a NULL plan; a solve on a plan whose bad_diagonal_row >= 0.  rows == 0 gives a valid plan with 0 levels and 0 launches
+ * (no device is touched).  nnz == 0 with UNIT gives x = alpha * b in one level (the matrix arrays may be NULL).
+ * Measured on MI355X against rocsparse_spsv (analysis outside the solve timing; profiles/csrsv_bench.txt; DESIGN.md 4 "Triangular
+ * solve"), fp64 solve / analysis: the lower part of a 5-point grid of 2000 x 2000 16.4 / 38 ms against 91 / 82 ms; the ILU(0)
+ * pattern of a 7-point grid of 128^3 2.12 / 12 ms against 44.7 / 24 ms; a bidiagonal chain of 2^16 rows 49 / 70 ms against 84 / 12 ms;
+ * the strict lower triangle of an R-MAT graph of scale 20 (rows of tens of thousands of entries, one lane each) 259 / 78 ms against
+ * 18.8 / 13 ms: rocSPARSE is 14 times faster there.  W = 256 by the sweep on the two grids. ---- */
+#define MSPMV_CSRSV_LOWER 0
+#define MSPMV_CSRSV_UPPER 1
+#define MSPMV_CSRSV_NON_UNIT 0
+#define MSPMV_CSRSV_UNIT 1
+typedef struct mspmv_csrsv_plan mspmv_csrsv_plan_t;
+typedef struct mspmv_csrsv_info {
+    int32_t rows, nnz, uplo, diag;
+    int32_t levels;            /* number of levels (0 for rows == 0)                                  */
+    int32_t launches;          /* kernels ONE solve launches: a function of the pattern alone         */
+    int32_t narrow_rows;       /* W: a level of <= W rows is "narrow" (above)                         */
+    int32_t max_level_rows;
+    int32_t bad_diagonal_row;  /* NON_UNIT: smallest row with no or more than one stored diagonal; -1 */
+    int64_t used_entries;      /* entries of the strict triangle                                      */
+    uint64_t device_bytes;     /* what the plan holds on the device                                   */
+} mspmv_csrsv_info_t;
+int mspmv_csrsv_plan_create(mspmv_csrsv_plan_t **plan, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                            int32_t rows, int32_t nnz, int32_t uplo, int32_t diag, mspmv_stream_t stream, int debug_sync);
+int mspmv_csrsv_plan_info(const mspmv_csrsv_plan_t *plan, mspmv_csrsv_info_t *info);
+const int32_t *mspmv_csrsv_plan_order(const mspmv_csrsv_plan_t *plan);          /* device, rows entries       */
+const int32_t *mspmv_csrsv_plan_level_offsets(const mspmv_csrsv_plan_t *plan);  /* device, levels + 1 entries */
+int mspmv_csrsv_solve_f32(mspmv_csrsv_plan_t *plan, const float *d_values, const int32_t *d_row_offsets,
+                          const int32_t *d_column_indices, float alpha, const float *d_b, float *d_x,
+                          mspmv_stream_t stream, int debug_sync);
+int mspmv_csrsv_solve_f64(mspmv_csrsv_plan_t *plan, const double *d_values, const int32_t *d_row_offsets,
+                          const int32_t *d_column_indices, double alpha, const double *d_b, double *d_x,
+                          mspmv_stream_t stream, int debug_sync);
+int mspmv_csrsv_plan_destroy(mspmv_csrsv_plan_t *plan);
+
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */
 typedef struct mspmv_launch_info {

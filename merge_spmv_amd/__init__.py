@@ -18,7 +18,7 @@ import os
 from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
-           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm",
+           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -59,6 +59,13 @@ def use_library(kind: str = "product") -> str:
 
 def active_library() -> str:
     return _active
+
+
+class _CsrSvInfo(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int32), ("nnz", ctypes.c_int32), ("uplo", ctypes.c_int32), ("diag", ctypes.c_int32),
+                ("levels", ctypes.c_int32), ("launches", ctypes.c_int32), ("narrow_rows", ctypes.c_int32),
+                ("max_level_rows", ctypes.c_int32), ("bad_diagonal_row", ctypes.c_int32), ("used_entries", ctypes.c_int64),
+                ("device_bytes", ctypes.c_uint64)]
 
 
 class _LaunchInfo(ctypes.Structure):
@@ -195,6 +202,19 @@ def load_library() -> ctypes.CDLL:
         fn = getattr(lib, "mspmv_sddmm_" + name)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, ct, ct, vp, ctypes.c_int]
+    lib.mspmv_csrsv_plan_create.restype = ctypes.c_int
+    lib.mspmv_csrsv_plan_create.argtypes = [ctypes.POINTER(vp), vp, vp, i32, i32, i32, i32, vp, ctypes.c_int]
+    lib.mspmv_csrsv_plan_info.restype = ctypes.c_int
+    lib.mspmv_csrsv_plan_info.argtypes = [vp, ctypes.POINTER(_CsrSvInfo)]
+    for name in ("mspmv_csrsv_plan_order", "mspmv_csrsv_plan_level_offsets"):
+        getattr(lib, name).restype = vp
+        getattr(lib, name).argtypes = [vp]
+    for name, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        fn = getattr(lib, "mspmv_csrsv_solve_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, ct, vp, vp, vp, ctypes.c_int]
+    lib.mspmv_csrsv_plan_destroy.restype = ctypes.c_int
+    lib.mspmv_csrsv_plan_destroy.argtypes = [vp]
     lib.mspmv_csr_gemm_products.restype = ctypes.c_int
     lib.mspmv_csr_gemm_products.argtypes = [vp, sz_p, vp, vp, i32, i32, i32, vp, i32, vp, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_skew.restype = ctypes.c_int
@@ -1067,6 +1087,121 @@ def sddmm(row_offsets, column_indices, U, V, out=None, alpha: float = 1.0, beta:
     _check(int(fn(_ptr(row_offsets), _ptr(column_indices), _ptr(U), int(ldu), _ptr(V), int(ldv), _ptr(out), rows, cols, nnz, k,
                   ct(alpha), ct(beta), _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_sddmm")
     return out
+
+
+class _PlanArray:
+    """plan-owned device memory seen by torch (torch.as_tensor reads __cuda_array_interface__: no copy)"""
+
+    def __init__(self, ptr: int, count: int):
+        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "<i4", "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+class CsrSv:
+    """The level-scheduled sparse triangular solve (mspmv_csrsv_*): op(A) x = alpha * b for one right-hand side.  The constructor
+    analyses the PATTERN (synchronous; the plan owns what it allocates); `solve` runs on any values with that pattern.  `lower`
+    chooses the triangle, `unit_diagonal` the diagonal; entries of the other triangle (and, with a unit diagonal, stored diagonals) are
+    ignored, so a full matrix may be swept with both of its parts.  include/mspmv.h states the bits of x.
+    .info: the plan's figures (levels, launches, narrow_rows, bad_diagonal_row, ...); .order: the rows sorted stably by level;
+    .level_offsets: levels + 1 entries (both int32 tensors on the matrix's device, copies)."""
+
+    def __init__(self, row_offsets, column_indices, lower: bool = True, unit_diagonal: bool = False, stream=None,
+                 debug_synchronous: bool = False):
+        import torch
+        self._handle = None
+        for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices")):
+            if not isinstance(t, torch.Tensor):
+                raise MspmvError(f"CsrSv: {name} must be a tensor")
+        if not (row_offsets.is_cuda and column_indices.is_cuda):
+            raise MspmvError("CsrSv needs CUDA (HIP) tensors: the kernels only run on the GPU")
+        if row_offsets.dtype != torch.int32 or column_indices.dtype != torch.int32:
+            raise TypeError("CsrSv: row_offsets / column_indices must be int32")
+        if row_offsets.dim() != 1 or row_offsets.numel() < 1 or not row_offsets.is_contiguous() or column_indices.dim() != 1 \
+                or not column_indices.is_contiguous() or column_indices.device != row_offsets.device:
+            raise MspmvError("CsrSv: row_offsets (rows + 1 entries) and column_indices must be contiguous 1-D tensors on one device")
+        self.device = row_offsets.device
+        self.rows, self.nnz = row_offsets.numel() - 1, column_indices.numel()
+        self.row_offsets, self.column_indices = row_offsets, column_indices
+        self._lib = load_library()
+        handle = ctypes.c_void_p(0)
+        with torch.cuda.device(self.device):
+            _check(self._lib.mspmv_csrsv_plan_create(ctypes.byref(handle), _ptr(row_offsets), _ptr(column_indices), self.rows, self.nnz,
+                                                     0 if lower else 1, 1 if unit_diagonal else 0, _stream_handle(stream),
+                                                     int(bool(debug_synchronous))), "mspmv_csrsv_plan_create")
+        self._handle = handle
+        raw = _CsrSvInfo()
+        _check(self._lib.mspmv_csrsv_plan_info(self._handle, ctypes.byref(raw)), "mspmv_csrsv_plan_info")
+        self.info = {name: int(getattr(raw, name)) for name, _ in _CsrSvInfo._fields_}
+
+    def _array(self, fn, count):
+        import torch
+        if self._handle is None:
+            raise MspmvError("CsrSv: the plan is closed")
+        ptr = fn(self._handle)
+        if not ptr or count == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device)
+        return torch.as_tensor(_PlanArray(ptr, count), device=self.device).clone()
+
+    @property
+    def order(self):
+        return self._array(self._lib.mspmv_csrsv_plan_order, self.rows)
+
+    @property
+    def level_offsets(self):
+        import torch
+        if self.rows == 0:                                         # (a plan of no rows holds nothing on the device)
+            return torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._array(self._lib.mspmv_csrsv_plan_level_offsets, self.info["levels"] + 1)
+
+    def solve(self, values, b, x=None, alpha: float = 1.0, stream=None, debug_synchronous: bool = False):
+        """x = the solution of op(A) x = alpha * b on `values` (the plan's pattern); x may be b (in place).  Asynchronous on `stream`;
+        info["launches"] launches, nothing allocated but a missing x, nothing read back."""
+        import torch
+        if self._handle is None:
+            raise MspmvError("CsrSv: the plan is closed")
+        for t, name in ((values, "values"), (b, "b")):
+            if not isinstance(t, torch.Tensor):
+                raise MspmvError(f"CsrSv.solve: {name} must be a tensor")
+        if not (values.is_cuda and b.is_cuda):
+            raise MspmvError("CsrSv.solve needs CUDA (HIP) tensors: the kernels only run on the GPU")
+        if b.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"CsrSv.solve is instantiated for float32 and float64, got {b.dtype}")
+        if values.dtype != b.dtype:
+            raise TypeError(f"CsrSv.solve: values hold {values.dtype}, b {b.dtype}")
+        if x is None:
+            x = torch.empty(self.rows, dtype=b.dtype, device=self.device)
+        if not isinstance(x, torch.Tensor) or x.dtype != b.dtype:
+            raise TypeError(f"CsrSv.solve: x must be a {b.dtype} tensor")
+        for t, name, need in ((values, "values", self.nnz), (b, "b", self.rows), (x, "x", self.rows)):
+            if t.device != self.device or t.dim() != 1 or not t.is_contiguous() or t.numel() != need:
+                raise MspmvError(f"CsrSv.solve: {name} must be a contiguous 1-D tensor of {need} entries on {self.device}")
+        if self.info["bad_diagonal_row"] >= 0:
+            raise MspmvError(f"CsrSv.solve: row {self.info['bad_diagonal_row']} has no or more than one stored diagonal entry")
+        fn, ct = (self._lib.mspmv_csrsv_solve_f32, ctypes.c_float) if b.dtype == torch.float32 else (self._lib.mspmv_csrsv_solve_f64, ctypes.c_double)
+        _check(int(fn(self._handle, _ptr(values), _ptr(self.row_offsets), _ptr(self.column_indices), ct(alpha), _ptr(b), _ptr(x),
+                      _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_csrsv_solve")
+        return x
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None:
+            handle, self._handle = self._handle, None
+            self._lib.mspmv_csrsv_plan_destroy(handle)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csrsv(values, row_offsets, column_indices, b, lower: bool = True, unit_diagonal: bool = False, alpha: float = 1.0):
+    """One-shot triangular solve: analyse the pattern, solve op(A) x = alpha * b, drop the plan.  A loop keeps a CsrSv."""
+    plan = CsrSv(row_offsets, column_indices, lower=lower, unit_diagonal=unit_diagonal)
+    try:
+        return plan.solve(values, b, alpha=alpha)
+    finally:
+        import torch
+        torch.cuda.current_stream(plan.device).synchronize()
+        plan.close()
 
 
 class CsrMVPlan:
