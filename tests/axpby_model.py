@@ -15,10 +15,19 @@ negative alpha and +0.0 otherwise; where t is -0.0 and non-zero products cancel,
 corner is undefined, zero_problem never draws it and model() asserts that.  test_axpby_model.py shows by brute force that the
 rule does not depend on cuts, association or the order of the carries.
 
+WIDE.  integer_problem's numbers sit at the bottom of that budget: every product, sum, carry and result is an integer below about
+2^21, so the low 32 bits of every fp64 number on the way are zero and alpha, beta are fp32 (and bf16) numbers -- half of a double, or
+a scalar narrowed to float, could be lost without one bit of any result changing.  wide_problem draws the same structure with ODD
+magnitudes that fill the budget (LIMIT // 2 // 8 per row: the 8 is the largest |alpha| / g + |beta| / g of PAIRS), so the lowest used
+bit of every input is a one and sums, carries and results carry bits in both halves; low_half() / low_half_share() /
+carry_low_half_shares() say how much of a problem's results and of a long row's running sums do.  WIDE_PAIRS are scalars that are
+no fp32 (no bf16, no fp16) numbers; their granule is 2^-30 (2^-12), so they run on the narrow draw, where the bound allows them.
+
 SCALES.  scaled() multiplies values and x by powers of two; the model's result is the exact ldexp of its int64 units.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from fractions import Fraction
 
@@ -28,6 +37,13 @@ import numpy as np
 PAIRS = [(1, 0), (2, 0), (-0.5, 3), (-1.5, 0.5), (1, 1), (2.5, -1), (0, -2), (3, -5)]
 
 LIMIT = {np.dtype(np.float32): 1 << 24, np.dtype(np.float64): 1 << 53}
+
+# scalars that fill the significand: no number here is an fp32 number (fp64) / a bf16 or fp16 number (fp32)
+WIDE_PAIRS = {np.dtype(np.float64): [(1 + 2.0 ** -30, 0), (-(1 + 2.0 ** -29), 1 + 2.0 ** -30)],
+              np.dtype(np.float32): [(1 + 2.0 ** -12, 0), (-(1 + 2.0 ** -11), 1 + 2.0 ** -12)]}
+WIDE_XMAX = {np.dtype(np.float32): 1 << 8, np.dtype(np.float64): 1 << 20}
+LOW_BITS = {np.dtype(np.float32): 16, np.dtype(np.float64): 32}        # the "low half" of a number's bit pattern
+CARRY_STRIDES = (256 * 7, 256 * 11)                                      # the two tile sizes: where a long row's running sum is cut
 
 
 @dataclass
@@ -63,6 +79,72 @@ def integer_problem(rng, rows, cols, lens, dtype, vmax=2, xmax=3, ymax=8):
     return csr, _signed(rng, cols, xmax, dtype), _signed(rng, rows, ymax, dtype)
 
 
+def _odd(rng, hi):
+    """odd integers from +-[1, hi], hi an array (or a size-1 array broadcast by the caller): never zero, the lowest bit a one"""
+    hi = np.asarray(hi, np.int64)
+    assert (hi >= 1).all()
+    return (2 * rng.integers(0, (hi + 1) // 2) + 1) * (2 * rng.integers(0, 2, size=hi.shape) - 1)
+
+
+def wide_budget(dtype) -> int:
+    """what sum |v*x| of a row and |y0| may reach: with |alpha| / g + |beta| / g <= 8 (PAIRS) the quotient stays below LIMIT / 2"""
+    return LIMIT[np.dtype(dtype)] // 2 // 8
+
+
+def wide_problem(rng, rows, cols, lens, dtype, vcap=None):
+    """integer_problem's structure with magnitudes that FILL the exactness budget B = wide_budget(dtype):
+      x       odd integers from +-[1, xmax], xmax = min(2^20 (fp64) | 2^8 (fp32), isqrt(B // longest row));
+      values  of a row of n entries: odd integers of magnitude in [1, max(1, B // (n * xmax))] (vcap: a further cap on it), signed
+              by the sign of their x so that THREE PRODUCTS IN FOUR ARE POSITIVE -- with even odds a long row's sums stay near
+              sqrt(n) products, and in fp32 a row of thousands of entries would leave the low half empty;
+      y0      odd integers from +-[1, B].
+    Then sum |v*x| <= B for every row of at most B entries.  A longer row (fp32 only) has values and x of +-1, and whether the
+    bound holds depends on the pair: model() asserts it.  Returns (csr, x, y0)."""
+    dtype = np.dtype(dtype)
+    lens = np.asarray(lens, np.int64)
+    csr, _, _ = integer_problem(rng, rows, cols, lens, dtype.type, vmax=1)
+    budget = wide_budget(dtype)
+    longest = max(int(lens.max(initial=0)), 1)
+    xmax = max(1, min(WIDE_XMAX[dtype], math.isqrt(budget // longest)))
+    vhi = np.maximum(1, budget // (np.maximum(lens, 1) * xmax))
+    if vcap is not None:                            # (values a narrower stored type holds: tests/test_mixed_precision.py)
+        vhi = np.minimum(vhi, vcap)
+    x = _odd(rng, np.full(cols, xmax))
+    val = np.abs(_odd(rng, np.repeat(vhi, lens))) * np.sign(x)[csr.column_indices] * np.where(rng.random(csr.nnz) < 0.75, 1, -1)
+    val, x = val.astype(dtype), x.astype(dtype)
+    y0 = _odd(rng, np.full(rows, budget)).astype(dtype)
+    return Csr(csr.rows, csr.cols, csr.row_offsets, csr.column_indices, val), x, y0
+
+
+def low_half(a) -> np.ndarray:
+    """the low 32 (fp64) / 16 (fp32) bits of each number's bit pattern"""
+    a = np.ascontiguousarray(a)
+    return bits(a) & ((1 << LOW_BITS[a.dtype]) - 1)
+
+
+def low_half_share(csr, y) -> float:
+    """the share of the rows with entries whose y has a non-zero low half (1.0 for a matrix without entries)"""
+    has = np.diff(csr.row_offsets.astype(np.int64)) > 0
+    return float((low_half(y)[has] != 0).mean()) if has.any() else 1.0
+
+
+def carry_low_half_shares(csr, x, strides=CARRY_STRIDES):
+    """for every row longer than min(strides): (row, the number of its running sums v*x taken after every stride-th entry, for each
+    stride -- what carries, records and folded carries of the row are made of --, the share of them with a non-zero low half as
+    numbers of the values' type)"""
+    dtype = np.dtype(csr.values.dtype)
+    off = csr.row_offsets.astype(np.int64)
+    prod = _exact_int(csr.values, "values") * _exact_int(x, "x")[csr.column_indices]
+    out = []
+    for r in np.flatnonzero(np.diff(off) > min(strides)):
+        n = int(off[r + 1] - off[r])
+        at = np.concatenate([np.arange(s, n, s) for s in strides])
+        sums = np.cumsum(prod[off[r]:off[r + 1]])[at - 1]      # (a running sum of THIS row: nothing of other rows to wrap round)
+        assert (np.abs(sums) < LIMIT[dtype]).all()
+        out.append((int(r), at.size, float((low_half(sums.astype(dtype)) != 0).mean())))
+    return out
+
+
 def granule(alpha, beta) -> Fraction:
     """the largest g = 2^-k <= 1 that alpha and beta are both multiples of"""
     a, b = Fraction(alpha), Fraction(beta)          # (exact for a float: every float is a dyadic rational)
@@ -78,13 +160,25 @@ def _exact_int(a, what):
     return i
 
 
+def segment_sums(a, off):
+    """the sum of a[off[r] : off[r + 1]] for every r, each row summed ON ITS OWN (np.add.reduceat over the rows with entries).
+    A running sum over the whole array would pass 2^63 -- the wide draw holds sum |v*x| of about 2^47 per row, so after some 10^5
+    rows -- and give the right differences only through two's-complement wraparound."""
+    off = np.asarray(off, np.int64)
+    out = np.zeros(off.size - 1, a.dtype)
+    has = off[1:] > off[:-1]
+    if has.any():
+        out[has] = np.add.reduceat(a, off[:-1][has])     # (rows with entries start where the last such row ended: rows without lie between)
+    return out
+
+
 def row_sums(csr, x):
-    """(sum v*x, sum |v*x|) per row in int64"""
+    """(sum v*x, sum |v*x|) per row in int64; asserts that no row's own sum comes near the int64 range"""
     off = csr.row_offsets.astype(np.int64)
     prod = _exact_int(csr.values, "values") * _exact_int(x, "x")[csr.column_indices]
-    cs = np.concatenate([[0], np.cumsum(prod)])
-    ca = np.concatenate([[0], np.cumsum(np.abs(prod))])
-    return cs[off[1:]] - cs[off[:-1]], ca[off[1:]] - ca[off[:-1]]
+    mag = np.abs(prod)
+    assert float(segment_sums(mag.astype(np.float64), off).max(initial=0)) < 2.0 ** 62, "a row's sum |v*x| does not fit int64"
+    return segment_sums(prod, off), segment_sums(mag, off)
 
 
 def quotient(csr, x, y0, alpha, beta) -> int:

@@ -4,7 +4,9 @@ owner's mailbox through hipIpc-opened memory, step tags instead of collectives -
 producer may run ahead: exercises the two-slot credit), then iterated SpMV with the row all-gather.  Rank 0 checks every
 row against the oracle and prints IPC-OK.  Kind `exact`: integer data (tests/axpby_model.py), a giant row spanning every rank plus
 ordinary rows (4 ranks: the two middle ones own nothing); rank 0 also compares the gathered y of the repeated steps with the int64
-model ON THE BITS."""
+model ON THE BITS.  Kind `wide`: the same shape on tests/axpby_model.wide_problem (mg_model.ipc_wide_problem) -- odd integers that fill
+the exactness budget, so the carries of the giant row, which this backend ships as two tagged 32-bit halves, have a non-zero low
+word --, the same comparison on the bits."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,7 +27,7 @@ if kind == "giant":                                     # one row spanning every
     lens = rng.integers(0, 4, rows); lens[rows // 2] = 900000
 elif kind == "short":
     lens = rng.integers(0, 12, rows)
-elif kind == "exact":                                   # longest row 200 000: sum |v x| <= 1.2e6 < 2^24, exact in fp32 too
+elif kind in ("exact", "wide"):                         # longest row 200 000: sum |v x| <= 1.2e6 < 2^24, exact in fp32 too
     lens = rng.integers(0, 4, rows); lens[rows // 2] = 200000
 else:                                                   # empty parts in the middle of a giant row + ordinary rows
     lens = np.zeros(rows, np.int64); lens[10] = 700000; lens[rows - 5:] = 7
@@ -40,9 +42,18 @@ if kind == "exact":
     ic, x0, _ = AM.integer_problem(rng, rows, rows, lens, dtype)
     col, val = ic.column_indices, ic.values
     exact = AM.model(ic, x0, None, 1, 0)                # asserts the exactness bound
+if kind == "wide":
+    import axpby_model as AM
+    import mg_model as MM
+    wide_lens, ic, x0 = MM.ipc_wide_problem(dtype)
+    assert np.array_equal(wide_lens, lens)              # the shape of `exact`
+    col, val = ic.column_indices, ic.values
+    exact = AM.model(ic, x0, None, 1, 0)                # asserts the exactness bound
+    carries, share = MM.wide_open_row_share(ic, x0, world)
+    assert carries == world - 1 and (prec == "f32" or share == 1.0), (carries, share)      # every carry handed on has a low word
 csr = O.Csr(rows, rows, off.astype(np.int32), col, val)
 row_split, nz_split = MG.partition(off, world)
-if kind == "exact":
+if kind in ("exact", "wide"):
     owned = np.diff(row_split)
     assert world < 4 or (owned[1:-1] == 0).all(), owned    # the middle ranks sit inside the giant row
     assert owned[0] > 0 and owned[-1] > 0

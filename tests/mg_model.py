@@ -147,6 +147,43 @@ def integer_problem(name, dtype):
     return csr, x
 
 
+WIDE_PARTS = [2, 7, 64]
+# the shapes the wide draw runs on: a boundary row shared by several parts (the giants, single_row), rows cut by most boundaries
+# (short, power_law), and every cut on a row end
+WIDE_NAMES = ["giant_middle", "giant_first", "giant_last", "giant_then_empty_rows", "single_row", "short", "power_law", "cuts_on_row_ends"]
+
+
+def wide_problem(name, dtype):
+    """(csr, x): axpby_model.wide_problem -- odd integers that fill the exactness budget, so that every part's sums, its open-row
+    entry and the folded carries hold bits in both halves of a double (in the low 16 bits of a float)"""
+    import axpby_model as AM
+    rows, cols, lens = shape(name)
+    csr, x, _ = AM.wide_problem(np.random.default_rng(_seed(name) + 3), rows, cols, lens, dtype)
+    return csr, x
+
+
+IPC_ROWS, IPC_GIANT = 30000, 200_000
+
+
+def ipc_wide_problem(dtype):
+    """(lens, csr, x) of kind `wide` of tests/mg_ipc_worker.py: the shape of its kind `exact` -- rows of 0 .. 3 entries and one row
+    of 200 000 in the middle, which spans every rank -- on axpby_model.wide_problem.  Here, not in the worker, so that
+    tests/test_mg_model.py can check the data on the CPU."""
+    import axpby_model as AM
+    lens = np.random.default_rng(1234).integers(0, 4, IPC_ROWS); lens[IPC_ROWS // 2] = IPC_GIANT      # (the worker's first draw)
+    csr, x, _ = AM.wide_problem(np.random.default_rng(1235), IPC_ROWS, IPC_ROWS, lens, dtype)
+    return lens, csr, x
+
+
+def wide_open_row_share(csr, x, parts):
+    """(the open-row entries that are not zero, the share of them with a non-zero low half): what the fold adds"""
+    import axpby_model as AM
+    row_split, nz_split = partition(csr.row_offsets.astype(np.int64), parts)
+    opens = np.array([AM.row_sums(local_csr(csr, row_split, nz_split, g), x)[0][-1] for g in range(parts)], np.int64)
+    opens = opens[opens != 0].astype(csr.values.dtype)
+    return opens.size, (float((AM.low_half(opens) != 0).mean()) if opens.size else 1.0)
+
+
 def float_problem(name, dtype, scale=1.0):
     """(csr, x): values and x uniform in (-1, 1) (values times `scale`): sums round, the association matters"""
     rows, cols, lens = shape(name)

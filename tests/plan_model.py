@@ -16,6 +16,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+import axpby_model as AM
+
 ALPHA_BETA = ((1.0, 0.0), (-2.0, 0.0), (-0.5, 3.0), (0.0, 2.0))
 EXACT_BOUND = 1 << 22
 SKEW_WINDOWS, SKEW_WINDOW = 512, 2048
@@ -126,6 +128,57 @@ def exact_case(rng, structure: Csr, cap: int = 4) -> ExactCase:
         worst = max(1.0, abs(alpha)) * s_abs + abs(beta) * np.abs(y0)
         assert worst.size == 0 or worst.max() <= EXACT_BOUND, (alpha, beta, float(worst.max()))
     return ExactCase(a, x, y0, product_int(a, x))
+
+
+# the wide rule is tests/axpby_model.py's: its limits, its cap on x, its budget, its odd draw and its scalars, by precision name
+NPDT = {"f32": np.dtype(np.float32), "f64": np.dtype(np.float64)}
+WIDE_LIMIT = {p: AM.LIMIT[d] for p, d in NPDT.items()}
+# alpha, beta that fill the significand: no number here is an fp32 number (f64) / a bf16 or fp16 number (f32); granule 2^-30 (2^-12)
+WIDE_SCALARS = {p: tuple((float(a), float(b)) for a, b in AM.WIDE_PAIRS[d]) for p, d in NPDT.items()}
+
+
+def fits_wide_scalars(case: ExactCase, prec: str) -> bool:
+    """whether y = alpha A x + beta y0 is exact in any association for the pairs of WIDE_SCALARS[prec]: in granules,
+    |alpha| sum |a x| + |beta| |y0| < 2^24 (2^53) on every row (then ExactCase.want, computed in float64, is exact as well)"""
+    v = np.asarray(case.a.values).astype(np.int64)
+    s_abs = np.zeros(case.a.rows, np.int64)
+    np.add.at(s_abs, case.a.row_of_entry(), np.abs(v * case.x[case.a.column_indices]))
+    g = 1 << (30 if prec == "f64" else 12)
+    worst = (g + 2) * s_abs + (g + 1) * np.abs(case.y0)
+    return bool(worst.size == 0 or worst.max() < WIDE_LIMIT[prec])
+
+
+def wide_case(rng, structure: Csr, prec: str) -> ExactCase:
+    """exact_case with magnitudes that FILL the exactness budget of the precision instead of sitting at its bottom, drawn by
+    tests/axpby_model.wide_problem (B = 2^24 (2^53) // 2 // 8; x odd integers up to xmax = min(2^8 (2^20), isqrt(B // longest row)),
+    the values of a row of n entries odd integers up to max(1, B // (n * xmax)), three products in four positive, y0 odd integers
+    up to B) and laid over `structure`.  Every number has a one in its lowest used bit, and sums, every band's partial sums and results carry
+    bits in both halves of a double.  Asserts |alpha| / g * sum |a x| + |beta| / g * |y0| < 2^24 (2^53) per row for ALPHA_BETA, g the
+    granule 1/2 of alpha = -0.5."""
+    lens = np.diff(structure.row_offsets)
+    col = structure.column_indices
+    # (wide_problem draws a structure of its own first; its values follow that structure's row lengths, and are signed here by the
+    #  x of THIS structure's columns)
+    drawn, x, y0 = AM.wide_problem(rng, structure.rows, structure.cols, lens, NPDT[prec])
+    x, y0 = x.astype(np.int64), y0.astype(np.int64)
+    val = np.abs(drawn.values.astype(np.int64)) * np.sign(x)[col] * np.where(rng.random(col.size) < 0.75, 1, -1)
+    a = Csr(structure.rows, structure.cols, structure.row_offsets, col, val.astype(np.float64))
+    s_abs = np.zeros(a.rows, np.int64)
+    np.add.at(s_abs, a.row_of_entry(), np.abs(val * x[col]))
+    for alpha, beta in ALPHA_BETA:
+        worst = int(2 * abs(alpha)) * s_abs + int(2 * abs(beta)) * np.abs(y0)              # in halves
+        assert worst.size == 0 or worst.max() < WIDE_LIMIT[prec], (alpha, beta, int(worst.max()))
+    return ExactCase(a, x.astype(np.int64), y0.astype(np.int64), product_int(a, x))
+
+
+def low_half_share(numbers, prec: str, among=None) -> float:
+    """the share of `numbers` (integers, exact in the precision) whose bit pattern in the precision has a non-zero low half (low 32
+    bits of a double, low 16 of a float); among: a mask of the ones that count (1.0 when none does)"""
+    f = np.asarray(numbers).astype(np.float32 if prec == "f32" else np.float64)
+    assert np.array_equal(f.astype(np.float64), np.asarray(numbers, np.float64))
+    low = AM.low_half(f)
+    low = low if among is None else low[among]
+    return float((low != 0).mean()) if low.size else 1.0
 
 
 # ---- the sparsity structures of tests/test_plan_exact.py (sorted rows; some depend on the band count) ----

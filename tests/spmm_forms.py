@@ -307,6 +307,7 @@ class Case:
     trim: int = 0            # nonzeros taken off the last row: nnz % 4 = 3 - trim
     pad: int = 0             # > 0: values and column indices start `pad` elements into their allocations (unaligned arrays)
     zeros: bool = False      # the zero-laden data of tests/test_spmm_forms.py (same structure, same launches)
+    wide: bool = False       # the wide data: odd integers that fill the exactness budget (same structure, same launches)
 
     def dims(self):
         s = structure(self.mat)
@@ -384,6 +385,19 @@ def _zero_cases():
 
 
 ZERO_CASES = _zero_cases()
+
+
+def _wide_cases():
+    """per precision one case per form on the wide data: the row-wise kernel, every pack width (alpha = -2, beta = 3), the slot form
+    of 16 and 8 with the packs behind it, two groups of 16 in the slot form; every one but the row-wise sends the giant row, the
+    one-tile rows and the open last row through the carries and the fix-up"""
+    import dataclasses
+    heads = ("mid_rowwise", "mid_packs_axpby", "big_slots_axpby", "big_slot_groups")
+    return [dataclasses.replace(c, name=c.name + "_wide", wide=True) for c in CASES if c.name.startswith(heads)]
+
+
+WIDE_CASES = _wide_cases()
+assert len(WIDE_CASES) == 8
 # NaN / Inf containment: one pack case and one slot case per precision
 CONTAINMENT = [c for c in CASES if c.name.startswith(("mid_packs_axpby", "big_slots_axpby"))]
 # the same four run scaled to both ends of the exponent range and with -0.0 in Y0

@@ -25,6 +25,33 @@ Sensitivity of the zero-laden tests, each a one-line change of csrc/mspmv_kernel
     same arithmetic): 198 zero-laden tests fail (the compact front end and the general kernel on 64 of 68 shapes, 69 path tests,
     32 tile shapes, the planted rows, prepared calls, tiny x, the deep fix-ups, the mixed calls) and 2 of test_plan_exact.py.
 
+WIDE.  The draws above hold integers below about 2^21: the low 32 bits of every fp64 product, sum, carry and result are zero, and
+every alpha and beta is an fp32 (and a bf16) number.  So every test that runs a dispatch path runs a third data kind as well,
+axpby_model.wide_problem -- odd integers that fill the exactness budget, (1, 0), (-1.5, 0.5) and (-0.5, 0), the plain call included
+--, and the path table and the prepared calls run alpha, beta = 1 + 2^-30, -(1 + 2^-29) (fp32: 1 + 2^-12, -(1 + 2^-11)) on the narrow
+draw wherever the model's bound admits them (Problem.wide_scalars: computed, not listed; the plain mspmv_csrmv_* entry point takes
+no alpha or beta, so it has no scalars to widen and runs the wide DATA instead).  WUSED lists the wide problems;
+tests/test_axpby_model.py asserts on the CPU that at least 95 % of their results, and in fp64 at least 90 % of the running sums of
+every row longer than a tile taken at every 1792nd and 2816th entry, have a non-zero low half.
+
+Sensitivity of the wide data, each a one-line change of the fp64 instantiations built once and run once on one MI355X against the
+parent commit's test_axpby_exact.py, test_spmm_forms.py, test_forward_progress.py, test_plan_exact.py and test_mixed_precision.py
+and against this commit's (failing tests: parent's files / these files; the unchanged library passes all):
+  * lb_publish handing rec_store p0 = 0: 147 / 161.  p0 is the HIGH word of the double: the sum is gone, and the parent sees it.
+  * the same with p1 = 0, the LOW word: 48 / 116 (this file 10 / 64, test_plan_exact.py 0 / 7).  What the parent sees it with: the
+    draws scaled to the smallest subnormal, whose integers then sit in the low word -- they run on the path table and the deep
+    fix-ups only -- and the tolerance tests on real data (2^-21 of a carry is far outside the strict bound).
+  * the carries read by fixup_kernel and fixup_onepass_kernel passed through (float): 125 / 253 (this file 35 / 160); the parent
+    again by the flush of the subnormal draws and on real data.
+  * alpha passed through (float) in csrmv_call<double>: 0 / 1.  Only the plans call it, and with more than one band alpha is applied
+    by the fold: test_plan_exact.py::test_plans_are_exact_with_scalars_that_fill_the_significand[f64-1] fails.  The same cast where
+    the entry points fill Params (csrmv_call_mv): 0 / 200 -- 187 path tests and 12 prepared ones of this file, 1 of test_plan_exact.py.
+  * the column-band passes' `c.value += carry_out->value` with the low 8 bits of the double cleared: 0 / 6
+    (test_forced_band_passes_equal_the_model, fp64, the shapes whose rows cross tiles).
+  (the slot form's carry: tests/test_spmm_forms.py.)
+
+Measured on one MI355X: the 1444 tests of this file take 20.1 s, 15.5 s at the parent commit (the same tests without the wide data).
+
 Forms are forced with the development setters (include/mspmv_dev.h) the way tests/test_gpu_parity.py, test_band_passes.py and
 test_tdm.py force them, and every form a test claims is asserted to have run (launch_info, band_passes, clocked_bands, the launch
 log).  PROBLEMS / USED list every (matrix, pair) of this file: tests/test_axpby_model.py checks the exactness bound on each of them
@@ -184,6 +211,30 @@ CENSUS_MUST = {"planted_zero:": ["kind_ii_crosses:{tile}"], "deep_long_rows:": [
                "deep_one_row:": ["kind_ii_crosses:1792", "kind_ii_crosses:2816"]}
 
 
+# the wide draw (axpby_model.wide_problem): odd magnitudes that fill the exactness budget, so that both halves of every fp64 number
+# on the way -- products, sums, carries, records, results -- hold bits; the pairs it runs with on every dispatch path
+WIDE = "wide"
+WIDE_RUN = [(1, 0), (-1.5, 0.5), NEG_ALPHA_ZERO_BETA]
+# label, precision -> the pairs the wide draw runs (tests/test_axpby_model.py: the bound, the share of results and of running sums
+# of long rows with a non-zero low half)
+WUSED = {}
+
+
+def wuses(labels, pairs=WIDE_RUN, precs=PRECS):
+    for label in labels:
+        assert label in PROBLEMS, label
+        for prec in precs:
+            WUSED.setdefault((label, prec), set()).update(pairs)
+
+
+def uses_wide_scalars(labels, precs=PRECS):
+    """axpby_model.WIDE_PAIRS (alpha, beta no fp32 / no bf16 numbers) on the NARROW draw: their granule is 2^-30 (2^-12), so a row
+    may hold sum |v*x| < 2^22 (< 4095).  Whether a problem qualifies is Problem.fits(), the model's own bound, computed -- not a
+    list kept by hand; tests/test_axpby_model.py checks it and that every group of tests keeps problems that qualify."""
+    for prec in precs:
+        uses(labels, A.WIDE_PAIRS[np.dtype(DT[prec][0])], [prec])
+
+
 def zuses(labels, pairs, precs=PRECS, data=(ZEROS,)):
     for label in labels:
         assert label in PROBLEMS, label
@@ -204,6 +255,9 @@ class Problem:
         if data == "nonzero":
             self.base = A.integer_problem(rng, rows, cols, np.asarray(lens, np.int64), self.dtype, vmax=vmax, xmax=xmax)
             self.csr, self.x, self.y0 = self.base
+        elif data == WIDE:
+            self.base = A.wide_problem(rng, rows, cols, np.asarray(lens, np.int64), self.dtype)
+            self.csr, self.x, self.y0 = self.base
         else:
             # base: the unscaled integers and zeros the model computes on; csr, x, y0: what the device gets
             self.base = A.zero_problem(rng, rows, cols, np.asarray(lens, np.int64), self.dtype, vmax=vmax, xmax=xmax,
@@ -222,6 +276,14 @@ class Problem:
             w.setflags(write=False)
             self._want[(alpha, beta)] = w
         return self._want[(alpha, beta)]
+
+    def fits(self, alpha, beta):
+        """the model's bound for this pair: every row's quotient below 2^24 (2^53) granules"""
+        return A.quotient(*self.base, alpha, beta) < A.LIMIT[np.dtype(self.dtype)]
+
+    def wide_scalars(self):
+        """the pairs of axpby_model.WIDE_PAIRS this problem is exact with (fp32: none where a row's sum |v*x| reaches 4095)"""
+        return [p for p in A.WIDE_PAIRS[np.dtype(self.dtype)] if self.fits(*p)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -295,6 +357,8 @@ def zero_calls(D, pairs, *where, garbage=False):
 # ------------------------------------------------------------------------------------------------- a. every path, every shape
 
 uses(["parity:" + n for n in T.SHAPES], ALL_PAIRS)
+uses_wide_scalars(["parity:" + n for n in T.SHAPES])
+wuses(["parity:" + n for n in T.SHAPES])
 
 
 @pytest.mark.parametrize("shape", sorted(T.SHAPES))
@@ -303,7 +367,8 @@ uses(["parity:" + n for n in T.SHAPES], ALL_PAIRS)
 def test_every_path_equals_the_model(M, shape, prec, path):
     """All 17 dispatch paths of test_gpu_parity.PATHS: the alpha/beta call equals the model for every pair, first call and call on
     hints; (1, 0) through the AXPBY kernels has the bits of the plain call (the two template halves agree).  Exact data make the
-    atomic fix-up order-independent, so it is held to the bits as well."""
+    atomic fix-up order-independent, so it is held to the bits as well.  Then alpha and beta that fill the significand
+    (axpby_model.WIDE_PAIRS, where the rows are short enough for them) and the wide draw, plain call included."""
     P = problem("parity:" + shape, prec)
     try:
         M.set_tuning(P.vb, 0, 0, T.PATHS[path])
@@ -314,11 +379,14 @@ def test_every_path_equals_the_model(M, shape, prec, path):
         plain = D.plain(ws)
         same(plain, P.want(1, 0), shape, prec, path, "plain call on hints")
         same(D.axpby(ws, 1, 0), plain, shape, prec, path, "(1, 0) through the AXPBY kernels against the plain call")
+        both_calls(D, P.wide_scalars(), shape, prec, path, "wide scalars")
+        zero_calls(OnDevice(M, problem("parity:" + shape, prec, WIDE)), WIDE_RUN, shape, prec, path)
     finally:
         M.set_tuning(P.vb)
 
 
 uses(["parity:" + n for n in T.COMPACT_SHAPES], ALL_PAIRS)
+wuses(["parity:" + n for n in T.COMPACT_SHAPES])
 
 
 @pytest.mark.parametrize("shape", sorted(T.COMPACT_SHAPES))
@@ -333,6 +401,7 @@ def test_compact_front_end_and_general_kernel_equal_the_model(M, shape, prec, co
         D = OnDevice(M, P)
         ws = both_calls(D, ALL_PAIRS, shape, prec, compact, garbage=True)
         same(D.plain(ws), P.want(1, 0), shape, prec, compact, "plain call on hints")
+        zero_calls(OnDevice(M, problem("parity:" + shape, prec, WIDE)), WIDE_RUN, shape, prec, compact, garbage=True)
     finally:
         M.set_compact_tiles(0)
 
@@ -342,24 +411,30 @@ def test_compact_front_end_and_general_kernel_equal_the_model(M, shape, prec, co
 PREPARED_SHAPES = ["power_law", "giant_plus_sprinkle", "leading_trailing_empty"]
 PREPARED_FLAGS = {"one_launch_small_shape": 0, "one_launch_large_shape": 16, "classic_small_shape": TWO_LAUNCH, "classic_three_launch": TWO_LAUNCH | 16}
 uses(["parity:" + n for n in PREPARED_SHAPES], ALL_PAIRS)
+uses_wide_scalars(["parity:" + n for n in PREPARED_SHAPES])
+wuses(["parity:" + n for n in PREPARED_SHAPES])
 
 
 @pytest.mark.parametrize("shape", PREPARED_SHAPES)
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("path", sorted(PREPARED_FLAGS))
 def test_prepared_calls_equal_the_model(M, shape, prec, path):
-    """CsrMVWorkspace.prepare + mspmv_csrmv_prepared_*: (1, 0) takes the plain kernels, every other pair the AXPBY set"""
-    P = problem("parity:" + shape, prec)
+    """CsrMVWorkspace.prepare + mspmv_csrmv_prepared_*: (1, 0) takes the plain kernels, every other pair the AXPBY set; the narrow
+    draw with every pair and the wide scalars it is exact with, the wide draw with WIDE_RUN and the plain prepared call"""
+    vb = DT[prec][1]
     try:
-        M.set_tuning(P.vb, 0, 0, PREPARED_FLAGS[path])
-        D = OnDevice(M, P)
-        ws = D.workspace(prepare=True)
-        assert ws.is_prepared_for(D.off, P.csr.rows, P.csr.nnz, D.tdt)          # (csrmv then calls the prepared entry point)
-        for alpha, beta in ALL_PAIRS:
-            for call in ("first", "second"):
-                same(D.axpby(ws, alpha, beta), P.want(alpha, beta), shape, prec, path, (alpha, beta), call + " prepared call")
+        M.set_tuning(vb, 0, 0, PREPARED_FLAGS[path])
+        for P in (problem("parity:" + shape, prec), problem("parity:" + shape, prec, WIDE)):
+            D = OnDevice(M, P)
+            ws = D.workspace(prepare=True)
+            assert ws.is_prepared_for(D.off, P.csr.rows, P.csr.nnz, D.tdt)          # (csrmv then calls the prepared entry point)
+            for alpha, beta in (WIDE_RUN if P.data == WIDE else ALL_PAIRS + P.wide_scalars()):
+                for call in ("first", "second"):
+                    same(D.axpby(ws, alpha, beta), P.want(alpha, beta), shape, prec, path, P.data, (alpha, beta), call + " prepared call")
+            if P.data == WIDE:
+                same(D.plain(ws), P.want(1, 0), shape, prec, path, P.data, "plain prepared call")
     finally:
-        M.set_tuning(P.vb)
+        M.set_tuning(vb)
 
 
 # -------------------------------------------------------------------------------------------- c. tile shapes and alignment
@@ -367,6 +442,7 @@ def test_prepared_calls_equal_the_model(M, shape, prec, path):
 TILE_PAIRS = [(-1.5, 0.5), (2, 0)]
 TILE_FLAGS = [0, 2, 4, 16, 18, 20, 24, 48, 80, 128, 144, 0xF000010, 0x3000010, 0x20000010, 0x10000010, 0x40000000, 0x40000010, 0x4F000010, 0x60000010]
 uses(["tile_grid:7", "tile_grid:11"], TILE_PAIRS)
+wuses(["tile_grid:7", "tile_grid:11"])
 
 
 @pytest.mark.parametrize("vb,block,ipt", [(4, 256, 7), (4, 256, 11), (8, 256, 7), (8, 256, 11)])
@@ -379,12 +455,14 @@ def test_every_compiled_tile_shape_equals_the_model(M, vb, block, ipt, flags):
         info = M.launch_info(P.csr.rows, P.csr.nnz, vb)
         assert (info["block_threads"], info["items_per_thread"], info["flags"]) == (block, ipt, flags)
         both_calls(OnDevice(M, P), TILE_PAIRS, vb, block, ipt, hex(flags))
+        zero_calls(OnDevice(M, problem(f"tile_grid:{ipt}", P.prec, WIDE)), WIDE_RUN, vb, block, ipt, hex(flags))
     finally:
         M.set_tuning(vb)
 
 
 UNALIGNED_PAIRS = [(-1.5, 0.5), (2, 0), (0, -2)]
 uses(["parity:power_law", "parity:one_giant_row"], UNALIGNED_PAIRS)
+wuses(["parity:power_law", "parity:one_giant_row"])
 
 
 @pytest.mark.parametrize("shape", ["power_law", "one_giant_row"])
@@ -402,6 +480,9 @@ def test_unaligned_arrays_equal_the_model(M, shape, prec, flags, capfd):
         log = capfd.readouterr().out
         assert "tile_kernel<<<" in log and "tile_kernel_vec" not in log and "tile_kernel_snap" not in log, log
         both_calls(D, UNALIGNED_PAIRS, shape, prec, flags, "unaligned")
+        W = OnDevice(M, problem("parity:" + shape, prec, WIDE), shift=True)
+        assert all(t.data_ptr() % 16 for t in (W.val, W.off, W.col, W.x))
+        zero_calls(W, WIDE_RUN, shape, prec, flags, "unaligned")
     finally:
         M.set_tuning(P.vb)
 
@@ -413,6 +494,7 @@ DEEP_PATHS = {"multilevel_fix": 0x90, "classic_multilevel_fix": TWO_LAUNCH | 0x9
               "one_launch_records_taken": 16, "one_launch_records_recomputed": 16}
 for _p in PRECS:
     uses([f"deep_one_row:{_p}", f"deep_long_rows:{_p}"], DEEP_PAIRS, [_p])
+    wuses([f"deep_one_row:{_p}", f"deep_long_rows:{_p}"], WIDE_RUN, [_p])
 
 
 @pytest.mark.parametrize("matrix", ["deep_one_row", "deep_long_rows"])
@@ -448,6 +530,16 @@ def test_deep_fixup_and_many_carries_per_row_equal_the_model(M, matrix, prec, pa
             for alpha, beta in DEEP_PAIRS:
                 same(D.axpby(ws, alpha, beta), P.want(alpha, beta), matrix, prec, path, (alpha, beta), "counted call")
             assert episodes() != before, "no tile recomputed a partial sum: the form this case is about did not run"
+        # the wide draw on the same shape, forced form and poll budget: every carry, record and group record of the giant row (of
+        # the long rows) now holds bits in both halves of the double
+        W = OnDevice(M, problem(f"{matrix}:{prec}", prec, WIDE))
+        zero_calls(W, WIDE_RUN, matrix, prec, path)
+        if path == "one_launch_records_recomputed":      # ... and the wide sums too were recomputed, not taken: the counter again
+            ws = W.workspace(); ws.buffer.zero_()
+            before = episodes()
+            for alpha, beta in WIDE_RUN:
+                same(W.axpby(ws, alpha, beta), W.P.want(alpha, beta), matrix, prec, path, WIDE, (alpha, beta), "counted call")
+            assert episodes() != before, "no tile recomputed a partial sum of the wide draw"
     finally:
         M.set_tuning(P.vb); M.set_record_polls(0)
 
@@ -456,6 +548,7 @@ def test_deep_fixup_and_many_carries_per_row_equal_the_model(M, matrix, prec, pa
 
 BAND_SHAPES = ["giant_row", "mostly_empty", "ragged_tail"]
 uses(["tdm:" + n for n in BAND_SHAPES], ALL_PAIRS)
+wuses(["tdm:" + n for n in BAND_SHAPES])
 
 
 def _only_tile_kernel_vec(log):
@@ -478,6 +571,11 @@ def test_forced_band_passes_equal_the_model(M, shape, prec, passes, capfd):
         same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, passes, "logged call")
         assert _only_tile_kernel_vec(capfd.readouterr().out)
         both_calls(D, ALL_PAIRS, shape, prec, passes, "band passes")
+        W = OnDevice(M, problem("tdm:" + shape, prec, WIDE))
+        capfd.readouterr()
+        same(W.axpby(W.workspace(), -1.5, 0.5, debug_synchronous=True), W.P.want(-1.5, 0.5), shape, prec, passes, WIDE, "logged call")
+        assert _only_tile_kernel_vec(capfd.readouterr().out)
+        zero_calls(W, WIDE_RUN, shape, prec, passes, "band passes")
     finally:
         TDM._reset()
 
@@ -501,6 +599,11 @@ def test_clocked_bands_equal_the_model(M, shape, prec, clock, capfd):
         same(D.axpby(D.workspace(), -1.5, 0.5, debug_synchronous=True), P.want(-1.5, 0.5), shape, prec, clock, "logged call")
         assert _only_tile_kernel_vec(capfd.readouterr().out)
         both_calls(D, ALL_PAIRS, shape, prec, clock, "clocked bands")
+        W = OnDevice(M, problem("tdm:" + shape, prec, WIDE))
+        capfd.readouterr()
+        same(W.axpby(W.workspace(), -1.5, 0.5, debug_synchronous=True), W.P.want(-1.5, 0.5), shape, prec, clock, WIDE, "logged call")
+        assert _only_tile_kernel_vec(capfd.readouterr().out)
+        zero_calls(W, WIDE_RUN, shape, prec, clock, "clocked bands")
     finally:
         TDM._reset()
 
@@ -584,6 +687,7 @@ def test_beta_nonzero_reads_exactly_its_own_row_of_y(M, prec, path):
 
 TINY_PAIRS = [(-1.5, 0.5), (2, 0)]
 uses([f"tiny_x:{c}:{r}" for c in TINY_COLS for r, _ in TINY_ROWS], TINY_PAIRS)
+wuses([f"tiny_x:{c}:{r}" for c in TINY_COLS for r, _ in TINY_ROWS])
 
 
 @pytest.mark.parametrize("cols", TINY_COLS)
@@ -594,12 +698,13 @@ def test_tiny_x_equals_the_model(M, cols, prec):
     vb = DT[prec][1]
     for rows, _ in TINY_ROWS:
         P = problem(f"tiny_x:{cols}:{rows}", prec)
-        D = OnDevice(M, P)
+        D, W = OnDevice(M, P), OnDevice(M, problem(f"tiny_x:{cols}:{rows}", prec, WIDE))
         for flags in ("compact", 0, 0x80000, 16, 16 | 0x80000):
             try:
                 M.set_compact_tiles(0 if flags == "compact" else -1)
                 M.set_tuning(vb, 0, 0, 0 if flags == "compact" else flags)
                 both_calls(D, TINY_PAIRS, cols, rows, prec, flags)
+                zero_calls(W, WIDE_RUN, cols, rows, prec, flags)
             finally:
                 M.set_tuning(vb); M.set_compact_tiles(0)
 

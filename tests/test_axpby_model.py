@@ -109,17 +109,139 @@ def test_every_gpu_problem_and_pair_is_within_the_bound():
     zero_only = {label for label in E.PROBLEMS if label.startswith("planted_zero:")}           # (shapes made for the zero-laden tests alone)
     assert set(label for label, _ in E.USED) == set(E.PROBLEMS) - zero_only, "a problem no test uses, or a test on an unlisted problem"
     assert zero_only <= set(label for label, _, _ in E.ZUSED) <= set(E.PROBLEMS)
+    qualifies = {}
     for (label, prec), pairs in sorted(E.USED.items()):
         P = E.problem(label, prec)
         limit = A.LIMIT[np.dtype(P.dtype)]
         # (the draws without a zero; the zero-laden ones: test_every_zero_laden_gpu_problem_has_its_rows_and_is_in_the_domain)
         assert not (P.csr.values == 0).any() and not (P.x == 0).any() and not (P.y0 == 0).any()
+        wide = A.WIDE_PAIRS[np.dtype(P.dtype)]
+        assert not pairs & {p for dt, ps in A.WIDE_PAIRS.items() if dt != np.dtype(P.dtype) for p in ps}, "wide scalars of the other type"
         for alpha, beta in sorted(pairs):
+            if (alpha, beta) in wide and not P.fits(alpha, beta):
+                continue                                         # (the GPU tests ask Problem.wide_scalars(), the same computation)
             assert A.quotient(P.csr, P.x, P.y0, alpha, beta) < limit, (label, prec, alpha, beta)
             P.want(alpha, beta)                                  # (the model's own assertion)
+        if pairs & set(wide):
+            assert set(P.wide_scalars()) <= set(wide) and (set(wide) <= pairs)
+            qualifies.setdefault(prec, set()).update([label] if len(P.wide_scalars()) == len(wide) else [])
+            # the arithmetic of the bound: both pairs fit exactly where sum |v*x| + |y0| stays below 2^23 (below 4095 and a bit)
+            _, sa = A.row_sums(P.csr, P.x)
+            g = 1 << (30 if prec == "f64" else 12)
+            fit = bool(((g + 2) * sa + (g + 1) * np.abs(P.y0.astype(np.int64)) < limit).all())
+            assert fit == (len(P.wide_scalars()) == len(wide)), (label, prec)
+    # which problems the wide scalars run on: in fp64 every one (the longest row, 1 445 000 entries of +-1, is below 2^22); in fp32
+    # those whose rows hold sum |v*x| < 4095 -- some of the path table and one of the prepared shapes
+    assert qualifies["f64"] == {label for (label, prec), pairs in E.USED.items() if prec == "f64" and pairs & set(A.WIDE_PAIRS[np.dtype(np.float64)])}
+    assert len(qualifies["f32"] & {"parity:" + n for n in E.T.SHAPES}) >= 6, qualifies["f32"]
+    assert qualifies["f32"] & {"parity:" + n for n in E.PREPARED_SHAPES}, qualifies["f32"]
     # the longest row of the shapes of test_gpu_parity run with the default value ranges: 200 000 entries, 6 per product, 5 granules
     # per unit of alpha, 64 for y0 -- the arithmetic of the bound
     assert 5 * 6 * 200_000 + 64 < 1 << 24
+
+
+def test_wide_scalars_are_what_they_say():
+    """no number of WIDE_PAIRS survives the narrower format, and granule() takes them"""
+    import torch
+    for alpha, beta in A.WIDE_PAIRS[np.dtype(np.float64)]:
+        for v in (alpha, beta):
+            assert v == 0 or float(np.float32(v)) != v
+        assert A.granule(alpha, beta) == 2.0 ** -30
+    for alpha, beta in A.WIDE_PAIRS[np.dtype(np.float32)]:
+        for v in (alpha, beta):
+            assert float(np.float32(v)) == v
+            assert v == 0 or (float(np.float16(v)) != v and float(torch.tensor(v, dtype=torch.float32).bfloat16().float()) != v)
+        assert A.granule(alpha, beta) == 2.0 ** -12
+    for pairs in A.WIDE_PAIRS.values():
+        assert [b == 0 for _, b in pairs] == [True, False] and pairs[1][0] < 0
+
+
+def test_wide_problem_draws_what_it_says():
+    rng = np.random.default_rng(2)
+    lens = rng.integers(0, 9, 600); lens[5] = 3000; lens[6] = 1
+    for dtype, xcap in ((np.float32, 1 << 8), (np.float64, 1 << 20)):
+        budget = A.wide_budget(dtype)
+        assert budget == A.LIMIT[np.dtype(dtype)] // 16
+        csr, x, y0 = A.wide_problem(rng, 600, 40, lens, dtype)
+        assert csr.values.dtype == dtype and x.dtype == dtype and y0.dtype == dtype
+        assert np.array_equal(np.diff(csr.row_offsets), lens)
+        v, xi, yi = (a.astype(np.int64) for a in (csr.values, x, y0))
+        assert (v % 2 == 1).all() and (xi % 2 == 1).all() and (yi % 2 == 1).all()            # odd: never zero, the lowest bit a one
+        assert (v < 0).any() and (v > 0).any() and (xi < 0).any() and (yi < 0).any()
+        import math
+        xmax = min(xcap, math.isqrt(budget // 3000))
+        assert np.abs(xi).max() <= xmax and np.abs(xi).max() > xmax // 2
+        assert np.abs(yi).max() <= budget and np.abs(yi).max() > budget // 2
+        off = csr.row_offsets
+        for r in range(600):
+            n = int(lens[r])
+            if n:
+                hi = max(1, budget // (n * xmax))
+                assert np.abs(v[off[r]:off[r + 1]]).max() <= hi
+            c = csr.column_indices[off[r]:off[r + 1]]
+            assert np.all(np.diff(c) >= 0) and np.all((c >= 0) & (c < 40))
+        assert np.abs(v[off[6]:off[7]]).max() > 1 << 8                                        # (a one-entry row: up to budget // xmax)
+        _, sa = A.row_sums(csr, x)
+        assert sa.max() <= budget and sa.max() > budget // 8                                  # the budget is filled, not only respected
+        for alpha, beta in A.PAIRS + [(-0.5, 0)]:
+            y = A.model(csr, x, y0, alpha, beta)
+            assert A.quotient(csr, x, y0, alpha, beta) <= A.LIMIT[np.dtype(dtype)] // 2
+            assert A.low_half_share(csr, y) >= 0.95
+        # the narrow draw is what the wide one is not
+        n = A.integer_problem(rng, 600, 40, lens, dtype)
+        assert A.low_half_share(n[0], A.model(*n, 1, 0)) == 0
+        assert all(share == 0 for _, _, share in A.carry_low_half_shares(n[0], n[1]))
+        shares = A.carry_low_half_shares(csr, x)
+        assert [(r, k) for r, k, _ in shares] == [(5, 2)]                                      # 3000 entries: one cut at 1792, one at 2816
+    assert A.low_half(np.array([1.0, 1 + 2.0 ** -30, 3 * 2.0 ** 40])).tolist() == [0, 1 << 22, 0]
+    assert A.low_half(np.array([1, 1 + 2.0 ** -12, 257], np.float32)).tolist() == [0, 1 << 11, 1 << 15]
+
+
+def test_row_sums_do_not_lean_on_wraparound():
+    """400 000 rows of the wide fp64 draw hold sum |v*x| of 2^47 and more each: a running sum over the whole matrix passes 2^63 (the
+    total is shown to, in exact Python integers).  row_sums adds every row on its own: its sums equal exact per-row sums, the
+    absolute sums are positive and within the budget, and rows without entries are zero."""
+    rng = np.random.default_rng(4)
+    lens = rng.integers(0, 9, 400_000)
+    csr, x, y0 = A.wide_problem(rng, lens.size, 1000, lens, np.float64)
+    s, sa = A.row_sums(csr, x)
+    assert sum(int(v) for v in sa) > 1 << 63                     # the whole-matrix running sum would have wrapped
+    assert s.dtype == np.int64 and (sa[lens > 0] > 0).all() and not sa[lens == 0].any() and not s[lens == 0].any()
+    assert sa.max() <= A.wide_budget(np.float64) and (np.abs(s) <= sa).all()
+    off = csr.row_offsets.astype(np.int64)
+    prod = csr.values.astype(np.int64) * x.astype(np.int64)[csr.column_indices]
+    for r in list(range(50)) + list(range(lens.size - 50, lens.size)) + rng.integers(0, lens.size, 300).tolist():
+        pr = [int(v) for v in prod[off[r]:off[r + 1]]]
+        assert int(s[r]) == sum(pr) and int(sa[r]) == sum(abs(v) for v in pr), r
+    assert A.segment_sums(np.array([5, 7, 11], np.int64), [0, 0, 2, 2, 3, 3]).tolist() == [0, 12, 0, 11, 0]
+    assert A.segment_sums(np.zeros(0, np.int64), [0, 0, 0]).tolist() == [0, 0]
+    with pytest.raises(AssertionError, match="does not fit int64"):
+        big = A.Csr(1, 1, np.array([0, 4], np.int32), np.zeros(4, np.int32), np.full(4, 2.0 ** 52))
+        A.row_sums(big, np.array([2.0 ** 9]))
+
+
+def test_every_wide_gpu_problem_fills_both_halves():
+    """every (matrix, precision, pair) the wide draw runs on the GPU: the bound (model() asserts it), at least 95 % of the rows with
+    entries have a y with a non-zero low half (low 32 bits of an fp64 pattern, low 16 of an fp32 one), and in fp64 at least 90 % of
+    the running sums of every row longer than a tile, taken after every 1792nd and every 2816th entry -- what carries and records are
+    made of --, have non-zero low 32 bits.  Conditions on the data: a shape that cannot meet one needs another shape or draw."""
+    E = _gpu_file()
+    assert E.WUSED, "no wide problem is registered"
+    # (the planted shapes are about which rows of y are read, not about a dispatch path's sums)
+    assert set(label for label, _ in E.WUSED) == set(label for label, _ in E.USED if not label.startswith("planted:")), \
+        "a problem the narrow draw runs and the wide one does not"
+    long_rows = 0
+    for (label, prec), pairs in sorted(E.WUSED.items()):
+        P = E.problem(label, prec, E.WIDE)
+        assert {(1, 0), E.NEG_ALPHA_ZERO_BETA} <= pairs and any(b != 0 for _, b in pairs)
+        for alpha, beta in sorted(pairs):
+            share = A.low_half_share(P.csr, P.want(alpha, beta))
+            assert share >= 0.95, (label, prec, alpha, beta, share)
+        if prec == "f64":
+            for row, count, share in A.carry_low_half_shares(P.csr, P.x):
+                long_rows += 1
+                assert count >= 1 and share >= 0.90, (label, row, count, share)
+    assert long_rows > 200
 
 
 def test_the_planted_problem_has_the_rows_the_gpu_test_plants_at():

@@ -5,12 +5,17 @@ reference's fp64 fix-up spins on such records without bound (cub/agent/single_pa
 in which the row ends polls a bounded number of times and then computes the missing sum from the matrix itself, so a stream
 restricted to a quarter of the CUs, a long kernel hogging the device, or a poll budget of ONE look (mspmv_set_record_polls)
 change the time of a call and, by a re-association, the last bits of such a row -- never whether y is complete and right.
+
+test_group_records_carry_both_halves_of_a_double runs the group-record shapes on tests/axpby_model.wide_problem: the one place
+where records and group records of fp64 sums -- two 32-bit payload words -- are taken from another workgroup, with numbers whose
+low word is not zero.  Measured on one MI355X: the 14 tests of this file take 3.5 s, the 12 before that test 3.3 s.
 """
 import ctypes
 
 import numpy as np
 import pytest
 
+import axpby_model as A
 from oracle import oracle as O
 
 torch = pytest.importorskip("torch")
@@ -234,5 +239,47 @@ def test_group_records_of_rows_that_span_hundreds_of_tiles(M, prec):
                     ys.append(y.cpu().numpy())
                 assert np.array_equal(ys[0], expect.astype(dtype)), (prec, polls, rows, int((ys[0] != expect).sum()))
                 assert np.array_equal(ys[0], ys[1])
+        finally:
+            M.set_record_polls(0)
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_group_records_carry_both_halves_of_a_double(M, prec):
+    """The shapes of the test above on axpby_model.wide_problem: odd integers that fill the exactness budget, so the records and
+    group records of the long rows -- the one place where a sum of one workgroup is taken by another, in fp64 as two 32-bit payload
+    words -- hold bits in both halves (asserted on the data in fp64: the row's running sums at every tile-th entry).  Two matrices:
+    rows of 70, 130 and 64 tiles behind 37 tiles of short rows, and one row of 400 tiles; the plain call and alpha, beta =
+    (-1.5, 0.5) equal the int64 model on the bits with the default poll budget, one look per record and none."""
+    dtype = np.float32 if prec == "f32" else np.float64
+    tdt = torch.float32 if prec == "f32" else torch.float64
+    rng = np.random.default_rng(65)
+    tile = M.launch_info(1000, 3_000_000, dtype().itemsize)["tile_items"]
+    cases = [np.concatenate([np.full(37 * tile // 4, 3), [70 * tile + 11], rng.integers(0, 5, 300), [130 * tile - 5], [64 * tile], rng.integers(0, 5, 50)]),
+             np.concatenate([rng.integers(0, 3, 40), [400 * tile + 1], rng.integers(0, 3, 40)])]
+    for lens in cases:
+        lens = lens.astype(np.int64)
+        csr, x, y0 = A.wide_problem(rng, lens.size, 4096, lens, dtype)
+        info = M.launch_info(csr.rows, csr.nnz, dtype().itemsize)
+        assert info["fixup_levels"] == 0 and info["snap_head_max"] > 0 and info["tile_items"] == tile      # the one-launch kernel, its records
+        assert lens.max() > 64 * tile
+        want = {(1, 0): A.model(csr, x, y0, 1, 0), (-1.5, 0.5): A.model(csr, x, y0, -1.5, 0.5)}
+        if prec == "f64":
+            shares = A.carry_low_half_shares(csr, x, strides=(tile,))
+            assert len(shares) == int((lens > tile).sum()) and all(share >= 0.9 for _, _, share in shares), shares
+            assert all(A.low_half_share(csr, w) >= 0.95 for w in want.values())
+        d = [dev(v) for v in (csr.values, csr.row_offsets, csr.column_indices, x)]
+        ws = M.CsrMVWorkspace(csr.rows, csr.nnz, tdt)
+        try:
+            for polls in (0, 1, -1):
+                M.set_record_polls(polls)
+                for call in range(2):
+                    for (alpha, beta), w in want.items():
+                        y = dev(y0.copy()) if beta else torch.full((csr.rows,), float("nan"), dtype=tdt, device="cuda")
+                        kw = {"alpha": alpha, "beta": beta} if beta else {}
+                        M.csrmv(*d, y=y, num_cols=csr.cols, workspace=ws, **kw)
+                        torch.cuda.synchronize()
+                        got = y.cpu().numpy()
+                        bad = np.flatnonzero(A.bits(got) != A.bits(w))
+                        assert bad.size == 0, (prec, polls, call, (alpha, beta), bad[:5].tolist(), got[bad[:5]].tolist(), w[bad[:5]].tolist())
         finally:
             M.set_record_polls(0)

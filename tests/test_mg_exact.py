@@ -12,7 +12,12 @@ Two layers, because each sees what the other cannot:
   (c) both with every part's arrays one element past a 256-byte boundary: the dword-per-lane classic form on coordinates found
       while the value and column pointers were still unknown.
   (d) K rounds of csrmv(); allgather_rows() enqueued WITHOUT a host synchronisation, against the same chain driven from the host.
-tests/test_mg_model.py guards the model and the inputs on the CPU; the hipIpc backend's exact case is tests/test_mg_plan.py's."""
+  (e) the routing of (a) on mg_model.wide_problem (odd integers that fill the exactness budget) at 2, 7 and 64 parts, with and
+      without the parts' hot-column plans, on unaligned part arrays, and through the RCCL one-rank backend: every part's sums, the
+      open-row entries of a boundary row shared by several parts and the folded carries then hold bits in the low word of a double.
+tests/test_mg_model.py guards the model and the inputs on the CPU; the hipIpc backend needs a process per part: its exact and its
+wide case are tests/test_mg_plan.py::test_ipc_backend_two_processes_sharing_the_device's (tests/mg_ipc_worker.py).  Measured on one MI355X: the 338 tests of this file take 51.8 s, the 288
+before the wide draw 35.1 s (a plan of 64 parts is built and closed per test: about 0.3 s each)."""
 import functools
 
 import numpy as np
@@ -50,6 +55,16 @@ def _frozen(*arrays):
 def _integer(name, prec):
     """(csr, x, the int64 model of A*x): computed once per problem and precision, read-only"""
     csr, x = MM.integer_problem(name, PRECS[prec][0])
+    want = AM.model(csr, x, None, 1, 0)
+    _frozen(csr.row_offsets, csr.column_indices, csr.values, x, want)
+    return csr, x, want
+
+
+@functools.lru_cache(maxsize=None)
+def _wide(name, prec):
+    """_integer on mg_model.wide_problem: odd integers that fill the exactness budget (both halves of every fp64 sum, open-row entry
+    and folded carry hold bits; tests/test_mg_model.py asserts it)"""
+    csr, x = MM.wide_problem(name, PRECS[prec][0])
     want = AM.model(csr, x, None, 1, 0)
     _frozen(csr.row_offsets, csr.column_indices, csr.values, x, want)
     return csr, x, want
@@ -135,8 +150,8 @@ def _exact_open_rows(csr, x, row_split, nz_split, dtype):
 
 # --------------------------------------------------------------------------------------------------------------- (a) routing
 
-def _check_routing(name, parts, prec, place=None):
-    csr, x, want = _integer(name, prec)
+def _check_routing(name, parts, prec, place=None, data=_integer):
+    csr, x, want = data(name, prec)
     B = Built(csr, parts, prec, place=place)
     plan = B.plan
     try:
@@ -177,13 +192,35 @@ def test_routing_is_exact_on_integer_data(name, parts, prec):
     _check_routing(name, parts, prec)
 
 
+@pytest.mark.parametrize("prec", sorted(PRECS))
+@pytest.mark.parametrize("parts", MM.WIDE_PARTS)
+@pytest.mark.parametrize("name", MM.WIDE_NAMES)
+def test_routing_is_exact_on_numbers_that_fill_the_significand(name, parts, prec):
+    """the routing test on mg_model.wide_problem at 2, 7 and 64 parts, the peer exchange with and without the parts' hot-column
+    plans: the open-row entries and the folded carries of a boundary row shared by several parts now have bits in the low word
+    of a double, so a carry that travels as a float, or as two words of which one is lost or taken from another part, shows"""
+    _check_routing(name, parts, prec, data=_wide)
+
+
+@pytest.mark.parametrize("parts", [7])
+@pytest.mark.parametrize("name", ["giant_middle", "short"])
+def test_unaligned_part_arrays_on_numbers_that_fill_the_significand(name, parts):
+    _check_routing(name, parts, "f64", place=off_by_one, data=_wide)
+
+
 @pytest.mark.parametrize("with_id", [False, True])
 @pytest.mark.parametrize("prec", sorted(PRECS))
 @pytest.mark.parametrize("name", NAMES)
 def test_one_part_through_the_rccl_backend_is_exact(name, prec, with_id):
     """parts == 1 through the RCCL one-rank backend: the single-process form (ncclCommInitAll) and the multi-process form with a
-    shipped id (ncclCommInitRank); its all-gather of the one carry is issued every step"""
-    csr, x, want = _integer(name, prec)
+    shipped id (ncclCommInitRank); its all-gather of the one carry is issued every step.  The shapes of mg_model.WIDE_NAMES on the
+    wide draw as well."""
+    for data in ([_integer, _wide] if name in MM.WIDE_NAMES else [_integer]):
+        _one_part_through_rccl(name, prec, with_id, data)
+
+
+def _one_part_through_rccl(name, prec, with_id, data):
+    csr, x, want = data(name, prec)
     B = Built(csr, 1, prec, exchange=MG.EXCHANGE_RCCL, id128=MG.unique_id() if with_id else None)
     try:
         assert B.plan.info()["exchange"] == MG.EXCHANGE_RCCL

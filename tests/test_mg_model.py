@@ -72,6 +72,52 @@ def test_the_models_routing_reproduces_the_whole_matrix(name, parts, dtype):
         assert all(s < g for s in src[g]) and src[g] == sorted(src[g])
 
 
+@pytest.mark.parametrize("name", MM.WIDE_NAMES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_wide_problems_are_exact_and_fill_both_halves(name, dtype):
+    """the wide draw of tests/test_mg_exact.py: the bound (model() asserts it), at least 95 % of the rows with entries have a y with
+    a non-zero low half, in fp64 at least 90 % of the running sums of every row longer than a tile and of the non-zero open-row
+    entries at every part count have one -- and the shared boundary rows do hand on such entries"""
+    csr, x = MM.wide_problem(name, dtype)
+    assert np.all(csr.values.astype(np.int64) % 2 == 1) and np.all(x.astype(np.int64) % 2 == 1)
+    want = AM.model(csr, x, None, 1, 0)
+    assert AM.low_half_share(csr, want) >= 0.95, name
+    taken = 0
+    for parts in MM.WIDE_PARTS:
+        count, share = MM.wide_open_row_share(csr, x, parts)
+        taken += count
+        if dtype == np.float64:
+            assert share >= 0.90, (name, parts, count, share)
+        # the routing of the model on this draw as well
+        row_split, nz_split = MM.partition(csr.row_offsets.astype(np.int64), parts)
+        y_locals = [AM.row_sums(MM.local_csr(csr, row_split, nz_split, g), x)[0].astype(dtype) for g in range(parts)]
+        assert np.array_equal(AM.bits(MM.fold(y_locals, row_split, dtype)[0]), AM.bits(want))
+    if dtype == np.float64:
+        assert all(share >= 0.90 for _, _, share in AM.carry_low_half_shares(csr, x)), name
+    if name != "cuts_on_row_ends":
+        assert taken >= (40 if name.startswith(("giant", "single")) else 2), (name, taken)
+
+
+@pytest.mark.parametrize("dtype,worlds", [(np.float64, (2, 4)), (np.float32, (2,))])
+def test_the_ipc_workers_wide_problem_hands_on_carries_with_a_low_word(dtype, worlds):
+    """kind `wide` of tests/mg_ipc_worker.py at the process counts tests/test_mg_plan.py runs it with: the bound (model() asserts
+    it), the giant row spans every rank (4 ranks: the middle ones own nothing), every rank but the last hands on a non-zero
+    open-row entry -- the carry the hipIpc backend ships as two tagged 32-bit halves -- and in fp64 every one of them has non-zero
+    low 32 bits, as have at least 95 % of the results"""
+    lens, csr, x = MM.ipc_wide_problem(dtype)
+    assert lens.size == MM.IPC_ROWS and lens.max() == MM.IPC_GIANT and np.array_equal(np.diff(csr.row_offsets), lens)
+    want = AM.model(csr, x, None, 1, 0)
+    assert AM.low_half_share(csr, want) >= 0.95
+    for world in worlds:
+        row_split, _ = MM.partition(csr.row_offsets.astype(np.int64), world)
+        owned = np.diff(row_split)
+        assert owned[0] > 0 and owned[-1] > 0 and (world < 4 or (owned[1:-1] == 0).all())
+        count, share = MM.wide_open_row_share(csr, x, world)
+        assert count == world - 1, (world, count)
+        if dtype == np.float64:
+            assert share == 1.0, (world, share)
+
+
 def test_a_dropped_or_misrouted_carry_changes_the_models_result():
     """the fold is not vacuous on these problems: without the sources, or with one fewer, y differs from the whole-matrix model"""
     csr, x = MM.integer_problem("giant_middle", np.float64)

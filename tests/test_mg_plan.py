@@ -299,12 +299,14 @@ def _run_bench(env_extra, nproc, *args, timeout=600, preflight=False):
 
 
 @gpu
-@pytest.mark.parametrize("kind,prec,nproc", [("giant", "f64", 2), ("short", "f32", 2), ("empty_parts", "f64", 4), ("exact", "f32", 2), ("exact", "f64", 4)])
+@pytest.mark.parametrize("kind,prec,nproc", [("giant", "f64", 2), ("short", "f32", 2), ("empty_parts", "f64", 4), ("exact", "f32", 2), ("exact", "f64", 4),
+                                             ("wide", "f64", 2), ("wide", "f64", 4), ("wide", "f32", 2)])
 def test_ipc_backend_two_processes_sharing_the_device(kind, prec, nproc):
     """The hipIpc peer backend of the one-process-per-GPU form (MSPMV_MG_EXCHANGE_IPC): `nproc` processes, one part each, all on
     cuda:0 of this box; carries go through hipIpc-opened mailboxes tagged with the step number, rows through the opened x
     replicas.  The worker checks every row against the oracle for repeated and iterated SpMV (tests/mg_ipc_worker.py); kind `exact`:
-    integer data, the repeated steps' y against the int64 model on the bits."""
+    integer data, the repeated steps' y against the int64 model on the bits; kind `wide`: the same on odd integers that fill the
+    exactness budget -- the fp64 carries travel as two tagged 32-bit halves, and on `exact` the low one is zero."""
     import subprocess, sys, socket
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]

@@ -6,7 +6,12 @@ what the wide call of the compute type returns for the widened values (include/m
 the wide call neither a column-band candidate nor on its small-shape layout).  No tolerance of its own anywhere: where a bound
 is checked it is the strict bound of tests/test_gpu_parity.py against the oracle on the widened matrix.
 
-CPU tests: exports, the size query, what the Python face refuses.  GPU tests (-m gpu): everything else."""
+test_values_that_fill_the_stored_significand_equal_the_int64_model compares with the int64 model of tests/axpby_model.py on values
+that use every bit of the stored type (odd integers up to 2^24 - 1 as fp32, up to 255 as bf16) and x, y0 as wide as the exactness
+budget allows: an error the mixed and the wide call share, or a conversion through float behind the widening, shows there.
+
+CPU tests: exports, the size query, what the Python face refuses.  GPU tests (-m gpu): everything else.  Measured on one MI355X:
+the 474 GPU tests of this file take 10.4 s, the 459 before the wide cases 10.1 s."""
 import ctypes
 import os
 import re
@@ -296,6 +301,66 @@ def test_zero_laden_and_scaled_values_equal_the_wide_call_and_the_model(G, pair,
                             assert same_bits(ym.cpu(), want[(alpha, beta)]), (where, "mixed call against the model")
                             assert same_bits(yw, ym), (where, "wide call against the mixed call")
                     assert same_bits(P.mixed(P.workspace(prepared)).cpu(), want[(1, 0)]), (pair, path, which, shift, prepared, "plain mixed call")
+    finally:
+        Mod.set_tuning(vb)
+
+
+WIDE_STORED_MAX = {"f32_f64": (1 << 24) - 1, "bf16_f32": 255}        # the largest odd integers the stored types hold exactly
+WIDE_PATHS = ["one_launch_small_shape", "one_launch_large_shape", "classic_three_launch"]
+
+
+def _long_among_short(rng):
+    """rows of 8 .. 40 entries and three rows longer than a tile: short enough (6000) that x keeps a few bits in fp32"""
+    lens = rng.integers(8, 41, 4000); lens[1000] = lens[1001] = 3000; lens[2500] = 6000
+    return 4000, 3000, lens
+
+
+WIDE_SHAPES = dict(T.COMPACT_SHAPES, long_among_short=_long_among_short)
+# bf16 values have 8 bits and a long row leaves x few: a result has bits in the low half of a float only where a row sums several
+# products, so the bf16 shapes hold no rows of one or two entries beside a long row (the shares are asserted below)
+WIDE_CASES = [("f32_f64", "power_law"), ("f32_f64", "giant_plus_sprinkle"), ("f32_f64", "long_among_short"),
+              ("bf16_f32", "five_point"), ("bf16_f32", "long_among_short")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair,shape", WIDE_CASES)
+@pytest.mark.parametrize("path", WIDE_PATHS)
+def test_values_that_fill_the_stored_significand_equal_the_int64_model(G, shape, pair, path):
+    """tests/axpby_model.wide_problem with the values capped at what the stored type holds: odd integers up to 2^24 - 1 stored as
+    fp32 in an fp64 product -- every bit of the stored significand set somewhere, and a product of 44 bits: a conversion through
+    float anywhere behind the widening changes y --, up to 255 stored as bf16 in an fp32 product; x and y0 odd integers as wide as
+    the exactness budget allows.  The mixed call against the INT64 MODEL on the bits (not only against the wide call, which would
+    share such an error): the one-launch kernel on both tile shapes and the classic launches, stateless and prepared, first call
+    and call on hints, plain and alpha / beta."""
+    import axpby_model as AM
+    sdt, cdt, npdt, vb, _ = PAIRS[pair]
+    rng = np.random.default_rng(101)
+    rows, cols, lens = WIDE_SHAPES[shape](rng)
+    csr, x, y0 = AM.wide_problem(rng, rows, cols, np.asarray(lens, np.int64), npdt, vcap=WIDE_STORED_MAX[pair])
+    assert WIDE_STORED_MAX[pair] * 15 // 16 <= np.abs(csr.values).max() <= WIDE_STORED_MAX[pair]
+    pairs = [(1, 0), (-1.5, 0.5), (-0.5, 0)]
+    want = {p: AM.model(csr, x, y0, *p) for p in pairs}
+    assert all(AM.low_half_share(csr, w) >= 0.95 for w in want.values())
+    if pair == "f32_f64":
+        assert all(share >= 0.9 for _, _, share in AM.carry_low_half_shares(csr, x))
+    want = {p: torch.from_numpy(w) for p, w in want.items()}
+    try:
+        Mod.set_tuning(vb, 0, 0, T.PATHS[path])
+        assert Mod.launch_info(rows, csr.nnz, vb)["flags"] == T.PATHS[path]
+        P = Problem(pair, rows, cols, csr.row_offsets, csr.column_indices, csr.values, x, exact=True)
+        assert Mod.band_passes(P.rows, P.cols, P.nnz, vb) <= 1
+        yin = torch.from_numpy(y0).cuda()
+        for prepared in (False, True):
+            for alpha, beta in pairs:
+                ws_w, ws_m = P.workspace(prepared), P.workspace(prepared)
+                for call in ("first", "on hints"):
+                    kw = {"alpha": float(alpha), "beta": float(beta)}
+                    yw, ym = P.wide(ws_w, yin, **kw), P.mixed(ws_m, yin, **kw)
+                    torch.cuda.synchronize()
+                    where = (shape, pair, path, prepared, alpha, beta, call)
+                    assert same_bits(ym.cpu(), want[(alpha, beta)]), (where, "mixed call against the model")
+                    assert same_bits(yw, ym), (where, "wide call against the mixed call")
+            assert same_bits(P.mixed(P.workspace(prepared)).cpu(), want[(1, 0)]), (shape, pair, path, prepared, "plain mixed call")
     finally:
         Mod.set_tuning(vb)
 

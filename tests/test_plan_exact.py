@@ -1,7 +1,12 @@
 """The band-major plan (mspmv_csrmv_plan_*, CsrMVPlan) pinned exactly: the stacked matrix the build leaves in the storage against
 tests/plan_model.py's stable sort, the `unsorted` flag at the places where it can be missed, y bit for bit on integer-valued cases
 (every association of the sums gives the same number), the kernels an apply and a build launch, what a real-valued y equals, a
-side stream, graph capture and the degenerate sizes.  tests/test_prepared_plan.py keeps the tolerance checks on real data."""
+side stream, graph capture and the degenerate sizes.  tests/test_prepared_plan.py keeps the tolerance checks on real data.
+
+The integer cases hold numbers of a few bits and alpha, beta that are fp32 numbers; plan_model.wide_case (odd integers that fill the
+exactness budget) runs the band-major plan's fold and the hot-column plan, x_is_permuted included, with bits in the low half of
+every partial sum, and plan_model.WIDE_SCALARS run alpha, beta that are no fp32 (no bf16) numbers through both plans.  Measured on
+one MI355X: the 136 tests of this file take 4.7 s, the 110 before the wide cases 3.8 s."""
 import ctypes
 import re
 
@@ -235,6 +240,104 @@ def test_y_is_exact_on_long_rows_and_both_fold_forms(prec, bands):
     form of the fold over more than one block (rows % 4, and y at a misaligned address with rows % 4 == 0)"""
     for name, st in PM.more_y_structures().items():
         exact_y_suite(st, prec, bands, (name, prec, bands), cap=1 if name == "giant_row" else 4)
+
+
+# ---- C3w: exact y on numbers that fill the significand -----------------------------------------------------------------------------
+WIDE_SHAPES = ("rows1027", "band_edges", "repeats", "row5000", "rows342_last2", "last_band")
+
+
+def assert_wide(case, prec, bands, label):
+    """conditions on the wide data: at least 95 % of the rows with entries have a result with a non-zero low half for every pair, and
+    so have at least 90 % of the non-empty (band, row) groups' sums -- what the fold adds"""
+    has = np.diff(case.a.row_offsets) > 0
+    for alpha, beta in PM.ALPHA_BETA:
+        units = (2 * case.want(alpha, beta)).astype(np.int64)                               # (halves: alpha = -0.5)
+        assert PM.low_half_share(units, prec, has) >= 0.95, (label, alpha, beta)
+    model = PM.stack(case.a, bands)
+    parts = PM.product_int(model, case.x)
+    assert np.array_equal(PM.fold(parts, case.a.rows, bands), case.ax)
+    if prec == "f64":
+        assert PM.low_half_share(parts, prec, np.diff(model.row_offsets) > 0) >= 0.90, label
+
+
+@gpu
+@pytest.mark.parametrize("bands", BANDS)
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_fold_is_exact_on_numbers_that_fill_the_significand(prec, bands, capfd):
+    """plan_model.wide_case: odd integers that fill the exactness budget, so the stacked matrix's partial sums y' -- written by the
+    CsrMV kernels with their carries and records, read again and added by the fold -- hold bits in both halves of a double (in the
+    low 16 bits of a float).  y on the bits for every pair at an aligned and a misaligned y; the fold is asserted to have run."""
+    sts = {n: st for n, st in PM.structures(bands).items() if n in WIDE_SHAPES}
+    sts.update({n: st for n, st in PM.more_y_structures().items() if n in ("giant_row", "rows1027")})
+    assert len(sts) == len(WIDE_SHAPES) + 1                                              # (rows1027 of both: the later one, 600 columns)
+    for name, st in sts.items():
+        case = PM.wide_case(np.random.default_rng(8), st, prec)
+        assert_wide(case, prec, bands, (name, prec, bands))
+        plan, _ = build(case.a, prec, bands, fill=0xFF)
+        xd, _ = device_x(case, prec)
+        capfd.readouterr()
+        plan(xd, debug_synchronous=True)
+        names = launch_names(capfd.readouterr().out)
+        assert ("plan_combine_kernel" in names) == (bands > 1), (name, names)
+        for alpha, beta in PM.ALPHA_BETA:
+            for offset in (0, 1):
+                assert_exact_y(plan, case, prec, alpha, beta, offset, xd, (name, prec, bands, "wide"))
+
+
+@gpu
+@pytest.mark.parametrize("bands", BANDS)
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_plans_are_exact_with_scalars_that_fill_the_significand(prec, bands):
+    """alpha and beta that are no fp32 (no bf16, no fp16) numbers -- plan_model.WIDE_SCALARS -- on the small integers of exact_case,
+    where their granule of 2^-30 (2^-12) leaves room: the band-major plan (the scalars travel through the plan's inner call into
+    the kernels and, with more than one band, into the fold) and, once, the hot-column plan."""
+    fitted = 0
+    for name in ("rows1027", "band_edges", "repeats", "empty_ends", "row5000"):
+        st = PM.structures(bands)[name]
+        case = PM.exact_case(np.random.default_rng(13), st, cap=1 if name == "row5000" else 4)
+        if not PM.fits_wide_scalars(case, prec):
+            continue
+        fitted += 1
+        plan, _ = build(case.a, prec, bands, fill=0xFF)
+        xd, _ = device_x(case, prec)
+        for alpha, beta in PM.WIDE_SCALARS[prec]:
+            for offset in (0, 1):
+                assert_exact_y(plan, case, prec, alpha, beta, offset, xd, (name, prec, bands, "wide scalars"))
+        if bands == BANDS[0]:
+            npdt, udt, _ = PREC[prec]
+            hot = M.CsrMVHotColumns(dev(case.a.values.astype(npdt)), dev(case.a.row_offsets.astype(np.int32)), dev(case.a.column_indices.astype(np.int32)), case.a.cols)
+            for alpha, beta in PM.WIDE_SCALARS[prec]:
+                y = hot(dev(case.x.astype(npdt)), dev(case.y0.astype(npdt)), alpha=alpha, beta=beta).cpu().numpy()
+                want = case.want(alpha, beta).astype(npdt)
+                assert np.array_equal(y.view(udt), want.view(udt)), (name, prec, alpha, beta, "hot-column plan")
+    assert fitted >= 4
+
+
+@gpu
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_hot_column_plan_is_exact_on_numbers_that_fill_the_significand(prec):
+    """the hot-column plan (renumbered columns, x gathered through the plan's order or permuted once by the caller) on
+    plan_model.wide_case: y on the bits against the int64 model, with x as it is and with x_is_permuted"""
+    npdt, udt, _ = PREC[prec]
+    sts = {"rows1027": PM.structures(3)["rows1027"], "repeats": PM.structures(3)["repeats"], "giant_row": PM.more_y_structures()["giant_row"]}
+    for name, st in sts.items():
+        case = PM.wide_case(np.random.default_rng(9), st, prec)
+        assert_wide(case, prec, 1, (name, prec))
+        val, off, col = dev(case.a.values.astype(npdt)), dev(case.a.row_offsets.astype(np.int32)), dev(case.a.column_indices.astype(np.int32))
+        plan = M.CsrMVHotColumns(val, off, col, case.a.cols)
+        order = plan.order().cpu().numpy()
+        assert np.array_equal(np.sort(order), np.arange(case.a.cols)) and not np.array_equal(order, np.arange(case.a.cols)), name
+        x = dev(case.x.astype(npdt))
+        xp = plan.permute(x)
+        assert np.array_equal(xp.cpu().numpy(), case.x.astype(npdt)[order])
+        for alpha, beta in PM.ALPHA_BETA:
+            want = case.want(alpha, beta).astype(npdt)
+            for permuted in (False, True):
+                y = dev(case.y0.astype(npdt)) if beta != 0.0 else torch.full((case.a.rows,), float("nan"), dtype=tdt(prec), device="cuda")
+                plan(xp if permuted else x, y, alpha=alpha, beta=beta, x_is_permuted=permuted)
+                got = y.cpu().numpy()
+                bad = np.flatnonzero(got.view(udt) != want.view(udt))
+                assert bad.size == 0, (name, prec, alpha, beta, permuted, bad[:5].tolist(), got[bad[:5]].tolist(), want[bad[:5]].tolist())
 
 
 # ---- C2: the unsorted flag ---------------------------------------------------------------------------------------------------------

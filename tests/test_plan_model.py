@@ -84,3 +84,29 @@ def test_skew_model_window_starts_and_small_sizes():
     # two lines, the second holding one column: columns 0 .. 32 of 4-byte values, 0 .. 16 of 8-byte values
     assert PM.skew(np.arange(4096) % 33, 33, 4)[0] == 2 and PM.skew(np.arange(4096) % 32, 33, 4)[0] == 1
     assert PM.skew(np.arange(4096) % 17, 17, 8)[0] == 2 and PM.skew(np.arange(4096) % 16, 17, 8)[0] == 1
+
+
+def test_wide_case_fills_the_budget_and_wide_scalars_are_no_narrower_numbers():
+    """the wide magnitude rule: odd numbers (a one in the lowest used bit), the budget of the precision filled and kept for every
+    pair of ALPHA_BETA (wide_case asserts the bound), results and the bands' partial sums with bits in the low half; the wide
+    scalars are what they say and fit the small integers of exact_case"""
+    for prec, limit in (("f32", 1 << 24), ("f64", 1 << 53)):
+        for bands in (1, 3, 64):
+            st = PM.structures(bands)["rows1027"]
+            case = PM.wide_case(np.random.default_rng(8), st, prec)
+            v = case.a.values.astype(np.int64)
+            assert (v % 2 == 1).all() and (case.x % 2 == 1).all() and (case.y0 % 2 == 1).all()
+            s_abs = np.zeros(case.a.rows, np.int64)
+            np.add.at(s_abs, case.a.row_of_entry(), np.abs(v * case.x[case.a.column_indices]))
+            assert limit // 128 < s_abs.max() <= limit // 16 and limit // 32 < np.abs(case.y0).max() <= limit // 16
+            has = np.diff(case.a.row_offsets) > 0
+            assert PM.low_half_share(case.ax, prec, has) >= 0.95
+            narrow = PM.exact_case(np.random.default_rng(8), st)
+            assert PM.low_half_share(narrow.ax, prec, has) == 0.0            # what the small integers leave empty
+            assert PM.fits_wide_scalars(narrow, prec) and not PM.fits_wide_scalars(case, prec)
+    for alpha, beta in PM.WIDE_SCALARS["f64"]:
+        assert all(v == 0 or float(np.float32(v)) != v for v in (alpha, beta))
+    for alpha, beta in PM.WIDE_SCALARS["f32"]:
+        assert all(float(np.float32(v)) == v and (v == 0 or float(np.float16(v)) != v) for v in (alpha, beta))
+        assert all(v == 0 or (np.float32(v).view(np.uint32) & 0xFFFF) != 0 for v in (alpha, beta))           # not a bf16
+    assert PM.low_half_share(np.array([1, 257, 1 << 20]), "f32") == 1 / 3 and PM.low_half_share(np.array([1, (1 << 21) + 1]), "f64") == 0.5

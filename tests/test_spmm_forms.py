@@ -20,6 +20,14 @@ integers scaled so that one unit of the reference is the smallest subnormal (val
 and 2^(emax - mantissa bits); the scaled arrays are made on the host.  test_negative_zero_in_y0_on_rows_without_entries is the one
 place where t is -0.0: on rows without entries, where the definition gives alpha * (+0.0) + (-0.0).
 
+WIDE.  All of the above are integers of a few bits: the low 32 bits of every fp64 product, sum and carry are zero.
+spmm_forms.WIDE_CASES run one case per form and precision -- the row-wise kernel, every pack width, the slot form of 16 and 8, two
+groups of 16 in the slot form; all but the row-wise through the carries and the fix-up on the giant row -- on odd integers that fill
+the exactness budget per row and per column of X (Call.plant_wide: the rule of tests/axpby_model.wide_problem, made on the device
+from the same hashes); Call.assert_wide asserts on the reference that at least 95 % of the results of every column, and in fp64 at
+least 90 % of the running sums of every row longer than a tile at every tile-th entry, have a non-zero low half.  The launch log is
+pinned as for every other case.
+
 The log names the kernel, grid.x and block of every launch: that pins the form and the tile size.  Which AXPBY / NT instantiation
 ran, the width of a pack launch among those sharing a tile size, and the fix-up's grid.y (groups) are not printed; the coverage
 table's axpby and nt columns are what the restated rule says of the call's alpha, beta and stream size, not an observation.  A wrong
@@ -27,8 +35,9 @@ width or group count does show in the exact comparison (columns left unwritten s
 
 The matrices (spmm_forms.structure) are built once each and freed before the next.
 
-Measured on one MI355X: the 62 tests of this file take 8.6 s (the 30 before the zero-laden and scaled cases: 5.3 s), beside some
-four minutes for the other GPU tests.  Sensitivity, each a one-line change of mspmv_spmm.hpp tried against this file, every failure the exact comparison:
+Measured on one MI355X: the 78 tests of this file take 11.6 s (the reference now adds its running sums in two halves that cannot wrap), the 70 of the
+parent commit 8.8 s (the 30 before the zero-laden and
+scaled cases: 5.3 s), beside some four minutes for the other GPU tests.  Sensitivity, each a one-line change of mspmv_spmm.hpp tried against this file, every failure the exact comparison:
 the slot form's before() stopping one slot early fails the 10 big_slots / big_slot_groups / huge_slots_nt cases; its carries
 indexed without g * num_tiles the 4 cases with two groups of 16 (big_slot_groups, huge_slots_nt_plain); the pack kernel without
 its nz_tail store every case that runs a pack (24 tests: the last row, in the pack widths' columns); the fix-up without its
@@ -38,13 +47,18 @@ carry or scan result that is used reads -- with X[0, :] = NaN those positions ho
 what test_nan_and_inf_stay_where_they_are asserts.  The "+ 0" of the beta == 0 write taken out again (pack kernel's row phase and
 the slot form's put, the state before the sign of a zero sum was pinned): 10 tests fail, all on the sign of a zero -- mid_wide_groups_* (alpha = -2, beta = 0) with
 and without zeros, big_slots_negative_alpha_beta_0_*_zeros, and step 4 of test_nan_and_inf_stay_where_they_are on the pack and the
-slot case of both precisions.
+slot case of both precisions.  The slot form's fp64 carry stored through (float) (`cr->value.v[c + k] = (T) (float) s[k]`), tried
+against the parent commit's version of this file and against this one: 3 / 5 tests fail -- both see it where the scaled case puts
+one unit at the smallest subnormal (the cast flushes: test_both_ends_of_the_exponent_range[big_slots_axpby_f64-*]); at the plain
+scale only big_slots_axpby_f64_wide and big_slot_groups_f64_wide do.  The other one-line changes tried against the wide data:
+tests/test_axpby_exact.py.
 """
 import re
 
 import numpy as np
 import pytest
 
+import axpby_model as AM
 import spmm_forms as F
 
 torch = pytest.importorskip("torch")
@@ -55,7 +69,12 @@ EXACT = {"f32": 1 << 24, "f64": 1 << 53}
 SENTINEL = 777.0
 ROW_CHUNK = 1 << 21
 MAT_ORDER = {"tiny": 0, "mid": 1, "big": 2, "huge": 3}
-ORDERED = sorted(F.CASES + F.ZERO_CASES, key=lambda c: MAT_ORDER[c.mat])
+ORDERED = sorted(F.CASES + F.ZERO_CASES + F.WIDE_CASES, key=lambda c: MAT_ORDER[c.mat])
+NPDT = {"f32": np.dtype(np.float32), "f64": np.dtype(np.float64)}
+# the constants of the wide rule are axpby_model's; the draw itself is restated on the device (Call.plant_wide: hashes, not an rng)
+WIDE_XMAX = {p: AM.WIDE_XMAX[d] for p, d in NPDT.items()}
+LOW_BITS = {p: AM.LOW_BITS[d] for p, d in NPDT.items()}       # the "low half" of a bit pattern
+assert all(AM.LIMIT[d] == EXACT[p] for p, d in NPDT.items())
 BOTTOM, TOP = {"f32": -149, "f64": -1074}, {"f32": 127 - 24, "f64": 1023 - 53}        # the smallest subnormal; 2^(emax - mantissa bits)
 KIND_I, KIND_II, KIND_III, KIND_II_EVEN = 3, 7, 11, 13      # row % 16 of the planted rows of the zero-laden data
 ZERO_COL, POS_COL, NEG_ZERO_COL, NEG_COL, EVEN_COL = 1, 2, 3, 4, 5
@@ -69,6 +88,20 @@ def _bits(t):
 def _hash(seed, idx):
     from merge_spmv_amd.generators import splitmix64
     return splitmix64(seed, idx) & ((1 << 63) - 1)
+
+
+def _odd(seed, idx, hi):
+    """odd integers in [1, hi] (hi a number or a tensor, >= 1)"""
+    return 2 * (_hash(seed, idx) % ((hi + 1) // 2)) + 1
+
+
+def _sign(seed, idx, negative_in=2):
+    """-1 for one index in `negative_in`, else 1"""
+    return 1 - 2 * (_hash(seed, idx) % negative_in == 0).to(torch.int64)
+
+
+def _low_half(t, prec):
+    return _bits(t) & ((1 << LOW_BITS[prec]) - 1)
 
 
 def _pm(seed, idx, m):
@@ -169,6 +202,8 @@ class Call:
         v = mat.vals(c.prec)[:nnz]
         if c.zeros:
             v = self.plant_zeros()
+        if c.wide:
+            v = self.plant_wide()
         ci = self.cidx.to(torch.int32)
         if c.pad:
             vp = torch.empty(nnz + c.pad, dtype=dt, device="cuda")[c.pad:]; vp.copy_(v); v = vp
@@ -185,6 +220,8 @@ class Call:
             hi = min(lo + ROW_CHUNK, cols)
             r = torch.arange(lo, hi, dtype=torch.int64, device="cuda")
             self.X[lo:hi] = _pm(0x5F0003, r[:, None] * 64 + j[None, :], 3).to(dt)
+            if c.wide:                                 # odd, up to xmax; one sign per row of X (plant_wide signs the values by it)
+                self.X[lo:hi] = (_odd(0x5F0024, r[:, None] * 64 + j[None, :], self.xmax) * _sign(0x5F0023, r)[:, None]).to(dt)
             if c.zeros:                                # a quarter zeros, of both signs
                 h = _hash(0x5F0013, r[:, None] * 64 + j[None, :]) % 8
                 self.X[lo:hi] = torch.where(h == 0, 0.0, torch.where(h == 1, -0.0, self.X[lo:hi].to(torch.float64))).to(dt)
@@ -198,6 +235,8 @@ class Call:
         assert self.Xw.data_ptr() % 256 == 0
         r = torch.arange(rows, dtype=torch.int64, device="cuda")
         self.y0 = _pm(0x5F0004, r[:, None] * 64 + j[None, :], 8)
+        if c.wide:
+            self.y0 = _odd(0x5F0025, r[:, None] * 64 + j[None, :], self.budget) * _sign(0x5F0026, r[:, None] * 64 + j[None, :])
         self.y_ref, self.s = self.reference(self.vals64, self.X)
 
     def plant_zeros(self):
@@ -247,17 +286,64 @@ class Call:
         assert bool((fb == _bits(torch.tensor([-0.0], dtype=dt, device="cuda"))).any()) and (nnz < 64 or bool((fb == 0).any()))
         return f
 
+    def plant_wide(self):
+        """the wide values of this case, the rule of axpby_model.wide_problem per row and per column of X: with the budget
+        B = 2^24 (2^53) // 16, X odd integers up to xmax = min(2^8 (2^20), isqrt(B // longest row)) and the values of a row of n
+        entries odd integers up to max(1, B // (n * xmax)), signed so that three products in four are positive in every column
+        of X (a row of X has one sign).  Returns the float values, leaves their integers in vals64."""
+        import math
+        c, nnz = self.c, self.nnz
+        self.budget = AM.wide_budget(NPDT[c.prec])
+        lens = self.off64[1:] - self.off64[:-1]
+        self.xmax = max(1, min(WIDE_XMAX[c.prec], math.isqrt(self.budget // int(lens.max()))))
+        k = torch.arange(nnz, dtype=torch.int64, device="cuda")
+        row = torch.searchsorted(self.off64, k, right=True) - 1
+        hi = (self.budget // (lens[row] * self.xmax)).clamp(min=1)
+        self.vals64 = _odd(0x5F0021, k, hi) * _sign(0x5F0023, self.cidx) * _sign(0x5F0022, k, 4)
+        return self.vals64.to(self.dt)
+
+    def assert_wide(self):
+        """conditions on the wide data, from the reference: in every column at least 95 % of the rows with entries have a Y with a
+        non-zero low half (low 32 bits of an fp64 pattern, low 16 of an fp32 one); in fp64, of the running sums of every row longer
+        than a tile of the case, taken at every tile-th entry (column 0 of X) -- what carries are made of --, at least 90 %"""
+        c = self.c
+        lens = self.off64[1:] - self.off64[:-1]
+        low = _low_half(self.want().to(self.dt), c.prec)[lens > 0]
+        share = (low != 0).to(torch.float64).mean(0)
+        assert float(share.min()) >= 0.95, f"{c.name}: the share of results with a non-zero low half is {share.tolist()}"
+        if c.prec != "f64" or c.launches()[0][0] == "spmm_rowwise_kernel":
+            return
+        p = self.vals64 * self.X[:, 0].to(torch.int64)[self.cidx]
+        seen = 0
+        for T in sorted({g.tile for g in c.groups()}):
+            for r in torch.nonzero(lens > T)[:, 0].tolist():
+                lo, hi = int(self.off64[r]), int(self.off64[r + 1])
+                sums = torch.cumsum(p[lo:hi], 0)[torch.arange(T - 1, hi - lo - 1, T, device="cuda")]      # (this row's own running sum)
+                wide = float((_low_half(sums.to(self.dt), c.prec) != 0).to(torch.float64).mean())
+                assert wide >= 0.9, f"{c.name}: row {r}, tile {T}: {wide} of {sums.numel()} running sums have a non-zero low half"
+                seen += 1
+        assert seen >= 2                                        # (the giant row and the open last row at least)
+
     def reference(self, vals64, X):
-        """int64 [rows, k]: the segmented sums of a * X[col] and of |a * X[col]|, from running sums (exact, no atomics)"""
+        """int64 [rows, k]: the segmented sums of a * X[col] and of |a * X[col]|, from running sums that CANNOT WRAP: a product is
+        split into p = hi * 2^24 + lo (0 <= lo < 2^24, hi the floor), and each half gets its own running sum over all nonzeros --
+        both stay below 2^62, which is asserted.  (One running sum of p itself passes 2^63 on the wide data, where sum |a x| is
+        about 2^47 per row, and would give the right differences only through two's-complement wraparound.  No atomics.)"""
         a, b = self.off64[:-1], self.off64[1:]
+
+        def segment_sums(p):
+            hi = p >> 24                                 # (arithmetic shift: the floor, also of a negative product)
+            lo = p - (hi << 24)
+            assert (int(hi.abs().max()) + 1) * p.numel() < 1 << 62 and p.numel() < 1 << 38
+            ch = torch.nn.functional.pad(torch.cumsum(hi, 0), (1, 0))
+            cl = torch.nn.functional.pad(torch.cumsum(lo, 0), (1, 0))
+            return ((ch[b] - ch[a]) << 24) + (cl[b] - cl[a])
         y = torch.empty(self.rows, self.c.k, dtype=torch.int64, device="cuda")
         s = torch.empty_like(y)
         for jj in range(self.c.k):
             p = vals64 * X[:, jj].to(torch.int64)[self.cidx]
-            cp = torch.nn.functional.pad(torch.cumsum(p, 0), (1, 0))
-            y[:, jj] = cp[b] - cp[a]
-            cp = torch.nn.functional.pad(torch.cumsum(p.abs(), 0), (1, 0))
-            s[:, jj] = cp[b] - cp[a]
+            y[:, jj] = segment_sums(p)
+            s[:, jj] = segment_sums(p.abs())
         return y, s
 
     def want(self, alpha=None, beta=None):
@@ -323,6 +409,8 @@ def test_form_runs_and_is_exact(M, mats, capfd, case):
     assert int(call.s.min()) >= 0 and int(call.cidx.min()) >= 1 and int(call.cidx.max()) == call.cols - 1
     if c.alpha < 0 and c.beta == 0:
         _assert_zero_rows(call)
+    if c.wide:
+        call.assert_wide()
     if c.zeros and c.mat != "tiny":
         # per column of X: zero sums of rows whose products are all zero, and of rows whose non-zero products cancel
         lens = (call.off64[1:] - call.off64[:-1])[:, None]
