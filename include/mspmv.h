@@ -55,7 +55,7 @@ extern "C" {
  * no HIP headers (NULL = the default stream). */
 typedef void *mspmv_stream_t;
 
-#define MSPMV_VERSION 102 /* (the accessors of the band-major plan's stacked matrix, mspmv_csrmv_plan_row_offsets / _columns / _values, the matrix addition mspmv_csr_add_*, the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, and the mixed-precision ones, mspmv_csrmv_mixed_* / mspmv_csrmv_mixed_prepared_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
+#define MSPMV_VERSION 102 /* (the incomplete LU factorisation mspmv_csrilu0_*, the accessors of the band-major plan's stacked matrix, mspmv_csrmv_plan_row_offsets / _columns / _values, the matrix addition mspmv_csr_add_*, the transpose entry points mspmv_csr_transpose_* / mspmv_csrmv_transpose_* and the COO ones, mspmv_coo_to_csr_* / mspmv_csr_sum_duplicates_* / mspmv_coomv_*, and the mixed-precision ones, mspmv_csrmv_mixed_* / mspmv_csrmv_mixed_prepared_*, came without a bump: find them by symbol); 0.1.2: + mspmv_get_clocked_bands (the clock-scheduled column bands serve the column-band candidates); 0.1.1: mspmv_launch_info_t grew (records_offset, layout_offset), the setters moved to mspmv_dev.h */
 int mspmv_version(void);
 
 /* hipGetErrorString for codes returned by this library. */
@@ -653,6 +653,56 @@ int mspmv_csrsv_solve_f64(mspmv_csrsv_plan_t *plan, const double *d_values, cons
                           const int32_t *d_column_indices, double alpha, const double *d_b, double *d_x,
                           mspmv_stream_t stream, int debug_sync);
 int mspmv_csrsv_plan_destroy(mspmv_csrsv_plan_t *plan);
+
+/* ---- extension: ILU(0), the incomplete LU factorisation without fill-in, level-scheduled (csrc/mspmv_csrilu0.hip; what
+ * rocsparse_csrilu0 is in rocSPARSE): A ~ L U on A's own pattern, the preconditioner whose two sweeps mspmv_csrsv_* solves.  With it
+ * a preconditioned Krylov iteration stays inside this library: mspmv_csrmv_* for A p, mspmv_csrilu0_* once per matrix, two
+ * mspmv_csrsv_solve_* per iteration.
+ * THE PLAN: lower_plan is any plan made by mspmv_csrsv_plan_create with MSPMV_CSRSV_LOWER (either diag) for this pattern: row i of
+ * the row-wise elimination needs the finished rows whose column its strict lower part stores, which is the dependency graph of
+ * L x = b, so the plan's levels, order and segments are the factorisation's too.  rows and nnz are taken from it; the same plan then
+ * serves the L solve (created with MSPMV_CSRSV_UNIT).  An UPPER plan or a NULL plan is refused.
+ * INPUT: A is rows x rows in CSR, every row SORTED by column with no column twice: the canonical form mspmv_csr_sum_duplicates_*,
+ * mspmv_csr_add_* and mspmv_csr_gemm_* write.  This is NOT checked: on other input the values are unspecified, but nothing outside
+ * the arrays is touched and the call ends.  The pattern arrays and d_values are not modified unless d_values_lu == d_values (in
+ * place), which is allowed; any other overlap is not.
+ * OUTPUT: d_values_lu, nnz entries on A's pattern: the strict lower part holds L (its unit diagonal implied), the diagonal and the
+ * upper part hold U -- what mspmv_csrsv_* sweeps with LOWER + UNIT and UPPER + NON_UNIT, nothing extracted.
+ * VALUES, defined bit for bit in the value type.  Rows in dependency order; for row i:
+ *     for every stored entry e of row i with k = col[e] < i, in stored (= ascending) order:
+ *         a[e] = a[e] / piv(k)              piv(k) = the FINAL diagonal value of row k; +0.0 if row k stores no diagonal
+ *         for every stored entry f of row k with j = col[f] > k for which row i stores column j, at position g:
+ *             a[g] = a[g] - a[e] * a[f]
+ * every divide, multiply and subtract rounded on its own (no fused multiply-add; the division correctly rounded), nothing flushed to
+ * zero.  So a[g] is a function of A's values and the pattern alone -- not of levels, segments, lanes per row, alignment or the
+ * kernel that ran.  Products whose (i, j) is not in the pattern are dropped (the "0").  A missing diagonal acts as a pivot of +0.0
+ * and its row has no diagonal to update: the definition is total, and a division by zero gives the IEEE inf or NaN.
+ * PIVOT: *d_pivot (one int32 ON THE DEVICE; may be NULL) = the smallest row whose diagonal is not stored or whose final diagonal
+ * compares == 0 (so -0.0 counts, NaN does not); -1 if there is none.  The host does not learn it inside the call.
+ * TEMP STORAGE, two-phase: d_temp == NULL writes the size to *temp_bytes, does no work and needs no device.  d_temp is 16-byte
+ * aligned and holds the diagonal position of every row: 4 * rows bytes rounded up to 16, at least 16.
+ * SCHEDULE: one prologue launch (each row's diagonal position by bisection; the copy of d_values to d_values_lu when they differ;
+ * rows without a stored diagonal go to *d_pivot), then one launch per segment of the plan: 1 + info.launches in all.  A row is
+ * worked by G consecutive lanes of one wave, G = mspmv_csrilu0_group(rows, nnz): the smallest power of two >= the mean row length,
+ * within [1, 64]; a function of rows and nnz alone (host only, launches nothing).  Each lane owns every G-th entry of the row; the
+ * quotient of a lower entry reaches the group by a shuffle.  No workgroup waits for another.
+ * Asynchronous on `stream`; allocates nothing, reads nothing back, launches the same kernels whatever the values and can be
+ * captured in a graph; debug_sync prints one line per launch with the lanes per row and waits for it; returns 0 or a hipError_t.
+ * LIMITS, refused before anything is launched: a NULL or UPPER plan; a NULL temp_bytes; *temp_bytes too small; a misaligned d_temp;
+ * NULL value or pattern arrays with nnz > 0.  rows == 0 succeeds and launches nothing.  nnz == 0 with rows > 0 reports pivot 0.
+ * Measured on MI355X against rocsparse_csrilu0 (analysis outside the timing; out of place, the copy included; profiles/
+ * csrilu0_bench.txt; DESIGN.md 4 "ILU(0)"), fp32 / fp64: a 5-point grid of 2000 x 2000 22.0 / 26.9 ms against 191 / 192 ms; a
+ * 7-point grid of 128^3 2.90 / 3.17 ms against 112 / 112 ms; A + A^T + I of an R-MAT graph of scale 14 (rows of thousands of
+ * entries, one group each) 612 / 621 ms against 9.6 / 9.6 ms: rocSPARSE is 64 times faster there, and at scale 16 and 18, where one
+ * group would run for seconds to minutes, this call was not run at all (rocSPARSE: 85 ms and 0.82 s).  G by the sweep on the two
+ * grids. ---- */
+int mspmv_csrilu0_group(int32_t rows, int32_t nnz, int32_t *lanes_per_row);
+int mspmv_csrilu0_f32(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t *temp_bytes, const float *d_values,
+                      float *d_values_lu, const int32_t *d_row_offsets, const int32_t *d_column_indices, int32_t *d_pivot,
+                      mspmv_stream_t stream, int debug_sync);
+int mspmv_csrilu0_f64(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t *temp_bytes, const double *d_values,
+                      double *d_values_lu, const int32_t *d_row_offsets, const int32_t *d_column_indices, int32_t *d_pivot,
+                      mspmv_stream_t stream, int debug_sync);
 
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */

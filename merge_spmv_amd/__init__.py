@@ -18,7 +18,7 @@ import os
 from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
-           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv",
+           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv", "csrilu0", "Ilu0",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -215,6 +215,11 @@ def load_library() -> ctypes.CDLL:
         fn.argtypes = [vp, vp, vp, vp, ct, vp, vp, vp, ctypes.c_int]
     lib.mspmv_csrsv_plan_destroy.restype = ctypes.c_int
     lib.mspmv_csrsv_plan_destroy.argtypes = [vp]
+    lib.mspmv_csrilu0_group.restype = ctypes.c_int
+    lib.mspmv_csrilu0_group.argtypes = [i32, i32, ctypes.POINTER(i32)]
+    for name in ("mspmv_csrilu0_f32", "mspmv_csrilu0_f64"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, vp, sz_p, vp, vp, vp, vp, vp, vp, ctypes.c_int]
     lib.mspmv_csr_gemm_products.restype = ctypes.c_int
     lib.mspmv_csr_gemm_products.argtypes = [vp, sz_p, vp, vp, i32, i32, i32, vp, i32, vp, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_skew.restype = ctypes.c_int
@@ -1202,6 +1207,143 @@ def csrsv(values, row_offsets, column_indices, b, lower: bool = True, unit_diago
         import torch
         torch.cuda.current_stream(plan.device).synchronize()
         plan.close()
+
+
+def csrilu0_group(rows: int, nnz: int) -> int:
+    """G, the lanes of one wave that work one row of mspmv_csrilu0_*: a function of rows and nnz alone (host only)."""
+    g = ctypes.c_int32(0)
+    _check(load_library().mspmv_csrilu0_group(int(rows), int(nnz), ctypes.byref(g)), "mspmv_csrilu0_group")
+    return int(g.value)
+
+
+def _ilu0_check(what, values, row_offsets, column_indices, plan=None, out=None):
+    """the refusals of csrilu0 / Ilu0.factor, raised before any device call"""
+    import torch
+    for t, name in ((values, "values"), (row_offsets, "row_offsets"), (column_indices, "column_indices")):
+        if not isinstance(t, torch.Tensor):
+            raise MspmvError(f"{what}: {name} must be a tensor")
+    if not (values.is_cuda and row_offsets.is_cuda and column_indices.is_cuda):
+        raise MspmvError(f"{what} needs CUDA (HIP) tensors: the kernels only run on the GPU")
+    if values.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what} is instantiated for float32 and float64, got {values.dtype}")
+    if row_offsets.dtype != torch.int32 or column_indices.dtype != torch.int32:
+        raise TypeError(f"{what}: row_offsets / column_indices must be int32")
+    if row_offsets.dim() != 1 or row_offsets.numel() < 1 or not row_offsets.is_contiguous() or column_indices.dim() != 1 \
+            or not column_indices.is_contiguous() or column_indices.device != row_offsets.device:
+        raise MspmvError(f"{what}: row_offsets (rows + 1 entries) and column_indices must be contiguous 1-D tensors on one device")
+    rows, nnz = row_offsets.numel() - 1, column_indices.numel()
+    if values.device != row_offsets.device or values.dim() != 1 or not values.is_contiguous() or values.numel() != nnz:
+        raise MspmvError(f"{what}: values must be a contiguous 1-D tensor of {nnz} entries on {row_offsets.device}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != values.dtype:
+            raise TypeError(f"{what}: out must be a {values.dtype} tensor")
+        if out.device != values.device or out.dim() != 1 or not out.is_contiguous() or out.numel() != nnz:
+            raise MspmvError(f"{what}: out must be a contiguous 1-D tensor of {nnz} entries on {values.device}")
+    if plan is not None:
+        if not isinstance(plan, CsrSv):
+            raise MspmvError(f"{what}: plan must be a CsrSv")
+        if plan._handle is None:
+            raise MspmvError(f"{what}: the plan is closed")
+        if plan.info["uplo"] != 0:
+            raise MspmvError(f"{what}: the plan must be a LOWER one (the factorisation runs along the levels of L x = b)")
+        if plan.rows != rows or plan.nnz != nnz or plan.device != row_offsets.device:
+            raise MspmvError(f"{what}: the plan was made for {plan.rows} rows and {plan.nnz} entries on {plan.device}")
+    return rows, nnz
+
+
+def _ilu0_temp_bytes(plan) -> int:
+    size = ctypes.c_size_t(0)
+    _check(plan._lib.mspmv_csrilu0_f32(plan._handle, None, ctypes.byref(size), None, None, None, None, None, None, 0), "mspmv_csrilu0 (size query)")
+    return int(size.value)
+
+
+def _ilu0_call(plan, temp, values, lu, row_offsets, column_indices, pivot, stream, debug_synchronous):
+    import torch
+    fn = plan._lib.mspmv_csrilu0_f32 if values.dtype == torch.float32 else plan._lib.mspmv_csrilu0_f64
+    size = ctypes.c_size_t(temp.numel())
+    with torch.cuda.device(plan.device):
+        _check(int(fn(plan._handle, ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), _ptr(values), _ptr(lu), _ptr(row_offsets),
+                      _ptr(column_indices), _ptr(pivot), _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_csrilu0")
+
+
+def csrilu0(values, row_offsets, column_indices, plan=None, out=None, stream=None, debug_synchronous: bool = False):
+    """ILU(0) of the CSR matrix (sorted rows, no column twice) on its own pattern (mspmv_csrilu0_*): returns (lu_values, pivot).
+    lu_values: L in the strict lower part (unit diagonal implied), U on and above the diagonal -- what CsrSv sweeps with lower=True,
+    unit_diagonal=True and lower=False.  pivot: a 1-element int32 DEVICE tensor (the smallest row with a missing or zero diagonal, -1
+    if none), so nothing waits for the device.  `plan`: a LOWER CsrSv of this pattern (one is made and dropped if not given; a loop
+    keeps an Ilu0).  `out`: where the factor goes; may be `values` (in place)."""
+    import torch
+    rows, nnz = _ilu0_check("csrilu0", values, row_offsets, column_indices, plan, out)
+    own = plan is None
+    if own:
+        plan = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=True, stream=stream)
+    try:
+        lu = out if out is not None else torch.empty(nnz, dtype=values.dtype, device=values.device)
+        pivot = torch.empty(1, dtype=torch.int32, device=values.device)
+        temp = torch.empty(_ilu0_temp_bytes(plan), dtype=torch.uint8, device=values.device)
+        _ilu0_call(plan, temp, values, lu, row_offsets, column_indices, pivot, stream, debug_synchronous)
+        return lu, pivot
+    finally:
+        if own:
+            (stream if stream is not None else torch.cuda.current_stream(plan.device)).synchronize()
+            plan.close()
+
+
+class Ilu0:
+    """The ILU(0) preconditioner of one pattern: the LOWER + UNIT and UPPER + NON_UNIT plans of CsrSv and the temp storage of
+    mspmv_csrilu0_*, made once (the constructor analyses the pattern twice; synchronous).  `factor(values)` factorises -- again and
+    again, on new values of the same pattern -- and returns the pivot tensor (1 int32 on the device: -1, or the smallest row with a
+    missing or zero diagonal); `solve(r)` is U^-1 (L^-1 r), two triangular solves through one kept vector; `close()` releases the
+    plans and the storage.  .lu_values: the factor of the last `factor`."""
+
+    def __init__(self, row_offsets, column_indices, stream=None):
+        import torch
+        self.lower = self.upper = None
+        for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices")):
+            if not isinstance(t, torch.Tensor):
+                raise MspmvError(f"Ilu0: {name} must be a tensor")
+        if not (row_offsets.is_cuda and column_indices.is_cuda):
+            raise MspmvError("Ilu0 needs CUDA (HIP) tensors: the kernels only run on the GPU")
+        self.lower = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=True, stream=stream)
+        self.upper = CsrSv(row_offsets, column_indices, lower=False, unit_diagonal=False, stream=stream)
+        self.device, self.rows, self.nnz = self.lower.device, self.lower.rows, self.lower.nnz
+        self.row_offsets, self.column_indices = row_offsets, column_indices
+        self._temp = torch.empty(_ilu0_temp_bytes(self.lower), dtype=torch.uint8, device=self.device)
+        self.pivot = torch.empty(1, dtype=torch.int32, device=self.device)
+        self.lu_values = None
+        self._mid = None
+
+    def factor(self, values, stream=None, debug_synchronous: bool = False):
+        import torch
+        if self.lower is None:
+            raise MspmvError("Ilu0: closed")
+        _ilu0_check("Ilu0.factor", values, self.row_offsets, self.column_indices, self.lower)
+        if self.lu_values is None or self.lu_values.dtype != values.dtype:
+            self.lu_values = torch.empty(self.nnz, dtype=values.dtype, device=self.device)
+            self._mid = torch.empty(self.rows, dtype=values.dtype, device=self.device)
+        _ilu0_call(self.lower, self._temp, values, self.lu_values, self.row_offsets, self.column_indices, self.pivot, stream, debug_synchronous)
+        return self.pivot
+
+    def solve(self, r, out=None, stream=None):
+        if self.lower is None:
+            raise MspmvError("Ilu0: closed")
+        if self.lu_values is None:
+            raise MspmvError("Ilu0.solve: nothing is factorised yet (call factor(values) first)")
+        self.lower.solve(self.lu_values, r, x=self._mid, stream=stream)
+        return self.upper.solve(self.lu_values, self._mid, x=out, stream=stream)
+
+    def close(self):
+        for plan in (getattr(self, "lower", None), getattr(self, "upper", None)):
+            if plan is not None:
+                plan.close()
+        self.lower = self.upper = None
+        self._temp = self.lu_values = self._mid = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CsrMVPlan:

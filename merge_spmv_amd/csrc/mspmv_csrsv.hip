@@ -34,15 +34,9 @@
 
 #include "../../include/mspmv.h"
 #include "mspmv_internal.hpp"
+#include "mspmv_csrsv_plan.hpp"
 
 #pragma clang fp contract(off)
-
-struct mspmv_csrsv_plan {
-    struct Segment { int32_t level_lo, level_hi, row_lo, row_hi; bool narrow; };
-    mspmv_csrsv_info_t info{};
-    int32_t *d_order = nullptr, *d_level_offsets = nullptr;
-    std::vector<Segment> segments;          // the launches of one solve, in order
-};
 
 namespace {
 
