@@ -704,6 +704,69 @@ int mspmv_csrilu0_f64(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t
                       double *d_values_lu, const int32_t *d_row_offsets, const int32_t *d_column_indices, int32_t *d_pivot,
                       mspmv_stream_t stream, int debug_sync);
 
+/* ---- extension: IC(0), the incomplete Cholesky factorisation without fill-in, level-scheduled (csrc/mspmv_csric0.hip; what
+ * rocsparse_csric0 is in rocSPARSE): A ~ L L^T on the pattern of A's lower triangle, the SYMMETRIC preconditioner that conjugate
+ * gradients needs and ILU(0) cannot give, at half of ILU(0)'s work and half of its factor.  With it a preconditioned CG stays
+ * inside this library: mspmv_csrmv_* for A p, mspmv_csric0_* once per matrix, two mspmv_csrsv_solve_* per iteration.
+ * THE PLAN: lower_plan is any plan made by mspmv_csrsv_plan_create with MSPMV_CSRSV_LOWER (either diag) for this pattern: row i of
+ * the row-wise Cholesky needs the finished rows whose column its strict lower part stores, which is the dependency graph of
+ * L x = b, so the plan's levels, order and segments are the factorisation's too, exactly as for mspmv_csrilu0_*.  rows and nnz are
+ * taken from it; the same plan then serves the L solve (created with MSPMV_CSRSV_NON_UNIT).  An UPPER or a NULL plan is refused.
+ * INPUT: A is rows x rows in CSR, every row SORTED by column with no column twice.  This is NOT checked: on other input the values
+ * are unspecified, but nothing outside the arrays is touched and the call ends.  ONLY THE LOWER TRIANGLE AND THE DIAGONAL ARE READ
+ * AS NUMBERS: the matrix factorised is the symmetric one they define.  The pattern arrays and d_values are not modified unless
+ * d_values_l == d_values (in place), which is allowed; any other overlap is not.
+ * OUTPUT: d_values_l, nnz entries on A's pattern: the strict lower part and the diagonal hold L.
+ * VALUES, defined bit for bit in the value type.  Rows in dependency order; for row i with stored diagonal position d:
+ *     for every stored entry e of row i with j = col[e] < i, in stored (= ascending) order:
+ *         a[e] = a[e] / piv(j)              piv(j) = the FINAL (rooted) diagonal of row j; +0.0 if row j stores no diagonal
+ *         for every stored entry g of row i behind e with k = col[g], j < k < i,
+ *             for which row k stores column j, at position f:       a[g] = a[g] - a[e] * a[f]
+ *         if row i stores its diagonal:                              a[d] = a[d] - a[e] * a[e]
+ *     a[d] = sqrt(a[d])
+ * every divide, multiply, subtract and root rounded on its own (no fused multiply-add; division and square root correctly
+ * rounded), nothing flushed to zero.  So a[g] is a function of A's lower triangle and the pattern alone -- not of levels, segments,
+ * lanes per row, alignment or the kernel that ran.  A missing diagonal acts as a pivot of +0.0; a negative value under the root
+ * gives the IEEE NaN: the definition is total.  Entries with column > i are copied unchanged when mirror == 0.
+ * PIVOT: *d_pivot (one int32 ON THE DEVICE; may be NULL) = the smallest row whose diagonal is not stored or whose value under the
+ * root compares <= 0 (so -0.0 counts, NaN does not); -1 if there is none.  The host does not learn it inside the call.
+ * MIRROR: with mirror == 1 one more launch, after the factorisation, writes L^T into the upper triangle: entry (i, j) with j > i
+ * receives the final a[f] of entry (j, i) if row j stores column i, else +0.0.  The array is then L\L^T in A's layout, and
+ * mspmv_csrsv_* sweeps it with LOWER + NON_UNIT and UPPER + NON_UNIT, nothing extracted and nothing transposed.  This needs a
+ * STRUCTURALLY SYMMETRIC pattern (merge_spmv_amd.csr_symmetrize, mspmv_csr_add_* of A and A^T, makes one): a lower entry without an upper
+ * partner is simply absent from the upper sweep, which then solves with another matrix than L^T.  With mirror == 0 the route for
+ * other patterns stays mspmv_csr_transpose_* of the factor followed by an UPPER solve.
+ * TEMP STORAGE, two-phase: d_temp == NULL writes the size to *temp_bytes, does no work and needs no device.  d_temp is 16-byte
+ * aligned and holds the diagonal position of every row: 4 * rows bytes rounded up to 16, at least 16.
+ * SCHEDULE: one prologue launch (each row's diagonal position by bisection; the copy of d_values to d_values_l when they differ;
+ * rows without a stored diagonal go to *d_pivot), then one launch per segment of the plan, then the mirror: 1 + info.launches +
+ * mirror in all.  A row is worked by G consecutive lanes of one wave, G = mspmv_csric0_group(rows, nnz): the smallest power of two
+ * >= ceil((nnz + rows) / (2 rows)), the mean length of a row's lower-plus-diagonal part under a symmetric pattern, within [1, 64];
+ * a function of rows and nnz alone (host only, launches nothing).  Each lane owns every G-th entry of the row up to the diagonal;
+ * the quotient of a lower entry reaches the group by a shuffle; an owned entry of column k looks the quotient's column up in row k
+ * by bisection.  No workgroup waits for another.
+ * Asynchronous on `stream`; allocates nothing, reads nothing back, launches the same kernels whatever the values and can be
+ * captured in a graph; debug_sync prints one line per launch with the lanes per row and waits for it; returns 0 or a hipError_t.
+ * LIMITS, refused before anything is launched: a NULL or UPPER plan; a NULL temp_bytes; mirror not in {0, 1}; *temp_bytes too
+ * small; a misaligned d_temp; NULL value or pattern arrays with nnz > 0.  rows == 0 succeeds and launches nothing.  nnz == 0 with
+ * rows > 0 reports pivot 0.
+ * Measured on MI355X against rocsparse_csric0 (analysis outside the timing; out of place, the copy included, mirror == 0; profiles/
+ * csric0_bench.txt; DESIGN.md 4 "IC(0)") and against mspmv_csrilu0_* on the same plan and arrays in the same run, fp32 / fp64: a
+ * 5-point grid of 2000 x 2000 21.9 / 25.8 ms against 121 / 122 ms (ILU(0): 22.0 / 27.0 ms); a 7-point grid of 128^3 2.89 / 3.02 ms
+ * against 75.0 / 75.2 ms (ILU(0): 2.91 / 3.16 ms); the mirror adds 0.03 - 0.08 ms.  IC(0) does half of ILU(0)'s arithmetic and is
+ * only 1 - 5 % faster: both are bound by the launches (one per level), not by the rows.  A + A^T + I of an R-MAT graph of scale 14
+ * (rows of thousands of entries, one group each) 667 / 677 ms against 6.5 / 6.5 ms: rocSPARSE is 100 times faster there, and ILU(0)
+ * (613 / 623 ms, 32 lanes per row against IC(0)'s 16) is 8 % faster than this call; at scale 16, where one group would run for
+ * seconds, this call was not run at all (rocSPARSE: 44 / 45 ms).  G by the sweep on the two grids: the rule's 4 is the fastest of
+ * 1 ... 64 on both. ---- */
+int mspmv_csric0_group(int32_t rows, int32_t nnz, int32_t *lanes_per_row);
+int mspmv_csric0_f32(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t *temp_bytes, const float *d_values,
+                     float *d_values_l, const int32_t *d_row_offsets, const int32_t *d_column_indices, int32_t mirror,
+                     int32_t *d_pivot, mspmv_stream_t stream, int debug_sync);
+int mspmv_csric0_f64(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t *temp_bytes, const double *d_values,
+                     double *d_values_l, const int32_t *d_row_offsets, const int32_t *d_column_indices, int32_t mirror,
+                     int32_t *d_pivot, mspmv_stream_t stream, int debug_sync);
+
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */
 typedef struct mspmv_launch_info {

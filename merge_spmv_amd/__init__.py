@@ -18,7 +18,7 @@ import os
 from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
-           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv", "csrilu0", "Ilu0",
+           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv", "csrilu0", "Ilu0", "csric0", "Ic0",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -220,6 +220,11 @@ def load_library() -> ctypes.CDLL:
     for name in ("mspmv_csrilu0_f32", "mspmv_csrilu0_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [vp, vp, sz_p, vp, vp, vp, vp, vp, vp, ctypes.c_int]
+    lib.mspmv_csric0_group.restype = ctypes.c_int
+    lib.mspmv_csric0_group.argtypes = [i32, i32, ctypes.POINTER(i32)]
+    for name in ("mspmv_csric0_f32", "mspmv_csric0_f64"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, vp, sz_p, vp, vp, vp, vp, i32, vp, vp, ctypes.c_int]
     lib.mspmv_csr_gemm_products.restype = ctypes.c_int
     lib.mspmv_csr_gemm_products.argtypes = [vp, sz_p, vp, vp, i32, i32, i32, vp, i32, vp, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_skew.restype = ctypes.c_int
@@ -1338,6 +1343,111 @@ class Ilu0:
                 plan.close()
         self.lower = self.upper = None
         self._temp = self.lu_values = self._mid = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csric0_group(rows: int, nnz: int) -> int:
+    """G, the lanes of one wave that work one row of mspmv_csric0_*: a function of rows and nnz alone (host only)."""
+    g = ctypes.c_int32(0)
+    _check(load_library().mspmv_csric0_group(int(rows), int(nnz), ctypes.byref(g)), "mspmv_csric0_group")
+    return int(g.value)
+
+
+def _ic0_temp_bytes(plan) -> int:
+    size = ctypes.c_size_t(0)
+    _check(plan._lib.mspmv_csric0_f32(plan._handle, None, ctypes.byref(size), None, None, None, None, 0, None, None, 0), "mspmv_csric0 (size query)")
+    return int(size.value)
+
+
+def _ic0_call(plan, temp, values, l, row_offsets, column_indices, mirror, pivot, stream, debug_synchronous):
+    import torch
+    fn = plan._lib.mspmv_csric0_f32 if values.dtype == torch.float32 else plan._lib.mspmv_csric0_f64
+    size = ctypes.c_size_t(temp.numel())
+    with torch.cuda.device(plan.device):
+        _check(int(fn(plan._handle, ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), _ptr(values), _ptr(l), _ptr(row_offsets),
+                      _ptr(column_indices), int(bool(mirror)), _ptr(pivot), _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_csric0")
+
+
+def csric0(values, row_offsets, column_indices, plan=None, out=None, mirror: bool = False, stream=None, debug_synchronous: bool = False):
+    """IC(0) of the CSR matrix (sorted rows, no column twice) on the pattern of its lower triangle (mspmv_csric0_*): returns
+    (l_values, pivot).  Only the lower triangle and the diagonal are read as numbers.  l_values: L in the lower part and on the diagonal
+    of A's layout; the upper part is A's, unchanged, or with `mirror` L^T (entry (i, j) = the final entry (j, i), +0.0 where row j does
+    not store column i) -- what CsrSv then sweeps with lower=True and lower=False, both with unit_diagonal=False.  pivot: a 1-element
+    int32 DEVICE tensor (the smallest row whose diagonal is missing or whose value under the root is <= 0, -1 if none), so nothing
+    waits for the device.  `plan`: a LOWER CsrSv of this pattern (one is made and dropped if not given; a loop keeps an Ic0).  `out`:
+    where the factor goes; may be `values` (in place)."""
+    import torch
+    rows, nnz = _ilu0_check("csric0", values, row_offsets, column_indices, plan, out)
+    own = plan is None
+    if own:
+        plan = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=False, stream=stream)
+    try:
+        l = out if out is not None else torch.empty(nnz, dtype=values.dtype, device=values.device)
+        pivot = torch.empty(1, dtype=torch.int32, device=values.device)
+        temp = torch.empty(_ic0_temp_bytes(plan), dtype=torch.uint8, device=values.device)
+        _ic0_call(plan, temp, values, l, row_offsets, column_indices, mirror, pivot, stream, debug_synchronous)
+        return l, pivot
+    finally:
+        if own:
+            (stream if stream is not None else torch.cuda.current_stream(plan.device)).synchronize()
+            plan.close()
+
+
+class Ic0:
+    """The IC(0) preconditioner of one (structurally symmetric) pattern: the LOWER + NON_UNIT and UPPER + NON_UNIT plans of CsrSv and
+    the temp storage of mspmv_csric0_*, made once (the constructor analyses the pattern twice; synchronous).  `factor(values)`
+    factorises with the mirror -- again and again, on new values of the same pattern -- and returns the pivot tensor (1 int32 on the
+    device: -1, or the smallest row whose diagonal is missing or whose value under the root is <= 0); `solve(r)` is
+    L^-T (L^-1 r), two triangular solves through one kept vector (a pattern that lacks a diagonal is refused there by the NON_UNIT
+    plan, as it is); `close()` releases the plans and the storage.  .l_values: the factor of the last `factor`: L below and on the diagonal, L^T above it, in A's layout."""
+
+    def __init__(self, row_offsets, column_indices, stream=None):
+        import torch
+        self.lower = self.upper = None
+        for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices")):
+            if not isinstance(t, torch.Tensor):
+                raise MspmvError(f"Ic0: {name} must be a tensor")
+        if not (row_offsets.is_cuda and column_indices.is_cuda):
+            raise MspmvError("Ic0 needs CUDA (HIP) tensors: the kernels only run on the GPU")
+        self.lower = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=False, stream=stream)
+        self.upper = CsrSv(row_offsets, column_indices, lower=False, unit_diagonal=False, stream=stream)
+        self.device, self.rows, self.nnz = self.lower.device, self.lower.rows, self.lower.nnz
+        self.row_offsets, self.column_indices = row_offsets, column_indices
+        self._temp = torch.empty(_ic0_temp_bytes(self.lower), dtype=torch.uint8, device=self.device)
+        self.pivot = torch.empty(1, dtype=torch.int32, device=self.device)
+        self.l_values = None
+        self._mid = None
+
+    def factor(self, values, stream=None, debug_synchronous: bool = False):
+        import torch
+        if self.lower is None:
+            raise MspmvError("Ic0: closed")
+        _ilu0_check("Ic0.factor", values, self.row_offsets, self.column_indices, self.lower)
+        if self.l_values is None or self.l_values.dtype != values.dtype:
+            self.l_values = torch.empty(self.nnz, dtype=values.dtype, device=self.device)
+            self._mid = torch.empty(self.rows, dtype=values.dtype, device=self.device)
+        _ic0_call(self.lower, self._temp, values, self.l_values, self.row_offsets, self.column_indices, True, self.pivot, stream, debug_synchronous)
+        return self.pivot
+
+    def solve(self, r, out=None, stream=None):
+        if self.lower is None:
+            raise MspmvError("Ic0: closed")
+        if self.l_values is None:
+            raise MspmvError("Ic0.solve: nothing is factorised yet (call factor(values) first)")
+        self.lower.solve(self.l_values, r, x=self._mid, stream=stream)
+        return self.upper.solve(self.l_values, self._mid, x=out, stream=stream)
+
+    def close(self):
+        for plan in (getattr(self, "lower", None), getattr(self, "upper", None)):
+            if plan is not None:
+                plan.close()
+        self.lower = self.upper = None
+        self._temp = self.l_values = self._mid = None
 
     def __del__(self):
         try:
