@@ -654,6 +654,61 @@ int mspmv_csrsv_solve_f64(mspmv_csrsv_plan_t *plan, const double *d_values, cons
                           mspmv_stream_t stream, int debug_sync);
 int mspmv_csrsv_plan_destroy(mspmv_csrsv_plan_t *plan);
 
+/* ---- extension: the sparse triangular solve for k right-hand sides  op(A) X = alpha * B, level-scheduled (csrc/mspmv_csrsm.hip; what
+ * rocsparse_csrsm / rocsparse_spsm is in rocSPARSE): the two sweeps of a preconditioner inside a block Krylov method, a solver that
+ * carries several right-hand sides, a Gauss-Seidel smoother on k vectors.  One chain of launches serves all k columns, where k calls
+ * of mspmv_csrsv_solve_* pay the chain k times.
+ * THE PLAN is any mspmv_csrsv_plan_t, used as made: the same triangle, the same diagonal rule, the same pattern contract, the same
+ * levels, order[] and level_offsets[].  There is no new analysis and no new plan type; one plan serves mspmv_csrsv_solve_* and
+ * mspmv_csrsm_solve_* for any k, in any order.
+ * INPUTS: A as for mspmv_csrsv_*.  B and X are rows x k, ROW-MAJOR, with leading dimensions ldb, ldx >= k in elements: exactly the
+ * layout of Y in mspmv_csrmm_*, so the output of mspmv_csrmm_* feeds the solve and back with no copy.
+ * VALUES, defined bit for bit in the value type: column j of X is what mspmv_csrsv_solve_* gives for column j of B.  For row r and
+ * right-hand side j:
+ *     s = +0.0;  for every stored entry e of row r in stored order whose column c is in the strict triangle:  s = s + a[e] * X[c, j]
+ *     t = alpha * B[r, j]
+ *     X[r, j] = (t - s) / d     (NON_UNIT; d = the row's one stored diagonal value)          X[r, j] = t - s     (UNIT)
+ * every operation rounded on its own (no fused multiply-add), nothing flushed to zero.  The bits depend on none of k, ldb, ldx, P, the
+ * schedule, the alignment or the kernel that ran.  X[r, j] for j in [k, ldx) is never written; B's padding is never read.
+ * d_x == d_b with ldx == ldb (in place) is allowed; any other overlap is not.  The matrix arrays and B are not modified.
+ * MAPPING: P = info.lanes_per_row = the smallest power of two >= min(k, 64) adjacent lanes of one wave work one row.  Lane j of the
+ * group takes the right-hand sides j, j + 64, ... (info.passes = ceil(k / 64) of them, each a pass of its own over the row); a lane
+ * with j >= k idles.  The group reads cols[e] and vals[e] at one address and gathers X[c, j .. j + P) in one coalesced request.
+ * One lane still adds one (row, right-hand side) sum serially: a row of L strict entries costs L multiply-adds per pass.  All index
+ * arithmetic on B and X is 64-bit (rows * ld may exceed 2^31).
+ * SCHEDULE: a level of n rows is narrow for this k when n * P <= info.narrow_lanes (256: the lanes of csrsv's W = 256, so that k = 1
+ * launches what mspmv_csrsv_solve_* launches).  A maximal run of consecutive narrow levels is ONE launch of ONE workgroup of 1024
+ * threads that walks its levels with a workgroup barrier between them; every other level is one launch of ceil(n * P / 256)
+ * workgroups.  The cut depends on P, so it is made on the host from the plan's copy of level_offsets[] while the solve walks them;
+ * mspmv_csrsm_info applies the same rule and states the count: info.launches is a function of the pattern, k and the budget alone.
+ * Nothing else orders two levels: no flags, no spinning, no cooperative launch.  A solve allocates nothing on the device or the
+ * host, reads nothing back, launches the same kernels whatever the values and can be captured in a graph.
+ * mspmv_csrsm_info is host only and touches no device.  The solve is asynchronous on `stream`; debug_sync prints one line per launch
+ * (sm_narrow_kernel or sm_level_kernel) and waits for it; returns 0 or a hipError_t.
+ * LIMITS, refused before anything is launched: a NULL plan (or, for mspmv_csrsm_info, NULL info); a plan whose bad_diagonal_row >= 0;
+ * k < 1; ldb < k or ldx < k; NULL B or X with rows > 0; NULL matrix arrays with nnz > 0.  rows == 0 succeeds and touches no device.
+ * nnz == 0 with UNIT gives X = alpha * B (the matrix arrays may be NULL).
+ * Measured on MI355X (profiles/csrsm_bench.txt; DESIGN.md 4 "Triangular solve, several right-hand sides"), fp64, one solve against k
+ * calls of mspmv_csrsv_solve_* on the columns copied out to vectors / against rocsparse_spsm (analysis outside the timing): the lower
+ * part of a 5-point grid of 2000 x 2000 at k = 16 18.5 ms against 302 / 138 ms, at k = 64 19.6 ms against 1220 / 147 ms; the ILU(0)
+ * pattern of a 7-point grid of 128^3 at k = 16 2.36 ms against 37.2 / 85.6 ms; at k = 1 the time of mspmv_csrsv_solve_* within the
+ * spread.  The strict lower triangle of an R-MAT graph of scale 20 (long rows, one lane per right-hand side each) at k = 16 322 ms
+ * against 4096 / 174 ms: rocSPARSE stays 1.9 times faster there.  narrow_lanes = 256 by the sweep on the two grids. ---- */
+typedef struct mspmv_csrsm_info {
+    int32_t k;
+    int32_t lanes_per_row;   /* P: the smallest power of two >= min(k, 64)                        */
+    int32_t passes;          /* ceil(k / 64): right-hand sides one lane takes, one after the other */
+    int32_t narrow_lanes;    /* the lane budget up to which a level is narrow (above)             */
+    int32_t launches;        /* kernels ONE solve with this k launches: pattern, k and budget alone */
+} mspmv_csrsm_info_t;
+int mspmv_csrsm_info(const mspmv_csrsv_plan_t *plan, int32_t k, mspmv_csrsm_info_t *info);
+int mspmv_csrsm_solve_f32(mspmv_csrsv_plan_t *plan, const float *d_values, const int32_t *d_row_offsets,
+                          const int32_t *d_column_indices, float alpha, const float *d_b, int32_t ldb,
+                          float *d_x, int32_t ldx, int32_t k, mspmv_stream_t stream, int debug_sync);
+int mspmv_csrsm_solve_f64(mspmv_csrsv_plan_t *plan, const double *d_values, const int32_t *d_row_offsets,
+                          const int32_t *d_column_indices, double alpha, const double *d_b, int32_t ldb,
+                          double *d_x, int32_t ldx, int32_t k, mspmv_stream_t stream, int debug_sync);
+
 /* ---- extension: ILU(0), the incomplete LU factorisation without fill-in, level-scheduled (csrc/mspmv_csrilu0.hip; what
  * rocsparse_csrilu0 is in rocSPARSE): A ~ L U on A's own pattern, the preconditioner whose two sweeps mspmv_csrsv_* solves.  With it
  * a preconditioned Krylov iteration stays inside this library: mspmv_csrmv_* for A p, mspmv_csrilu0_* once per matrix, two

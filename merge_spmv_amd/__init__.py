@@ -18,7 +18,7 @@ import os
 from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
-           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv", "csrilu0", "Ilu0", "csric0", "Ic0",
+           "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv", "csrsm", "csrilu0", "Ilu0", "csric0", "Ic0",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -66,6 +66,11 @@ class _CsrSvInfo(ctypes.Structure):
                 ("levels", ctypes.c_int32), ("launches", ctypes.c_int32), ("narrow_rows", ctypes.c_int32),
                 ("max_level_rows", ctypes.c_int32), ("bad_diagonal_row", ctypes.c_int32), ("used_entries", ctypes.c_int64),
                 ("device_bytes", ctypes.c_uint64)]
+
+
+class _CsrSmInfo(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("lanes_per_row", ctypes.c_int32), ("passes", ctypes.c_int32), ("narrow_lanes", ctypes.c_int32),
+                ("launches", ctypes.c_int32)]
 
 
 class _LaunchInfo(ctypes.Structure):
@@ -215,6 +220,12 @@ def load_library() -> ctypes.CDLL:
         fn.argtypes = [vp, vp, vp, vp, ct, vp, vp, vp, ctypes.c_int]
     lib.mspmv_csrsv_plan_destroy.restype = ctypes.c_int
     lib.mspmv_csrsv_plan_destroy.argtypes = [vp]
+    lib.mspmv_csrsm_info.restype = ctypes.c_int
+    lib.mspmv_csrsm_info.argtypes = [vp, i32, ctypes.POINTER(_CsrSmInfo)]
+    for name, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+        fn = getattr(lib, "mspmv_csrsm_solve_" + name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, ct, vp, i32, vp, i32, i32, vp, ctypes.c_int]
     lib.mspmv_csrilu0_group.restype = ctypes.c_int
     lib.mspmv_csrilu0_group.argtypes = [i32, i32, ctypes.POINTER(i32)]
     for name in ("mspmv_csrilu0_f32", "mspmv_csrilu0_f64"):
@@ -1191,6 +1202,40 @@ class CsrSv:
                       _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_csrsv_solve")
         return x
 
+    def many_info(self, k: int) -> dict:
+        """The figures of mspmv_csrsm_info for k right-hand sides on this plan: k, lanes_per_row (P), passes, narrow_lanes, launches."""
+        if self._handle is None:
+            raise MspmvError("CsrSv: the plan is closed")
+        raw = _CsrSmInfo()
+        _check(self._lib.mspmv_csrsm_info(self._handle, int(k), ctypes.byref(raw)), "mspmv_csrsm_info")
+        return {name: int(getattr(raw, name)) for name, _ in _CsrSmInfo._fields_}
+
+    def solve_many(self, values, B, X=None, alpha: float = 1.0, stream=None, debug_synchronous: bool = False):
+        """X = the solution of op(A) X = alpha * B for the k columns of B (mspmv_csrsm_solve_*), column j bit for bit what `solve` gives
+        for column j.  B and X: [rows, k], row-major (stride(1) == 1, stride(0) >= k: the leading dimension is the stride, as in csrmm);
+        X may be B (in place).  Asynchronous on `stream`; many_info(k)["launches"] launches, nothing allocated but a missing X."""
+        import torch
+        if self._handle is None:
+            raise MspmvError("CsrSv: the plan is closed")
+        k = _many_layout("CsrSv.solve_many", values, B, X)
+        if not (values.is_cuda and B.is_cuda):
+            raise MspmvError("CsrSv.solve_many needs CUDA (HIP) tensors: the kernels only run on the GPU")
+        if X is None:
+            X = torch.empty(self.rows, k, dtype=B.dtype, device=self.device)
+        if values.device != self.device or values.dim() != 1 or not values.is_contiguous() or values.numel() != self.nnz:
+            raise MspmvError(f"CsrSv.solve_many: values must be a contiguous 1-D tensor of {self.nnz} entries on {self.device}")
+        for t, name in ((B, "B"), (X, "X")):
+            if t.device != self.device or t.shape != (self.rows, k):
+                raise MspmvError(f"CsrSv.solve_many: {name} must be a [{self.rows}, {k}] tensor on {self.device}")
+        if self.info["bad_diagonal_row"] >= 0:
+            raise MspmvError(f"CsrSv.solve_many: row {self.info['bad_diagonal_row']} has no or more than one stored diagonal entry")
+        ldb = B.stride(0) if self.rows > 1 else k
+        ldx = X.stride(0) if self.rows > 1 else k
+        fn, ct = (self._lib.mspmv_csrsm_solve_f32, ctypes.c_float) if B.dtype == torch.float32 else (self._lib.mspmv_csrsm_solve_f64, ctypes.c_double)
+        _check(int(fn(self._handle, _ptr(values), _ptr(self.row_offsets), _ptr(self.column_indices), ct(alpha), _ptr(B), int(ldb), _ptr(X),
+                      int(ldx), k, _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_csrsm_solve")
+        return X
+
     def close(self):
         if getattr(self, "_handle", None) is not None:
             handle, self._handle = self._handle, None
@@ -1212,6 +1257,50 @@ def csrsv(values, row_offsets, column_indices, b, lower: bool = True, unit_diago
         import torch
         torch.cuda.current_stream(plan.device).synchronize()
         plan.close()
+
+
+def _many_layout(what, values, B, X) -> int:
+    """the refusals of solve_many / csrsm that need neither a plan nor a device: B (and X) 2-D, row-major, of one value type; returns k"""
+    import torch
+    for t, name in ((values, "values"), (B, "B")) + (((X, "X"),) if X is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise MspmvError(f"{what}: {name} must be a tensor")
+    for t, name in ((B, "B"),) + (((X, "X"),) if X is not None else ()):
+        if t.dim() != 2 or t.shape[1] < 1:
+            raise MspmvError(f"{what}: {name} must be 2-D, [rows, k] with k >= 1")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise MspmvError(f"{what}: {name} must have unit stride along the right-hand-side index (row-major)")
+        if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+            raise MspmvError(f"{what}: the leading dimension of {name} (stride(0)) must be at least k (no overlapping / broadcast rows)")
+    if B.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{what} is instantiated for float32 and float64, got {B.dtype}")
+    if values.dtype != B.dtype:
+        raise TypeError(f"{what}: values hold {values.dtype}, B {B.dtype}")
+    if X is not None and X.dtype != B.dtype:
+        raise TypeError(f"{what}: X must be a {B.dtype} tensor")
+    return int(B.shape[1])
+
+
+def csrsm(values, row_offsets, column_indices, B, lower: bool = True, unit_diagonal: bool = False, alpha: float = 1.0):
+    """One-shot triangular solve for the k columns of B ([rows, k], row-major): analyse the pattern, solve op(A) X = alpha * B, drop
+    the plan.  A loop keeps a CsrSv and calls solve_many."""
+    _many_layout("csrsm", values, B, None)
+    plan = CsrSv(row_offsets, column_indices, lower=lower, unit_diagonal=unit_diagonal)
+    try:
+        return plan.solve_many(values, B, alpha=alpha)
+    finally:
+        import torch
+        torch.cuda.current_stream(plan.device).synchronize()
+        plan.close()
+
+
+def _mid_block(kept, what, factor, R):
+    """the rows x k block between the two sweeps of a preconditioner: the kept one, or a new one when k or the dtype changed"""
+    import torch
+    k = _many_layout(what, factor, R, None)
+    if kept is None or kept.dtype != R.dtype or kept.shape != (R.shape[0], k):
+        kept = torch.empty(R.shape[0], k, dtype=R.dtype, device=R.device)
+    return kept
 
 
 def csrilu0_group(rows: int, nnz: int) -> int:
@@ -1317,6 +1406,7 @@ class Ilu0:
         self.pivot = torch.empty(1, dtype=torch.int32, device=self.device)
         self.lu_values = None
         self._mid = None
+        self._mid_many = None
 
     def factor(self, values, stream=None, debug_synchronous: bool = False):
         import torch
@@ -1337,12 +1427,23 @@ class Ilu0:
         self.lower.solve(self.lu_values, r, x=self._mid, stream=stream)
         return self.upper.solve(self.lu_values, self._mid, x=out, stream=stream)
 
+    def solve_many(self, R, out=None, stream=None):
+        """U^-1 (L^-1 R) for the k columns of R ([rows, k], row-major): two solve_many sweeps through one kept rows x k block
+        (allocated when k or the dtype changes); column j is bit for bit solve(R[:, j])."""
+        if self.lower is None:
+            raise MspmvError("Ilu0: closed")
+        if self.lu_values is None:
+            raise MspmvError("Ilu0.solve_many: nothing is factorised yet (call factor(values) first)")
+        self._mid_many = _mid_block(self._mid_many, "Ilu0.solve_many", self.lu_values, R)
+        self.lower.solve_many(self.lu_values, R, X=self._mid_many, stream=stream)
+        return self.upper.solve_many(self.lu_values, self._mid_many, X=out, stream=stream)
+
     def close(self):
         for plan in (getattr(self, "lower", None), getattr(self, "upper", None)):
             if plan is not None:
                 plan.close()
         self.lower = self.upper = None
-        self._temp = self.lu_values = self._mid = None
+        self._temp = self.lu_values = self._mid = self._mid_many = None
 
     def __del__(self):
         try:
@@ -1422,6 +1523,7 @@ class Ic0:
         self.pivot = torch.empty(1, dtype=torch.int32, device=self.device)
         self.l_values = None
         self._mid = None
+        self._mid_many = None
 
     def factor(self, values, stream=None, debug_synchronous: bool = False):
         import torch
@@ -1442,12 +1544,23 @@ class Ic0:
         self.lower.solve(self.l_values, r, x=self._mid, stream=stream)
         return self.upper.solve(self.l_values, self._mid, x=out, stream=stream)
 
+    def solve_many(self, R, out=None, stream=None):
+        """L^-T (L^-1 R) for the k columns of R ([rows, k], row-major): two solve_many sweeps through one kept rows x k block
+        (allocated when k or the dtype changes); column j is bit for bit solve(R[:, j])."""
+        if self.lower is None:
+            raise MspmvError("Ic0: closed")
+        if self.l_values is None:
+            raise MspmvError("Ic0.solve_many: nothing is factorised yet (call factor(values) first)")
+        self._mid_many = _mid_block(self._mid_many, "Ic0.solve_many", self.l_values, R)
+        self.lower.solve_many(self.l_values, R, X=self._mid_many, stream=stream)
+        return self.upper.solve_many(self.l_values, self._mid_many, X=out, stream=stream)
+
     def close(self):
         for plan in (getattr(self, "lower", None), getattr(self, "upper", None)):
             if plan is not None:
                 plan.close()
         self.lower = self.upper = None
-        self._temp = self.l_values = self._mid = None
+        self._temp = self.l_values = self._mid = self._mid_many = None
 
     def __del__(self):
         try:

@@ -387,6 +387,7 @@ static int sv_analyse(mspmv_csrsv_plan &p, const int32_t *d_off, const int32_t *
     }
     if (hipStreamSynchronize(stream) != hipSuccess) return hipErrorInvalidValue;
     sv_segments(p, h_lo);
+    p.h_level_offsets = std::move(h_lo);                            // (kept for mspmv_csrsm_*, whose cut depends on k)
     return hipSuccess;
 }
 
