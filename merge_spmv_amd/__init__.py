@@ -1345,19 +1345,57 @@ def _ilu0_check(what, values, row_offsets, column_indices, plan=None, out=None):
     return rows, nnz
 
 
-def _ilu0_temp_bytes(plan) -> int:
+def _factor_temp_bytes(plan, family, extra) -> int:
+    """the size query of mspmv_csrilu0_* / mspmv_csric0_* (`extra`: the arguments between column_indices and d_pivot)"""
     size = ctypes.c_size_t(0)
-    _check(plan._lib.mspmv_csrilu0_f32(plan._handle, None, ctypes.byref(size), None, None, None, None, None, None, 0), "mspmv_csrilu0 (size query)")
+    fn = getattr(plan._lib, f"mspmv_{family}_f32")
+    _check(fn(plan._handle, None, ctypes.byref(size), None, None, None, None, *extra, None, None, 0), f"mspmv_{family} (size query)")
     return int(size.value)
 
 
-def _ilu0_call(plan, temp, values, lu, row_offsets, column_indices, pivot, stream, debug_synchronous):
+def _factor_call(plan, family, extra, temp, values, out, row_offsets, column_indices, pivot, stream, debug_synchronous):
     import torch
-    fn = plan._lib.mspmv_csrilu0_f32 if values.dtype == torch.float32 else plan._lib.mspmv_csrilu0_f64
+    fn = getattr(plan._lib, f"mspmv_{family}_f32" if values.dtype == torch.float32 else f"mspmv_{family}_f64")
     size = ctypes.c_size_t(temp.numel())
     with torch.cuda.device(plan.device):
-        _check(int(fn(plan._handle, ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), _ptr(values), _ptr(lu), _ptr(row_offsets),
-                      _ptr(column_indices), _ptr(pivot), _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_csrilu0")
+        _check(int(fn(plan._handle, ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), _ptr(values), _ptr(out), _ptr(row_offsets),
+                      _ptr(column_indices), *extra, _ptr(pivot), _stream_handle(stream), int(bool(debug_synchronous)))), f"mspmv_{family}")
+
+
+def _ilu0_temp_bytes(plan) -> int:
+    return _factor_temp_bytes(plan, "csrilu0", ())
+
+
+def _ilu0_call(plan, temp, values, lu, row_offsets, column_indices, pivot, stream, debug_synchronous):
+    _factor_call(plan, "csrilu0", (), temp, values, lu, row_offsets, column_indices, pivot, stream, debug_synchronous)
+
+
+def _ic0_temp_bytes(plan) -> int:
+    return _factor_temp_bytes(plan, "csric0", (0,))
+
+
+def _ic0_call(plan, temp, values, l, row_offsets, column_indices, mirror, pivot, stream, debug_synchronous):
+    _factor_call(plan, "csric0", (int(bool(mirror)),), temp, values, l, row_offsets, column_indices, pivot, stream, debug_synchronous)
+
+
+def _factor_once(what, unit_diagonal, temp_bytes, call, values, row_offsets, column_indices, plan, out, stream):
+    """csrilu0 / csric0: the plan given or one of its own, out / pivot / temp allocated, `call(plan, temp, out, pivot)`; a plan of its
+    own is dropped after the stream has finished"""
+    import torch
+    rows, nnz = _ilu0_check(what, values, row_offsets, column_indices, plan, out)
+    own = plan is None
+    if own:
+        plan = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=unit_diagonal, stream=stream)
+    try:
+        factor = out if out is not None else torch.empty(nnz, dtype=values.dtype, device=values.device)
+        pivot = torch.empty(1, dtype=torch.int32, device=values.device)
+        temp = torch.empty(temp_bytes(plan), dtype=torch.uint8, device=values.device)
+        call(plan, temp, factor, pivot)
+        return factor, pivot
+    finally:
+        if own:
+            (stream if stream is not None else torch.cuda.current_stream(plan.device)).synchronize()
+            plan.close()
 
 
 def csrilu0(values, row_offsets, column_indices, plan=None, out=None, stream=None, debug_synchronous: bool = False):
@@ -1366,112 +1404,9 @@ def csrilu0(values, row_offsets, column_indices, plan=None, out=None, stream=Non
     unit_diagonal=True and lower=False.  pivot: a 1-element int32 DEVICE tensor (the smallest row with a missing or zero diagonal, -1
     if none), so nothing waits for the device.  `plan`: a LOWER CsrSv of this pattern (one is made and dropped if not given; a loop
     keeps an Ilu0).  `out`: where the factor goes; may be `values` (in place)."""
-    import torch
-    rows, nnz = _ilu0_check("csrilu0", values, row_offsets, column_indices, plan, out)
-    own = plan is None
-    if own:
-        plan = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=True, stream=stream)
-    try:
-        lu = out if out is not None else torch.empty(nnz, dtype=values.dtype, device=values.device)
-        pivot = torch.empty(1, dtype=torch.int32, device=values.device)
-        temp = torch.empty(_ilu0_temp_bytes(plan), dtype=torch.uint8, device=values.device)
+    def call(plan, temp, lu, pivot):
         _ilu0_call(plan, temp, values, lu, row_offsets, column_indices, pivot, stream, debug_synchronous)
-        return lu, pivot
-    finally:
-        if own:
-            (stream if stream is not None else torch.cuda.current_stream(plan.device)).synchronize()
-            plan.close()
-
-
-class Ilu0:
-    """The ILU(0) preconditioner of one pattern: the LOWER + UNIT and UPPER + NON_UNIT plans of CsrSv and the temp storage of
-    mspmv_csrilu0_*, made once (the constructor analyses the pattern twice; synchronous).  `factor(values)` factorises -- again and
-    again, on new values of the same pattern -- and returns the pivot tensor (1 int32 on the device: -1, or the smallest row with a
-    missing or zero diagonal); `solve(r)` is U^-1 (L^-1 r), two triangular solves through one kept vector; `close()` releases the
-    plans and the storage.  .lu_values: the factor of the last `factor`."""
-
-    def __init__(self, row_offsets, column_indices, stream=None):
-        import torch
-        self.lower = self.upper = None
-        for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices")):
-            if not isinstance(t, torch.Tensor):
-                raise MspmvError(f"Ilu0: {name} must be a tensor")
-        if not (row_offsets.is_cuda and column_indices.is_cuda):
-            raise MspmvError("Ilu0 needs CUDA (HIP) tensors: the kernels only run on the GPU")
-        self.lower = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=True, stream=stream)
-        self.upper = CsrSv(row_offsets, column_indices, lower=False, unit_diagonal=False, stream=stream)
-        self.device, self.rows, self.nnz = self.lower.device, self.lower.rows, self.lower.nnz
-        self.row_offsets, self.column_indices = row_offsets, column_indices
-        self._temp = torch.empty(_ilu0_temp_bytes(self.lower), dtype=torch.uint8, device=self.device)
-        self.pivot = torch.empty(1, dtype=torch.int32, device=self.device)
-        self.lu_values = None
-        self._mid = None
-        self._mid_many = None
-
-    def factor(self, values, stream=None, debug_synchronous: bool = False):
-        import torch
-        if self.lower is None:
-            raise MspmvError("Ilu0: closed")
-        _ilu0_check("Ilu0.factor", values, self.row_offsets, self.column_indices, self.lower)
-        if self.lu_values is None or self.lu_values.dtype != values.dtype:
-            self.lu_values = torch.empty(self.nnz, dtype=values.dtype, device=self.device)
-            self._mid = torch.empty(self.rows, dtype=values.dtype, device=self.device)
-        _ilu0_call(self.lower, self._temp, values, self.lu_values, self.row_offsets, self.column_indices, self.pivot, stream, debug_synchronous)
-        return self.pivot
-
-    def solve(self, r, out=None, stream=None):
-        if self.lower is None:
-            raise MspmvError("Ilu0: closed")
-        if self.lu_values is None:
-            raise MspmvError("Ilu0.solve: nothing is factorised yet (call factor(values) first)")
-        self.lower.solve(self.lu_values, r, x=self._mid, stream=stream)
-        return self.upper.solve(self.lu_values, self._mid, x=out, stream=stream)
-
-    def solve_many(self, R, out=None, stream=None):
-        """U^-1 (L^-1 R) for the k columns of R ([rows, k], row-major): two solve_many sweeps through one kept rows x k block
-        (allocated when k or the dtype changes); column j is bit for bit solve(R[:, j])."""
-        if self.lower is None:
-            raise MspmvError("Ilu0: closed")
-        if self.lu_values is None:
-            raise MspmvError("Ilu0.solve_many: nothing is factorised yet (call factor(values) first)")
-        self._mid_many = _mid_block(self._mid_many, "Ilu0.solve_many", self.lu_values, R)
-        self.lower.solve_many(self.lu_values, R, X=self._mid_many, stream=stream)
-        return self.upper.solve_many(self.lu_values, self._mid_many, X=out, stream=stream)
-
-    def close(self):
-        for plan in (getattr(self, "lower", None), getattr(self, "upper", None)):
-            if plan is not None:
-                plan.close()
-        self.lower = self.upper = None
-        self._temp = self.lu_values = self._mid = self._mid_many = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def csric0_group(rows: int, nnz: int) -> int:
-    """G, the lanes of one wave that work one row of mspmv_csric0_*: a function of rows and nnz alone (host only)."""
-    g = ctypes.c_int32(0)
-    _check(load_library().mspmv_csric0_group(int(rows), int(nnz), ctypes.byref(g)), "mspmv_csric0_group")
-    return int(g.value)
-
-
-def _ic0_temp_bytes(plan) -> int:
-    size = ctypes.c_size_t(0)
-    _check(plan._lib.mspmv_csric0_f32(plan._handle, None, ctypes.byref(size), None, None, None, None, 0, None, None, 0), "mspmv_csric0 (size query)")
-    return int(size.value)
-
-
-def _ic0_call(plan, temp, values, l, row_offsets, column_indices, mirror, pivot, stream, debug_synchronous):
-    import torch
-    fn = plan._lib.mspmv_csric0_f32 if values.dtype == torch.float32 else plan._lib.mspmv_csric0_f64
-    size = ctypes.c_size_t(temp.numel())
-    with torch.cuda.device(plan.device):
-        _check(int(fn(plan._handle, ctypes.c_void_p(temp.data_ptr()), ctypes.byref(size), _ptr(values), _ptr(l), _ptr(row_offsets),
-                      _ptr(column_indices), int(bool(mirror)), _ptr(pivot), _stream_handle(stream), int(bool(debug_synchronous)))), "mspmv_csric0")
+    return _factor_once("csrilu0", True, _ilu0_temp_bytes, call, values, row_offsets, column_indices, plan, out, stream)
 
 
 def csric0(values, row_offsets, column_indices, plan=None, out=None, mirror: bool = False, stream=None, debug_synchronous: bool = False):
@@ -1482,91 +1417,116 @@ def csric0(values, row_offsets, column_indices, plan=None, out=None, mirror: boo
     int32 DEVICE tensor (the smallest row whose diagonal is missing or whose value under the root is <= 0, -1 if none), so nothing
     waits for the device.  `plan`: a LOWER CsrSv of this pattern (one is made and dropped if not given; a loop keeps an Ic0).  `out`:
     where the factor goes; may be `values` (in place)."""
-    import torch
-    rows, nnz = _ilu0_check("csric0", values, row_offsets, column_indices, plan, out)
-    own = plan is None
-    if own:
-        plan = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=False, stream=stream)
-    try:
-        l = out if out is not None else torch.empty(nnz, dtype=values.dtype, device=values.device)
-        pivot = torch.empty(1, dtype=torch.int32, device=values.device)
-        temp = torch.empty(_ic0_temp_bytes(plan), dtype=torch.uint8, device=values.device)
+    def call(plan, temp, l, pivot):
         _ic0_call(plan, temp, values, l, row_offsets, column_indices, mirror, pivot, stream, debug_synchronous)
-        return l, pivot
-    finally:
-        if own:
-            (stream if stream is not None else torch.cuda.current_stream(plan.device)).synchronize()
-            plan.close()
+    return _factor_once("csric0", False, _ic0_temp_bytes, call, values, row_offsets, column_indices, plan, out, stream)
 
 
-class Ic0:
-    """The IC(0) preconditioner of one (structurally symmetric) pattern: the LOWER + NON_UNIT and UPPER + NON_UNIT plans of CsrSv and
-    the temp storage of mspmv_csric0_*, made once (the constructor analyses the pattern twice; synchronous).  `factor(values)`
-    factorises with the mirror -- again and again, on new values of the same pattern -- and returns the pivot tensor (1 int32 on the
-    device: -1, or the smallest row whose diagonal is missing or whose value under the root is <= 0); `solve(r)` is
-    L^-T (L^-1 r), two triangular solves through one kept vector (a pattern that lacks a diagonal is refused there by the NON_UNIT
-    plan, as it is); `close()` releases the plans and the storage.  .l_values: the factor of the last `factor`: L below and on the diagonal, L^T above it, in A's layout."""
+class _Factor0:
+    """What Ilu0 and Ic0 share: the LOWER and UPPER plans of one pattern, the temp storage, the pivot, the factor of the last `factor`
+    and the kept vector and block between the two sweeps.  A subclass states _unit_lower (its lower plan's unit_diagonal), _temp_bytes
+    and _call (its factorisation), and shows the factor under its public name."""
 
     def __init__(self, row_offsets, column_indices, stream=None):
         import torch
+        name = type(self).__name__
         self.lower = self.upper = None
-        for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices")):
+        for t, tname in ((row_offsets, "row_offsets"), (column_indices, "column_indices")):
             if not isinstance(t, torch.Tensor):
-                raise MspmvError(f"Ic0: {name} must be a tensor")
+                raise MspmvError(f"{name}: {tname} must be a tensor")
         if not (row_offsets.is_cuda and column_indices.is_cuda):
-            raise MspmvError("Ic0 needs CUDA (HIP) tensors: the kernels only run on the GPU")
-        self.lower = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=False, stream=stream)
+            raise MspmvError(f"{name} needs CUDA (HIP) tensors: the kernels only run on the GPU")
+        self.lower = CsrSv(row_offsets, column_indices, lower=True, unit_diagonal=self._unit_lower, stream=stream)
         self.upper = CsrSv(row_offsets, column_indices, lower=False, unit_diagonal=False, stream=stream)
         self.device, self.rows, self.nnz = self.lower.device, self.lower.rows, self.lower.nnz
         self.row_offsets, self.column_indices = row_offsets, column_indices
-        self._temp = torch.empty(_ic0_temp_bytes(self.lower), dtype=torch.uint8, device=self.device)
+        self._temp = torch.empty(self._temp_bytes(self.lower), dtype=torch.uint8, device=self.device)
         self.pivot = torch.empty(1, dtype=torch.int32, device=self.device)
-        self.l_values = None
+        self._factor = None
         self._mid = None
         self._mid_many = None
 
+    def _ready(self, what=None):
+        name = type(self).__name__
+        if self.lower is None:
+            raise MspmvError(f"{name}: closed")
+        if what is not None and self._factor is None:
+            raise MspmvError(f"{name}.{what}: nothing is factorised yet (call factor(values) first)")
+        return name
+
     def factor(self, values, stream=None, debug_synchronous: bool = False):
         import torch
-        if self.lower is None:
-            raise MspmvError("Ic0: closed")
-        _ilu0_check("Ic0.factor", values, self.row_offsets, self.column_indices, self.lower)
-        if self.l_values is None or self.l_values.dtype != values.dtype:
-            self.l_values = torch.empty(self.nnz, dtype=values.dtype, device=self.device)
+        name = self._ready()
+        _ilu0_check(f"{name}.factor", values, self.row_offsets, self.column_indices, self.lower)
+        if self._factor is None or self._factor.dtype != values.dtype:
+            self._factor = torch.empty(self.nnz, dtype=values.dtype, device=self.device)
             self._mid = torch.empty(self.rows, dtype=values.dtype, device=self.device)
-        _ic0_call(self.lower, self._temp, values, self.l_values, self.row_offsets, self.column_indices, True, self.pivot, stream, debug_synchronous)
+        self._call(self.lower, self._temp, values, self._factor, self.row_offsets, self.column_indices, self.pivot, stream, debug_synchronous)
         return self.pivot
 
     def solve(self, r, out=None, stream=None):
-        if self.lower is None:
-            raise MspmvError("Ic0: closed")
-        if self.l_values is None:
-            raise MspmvError("Ic0.solve: nothing is factorised yet (call factor(values) first)")
-        self.lower.solve(self.l_values, r, x=self._mid, stream=stream)
-        return self.upper.solve(self.l_values, self._mid, x=out, stream=stream)
+        self._ready("solve")
+        self.lower.solve(self._factor, r, x=self._mid, stream=stream)
+        return self.upper.solve(self._factor, self._mid, x=out, stream=stream)
 
     def solve_many(self, R, out=None, stream=None):
-        """L^-T (L^-1 R) for the k columns of R ([rows, k], row-major): two solve_many sweeps through one kept rows x k block
-        (allocated when k or the dtype changes); column j is bit for bit solve(R[:, j])."""
-        if self.lower is None:
-            raise MspmvError("Ic0: closed")
-        if self.l_values is None:
-            raise MspmvError("Ic0.solve_many: nothing is factorised yet (call factor(values) first)")
-        self._mid_many = _mid_block(self._mid_many, "Ic0.solve_many", self.l_values, R)
-        self.lower.solve_many(self.l_values, R, X=self._mid_many, stream=stream)
-        return self.upper.solve_many(self.l_values, self._mid_many, X=out, stream=stream)
+        """The two sweeps of `solve` for the k columns of R ([rows, k], row-major): two solve_many sweeps through one kept rows x k
+        block (allocated when k or the dtype changes); column j is bit for bit solve(R[:, j])."""
+        name = self._ready("solve_many")
+        self._mid_many = _mid_block(self._mid_many, f"{name}.solve_many", self._factor, R)
+        self.lower.solve_many(self._factor, R, X=self._mid_many, stream=stream)
+        return self.upper.solve_many(self._factor, self._mid_many, X=out, stream=stream)
 
     def close(self):
         for plan in (getattr(self, "lower", None), getattr(self, "upper", None)):
             if plan is not None:
                 plan.close()
         self.lower = self.upper = None
-        self._temp = self.l_values = self._mid = self._mid_many = None
+        self._temp = self._factor = self._mid = self._mid_many = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+class Ilu0(_Factor0):
+    """The ILU(0) preconditioner of one pattern: the LOWER + UNIT and UPPER + NON_UNIT plans of CsrSv and the temp storage of
+    mspmv_csrilu0_*, made once (the constructor analyses the pattern twice; synchronous).  `factor(values)` factorises -- again and
+    again, on new values of the same pattern -- and returns the pivot tensor (1 int32 on the device: -1, or the smallest row with a
+    missing or zero diagonal); `solve(r)` is U^-1 (L^-1 r), two triangular solves through one kept vector; `solve_many(R)` is the
+    same for the k columns of R; `close()` releases the plans and the storage.  .lu_values: the factor of the last `factor`."""
+
+    _unit_lower = True
+    _temp_bytes = staticmethod(_ilu0_temp_bytes)
+    _call = staticmethod(_ilu0_call)
+    lu_values = property(lambda self: self._factor)
+
+
+def csric0_group(rows: int, nnz: int) -> int:
+    """G, the lanes of one wave that work one row of mspmv_csric0_*: a function of rows and nnz alone (host only)."""
+    g = ctypes.c_int32(0)
+    _check(load_library().mspmv_csric0_group(int(rows), int(nnz), ctypes.byref(g)), "mspmv_csric0_group")
+    return int(g.value)
+
+
+class Ic0(_Factor0):
+    """The IC(0) preconditioner of one (structurally symmetric) pattern: the LOWER + NON_UNIT and UPPER + NON_UNIT plans of CsrSv and
+    the temp storage of mspmv_csric0_*, made once (the constructor analyses the pattern twice; synchronous).  `factor(values)`
+    factorises with the mirror -- again and again, on new values of the same pattern -- and returns the pivot tensor (1 int32 on the
+    device: -1, or the smallest row whose diagonal is missing or whose value under the root is <= 0); `solve(r)` is
+    L^-T (L^-1 r), two triangular solves through one kept vector (a pattern that lacks a diagonal is refused there by the NON_UNIT
+    plan, as it is); `solve_many(R)` is the same for the k columns of R; `close()` releases the plans and the storage.  .l_values: the
+    factor of the last `factor`: L below and on the diagonal, L^T above it, in A's layout."""
+
+    _unit_lower = False
+    _temp_bytes = staticmethod(_ic0_temp_bytes)
+    l_values = property(lambda self: self._factor)
+
+    @staticmethod
+    def _call(plan, temp, values, l, row_offsets, column_indices, pivot, stream, debug_synchronous):
+        _ic0_call(plan, temp, values, l, row_offsets, column_indices, True, pivot, stream, debug_synchronous)
 
 
 class CsrMVPlan:

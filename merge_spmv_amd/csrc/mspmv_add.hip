@@ -41,7 +41,7 @@ using namespace mspmv;
 
 #include "mspmv_scan.hpp"      // block_inclusive_scan, the three scan kernels
 
-#include "mspmv_radix.hpp"     // launched, grid_for, scan_table, tr_fill_kernel
+#include "mspmv_radix.hpp"     // launched, scan_table, tr_fill_kernel
 
 // 256 threads x 7 merged entries.  An odd count per thread keeps the lanes' walks through the two staged column lists (a stride of
 // up to ADD_IPT words between neighbouring lanes) off a common bank; 7 x 256 entries need 7 KiB of LDS for the columns and 7 / 14

@@ -5,12 +5,8 @@
 // Scheme: the level schedule of the LOWER triangular solve.  Row i of the row-wise (IKJ) elimination needs the FINISHED rows k whose
 // column is stored in its strict lower part -- the dependency graph of L x = b -- so a LOWER mspmv_csrsv_plan_t already holds the
 // analysis: order[], level_offsets[] and the segments.  A maximal run of narrow levels is ONE workgroup of 1024 threads that walks its
-// levels with __syncthreads() between them; every other level is one launch of many workgroups.  Nothing else orders two levels: no
-// flags, no spinning, no cooperative launch.
-//
-// Prologue (one launch): a lane per row finds, by bisection, the first entry whose column is >= the row (the end of the strict lower
-// part) and writes it to temp: the position p itself when that entry is the diagonal, ~p (negative) when the row stores none, which
-// also goes to *d_pivot by atomicMin; a lane per entry copies d_values to d_values_lu when they differ.
+// levels with __syncthreads() between them; every other level is one launch of many workgroups.  mspmv_levels.hpp holds what is not
+// ILU(0)'s own: the prologue that finds the diagonals (dpos), the lane-group body of a wide level and the host path.
 //
 // A row is worked by a GROUP of G consecutive lanes of one wave (G a power of two, a function of rows and nnz alone).  Lane l of the
 // group OWNS the entries e0 + l, e0 + l + G, ... of the row: only that lane ever reads or writes them while the row is worked, so no
@@ -27,53 +23,14 @@
 // returned, so nothing outside the arrays is touched and every loop ends.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-
 #include "../../include/mspmv.h"
-#include "mspmv_internal.hpp"
-#include "mspmv_csrsv_plan.hpp"
+#include "mspmv_levels.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 using namespace mspmv;
-
-constexpr int ILU_BLOCK = 256;              // a wide level: ILU_BLOCK / G rows per workgroup
-constexpr int ILU_NARROW_BLOCK = 1024;      // a run of narrow levels: one workgroup
-constexpr int ILU_LEVEL_CHUNK = 1024;       // level offsets staged in LDS at a time
-
-static unsigned ilu_grid(long long n, int per_block) { return (unsigned) std::max<long long>(1, (n + per_block - 1) / per_block); }
-
-// first position in [lo, hi) whose column is >= c (hi when none)
-__device__ __forceinline__ int ilu_lower_bound(const int *__restrict__ cols, int lo, int hi, int c)
-{
-    while (lo < hi) {
-        const int mid = (int) (((unsigned) lo + (unsigned) hi) >> 1);
-        if (cols[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// lane t < rows: the diagonal position of row t; lane t < nnz: one value copied (out of place only)
-template <typename V>
-__global__ __launch_bounds__(256) void ilu0_prologue_kernel(const V *vals, V *lu, const int *__restrict__ off, const int *__restrict__ cols,
-                                                            int rows, int nnz, int *__restrict__ dpos, unsigned *__restrict__ pivot)
-{
-    const long long t = (long long) blockIdx.x * 256 + threadIdx.x;
-    if (t < nnz && lu != vals) lu[t] = vals[t];
-    if (t < rows) {
-        const int r = (int) t;
-        int e0 = 0, e1 = 0;
-        if (off) { e0 = off[r]; e1 = off[r + 1]; }                   // (off may be NULL only when the matrix has no entries)
-        const int p = ilu_lower_bound(cols, e0, e1, r);
-        const bool stored = p < e1 && cols[p] == r;
-        dpos[r] = stored ? p : ~p;
-        if (!stored && pivot) atomicMin(pivot, (unsigned) r);
-    }
-}
 
 // All 64 lanes of a wave come here together; the G lanes of a group share `have` and the row i.  gl = the lane's place in its group.
 template <typename V>
@@ -110,7 +67,7 @@ __device__ __forceinline__ void ilu_row(bool have, int i, int G, int gl, const i
             // this lane's entries behind e: e0 + r for r = gl (mod G), r > t
             for (int g = e + 1 + ((gl - t - 1) & (G - 1)); g < e1; g += G) {
                 const int j = cols[g];
-                const int f = ilu_lower_bound(cols, u0, u1, j);
+                const int f = lv_lower_bound(cols, u0, u1, j);
                 if (f < u1 && cols[f] == j) {
                     const V p = q * a[f];
                     a[g] = a[g] - p;
@@ -121,31 +78,35 @@ __device__ __forceinline__ void ilu_row(bool have, int i, int G, int gl, const i
     if (pivot && diag && (nlow & (G - 1)) == gl && a[lo_end] == V(0)) atomicMin(pivot, (unsigned) i);
 }
 
-// one level (or a stretch of one): rows order[0 .. n), ILU_BLOCK / G of them per workgroup
 template <typename V>
-__global__ __launch_bounds__(ILU_BLOCK) void ilu0_level_kernel(const int *__restrict__ order, int n, int G, const int *__restrict__ off,
-                                                               const int *__restrict__ cols, const int *__restrict__ dpos, V *a,
-                                                               unsigned *__restrict__ pivot)
+__global__ __launch_bounds__(LV_BLOCK) void ilu0_prologue_kernel(const V *vals, V *lu, const int *__restrict__ off, const int *__restrict__ cols,
+                                                                 int rows, int nnz, int *__restrict__ dpos, unsigned *__restrict__ pivot)
 {
-    const int tid = (int) threadIdx.x;
-    const long long idx = (long long) blockIdx.x * (ILU_BLOCK / G) + tid / G;
-    const bool have = idx < n;
-    ilu_row<V>(have, have ? order[idx] : 0, G, tid & (G - 1), off, cols, dpos, a, pivot);
+    lv_prologue<V>(vals, lu, off, cols, rows, nnz, dpos, pivot);
+}
+
+template <typename V>
+__global__ __launch_bounds__(LV_BLOCK) void ilu0_level_kernel(const int *__restrict__ order, int n, int G, const int *__restrict__ off,
+                                                              const int *__restrict__ cols, const int *__restrict__ dpos, V *a,
+                                                              unsigned *__restrict__ pivot)
+{
+    lv_level_groups(order, n, G, [=](bool have, int i, int gl) { ilu_row<V>(have, i, G, gl, off, cols, dpos, a, pivot); });
 }
 
 // levels [level_lo, level_hi), every one narrow: ONE workgroup, a barrier between two levels.  Every trip count that encloses a
-// barrier or a shuffle is the same in every thread.
+// barrier or a shuffle is the same in every thread.  (The twin of ic0_narrow_kernel of mspmv_csric0.hip:
+// mspmv_levels.hpp says why the two are not one.)
 template <typename V>
-__global__ __launch_bounds__(ILU_NARROW_BLOCK) void ilu0_narrow_kernel(const int *__restrict__ order, const int *__restrict__ level_offsets,
-                                                                       int level_lo, int level_hi, int G, const int *__restrict__ off,
-                                                                       const int *__restrict__ cols, const int *__restrict__ dpos, V *a,
-                                                                       unsigned *__restrict__ pivot)
+__global__ __launch_bounds__(LV_NARROW_BLOCK) void ilu0_narrow_kernel(const int *__restrict__ order, const int *__restrict__ level_offsets,
+                                                                      int level_lo, int level_hi, int G, const int *__restrict__ off,
+                                                                      const int *__restrict__ cols, const int *__restrict__ dpos, V *a,
+                                                                      unsigned *__restrict__ pivot)
 {
-    __shared__ int s_lo[ILU_LEVEL_CHUNK + 1];
-    const int tid = (int) threadIdx.x, grp = tid / G, gl = tid & (G - 1), per_pass = ILU_NARROW_BLOCK / G;
-    for (int base = level_lo; base < level_hi; base += ILU_LEVEL_CHUNK) {
-        const int n = min(ILU_LEVEL_CHUNK, level_hi - base);
-        for (int i = tid; i <= n; i += ILU_NARROW_BLOCK) s_lo[i] = level_offsets[base + i];
+    __shared__ int s_lo[LV_LEVEL_CHUNK + 1];
+    const int tid = (int) threadIdx.x, grp = tid / G, gl = tid & (G - 1), per_pass = LV_NARROW_BLOCK / G;
+    for (int base = level_lo; base < level_hi; base += LV_LEVEL_CHUNK) {
+        const int n = min(LV_LEVEL_CHUNK, level_hi - base);
+        for (int i = tid; i <= n; i += LV_NARROW_BLOCK) s_lo[i] = level_offsets[base + i];
         __syncthreads();
         for (int l = 0; l < n; ++l) {
             const int hi = s_lo[l + 1];
@@ -160,71 +121,36 @@ __global__ __launch_bounds__(ILU_NARROW_BLOCK) void ilu0_narrow_kernel(const int
     }
 }
 
-static int ilu_launched(hipStream_t stream, int debug_sync, const char *name, unsigned grid, int block, int G)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int) e;
-    if (debug_sync) {
-        printf("mspmv: %s<<<%u, %d>>> %d lanes per row\n", name, grid, block, G);
-        fflush(stdout);
-        e = hipStreamSynchronize(stream);
-    }
-    return (int) e;
-}
-
-// G: the smallest power of two that is at least the mean row length, within [1, 64].  Measured (profiles/csrilu0_bench.txt, the sweep;
-// DESIGN.md 4 "ILU(0)"), fp64, G = 1 / 2 / 4 / 8 / 16 / 32 / 64: a 5-point grid of 2000 x 2000 (the rule: 8) 45.9 / 30.4 / 26.3 / 26.7 / 28.4 /
-// 32.0 / 40.9 ms, a 7-point grid of 128^3 (the rule: 8) 6.53 / 4.13 / 3.33 / 3.12 / 3.35 / 3.88 / 5.49 ms.
+// G for the mean row length.  Measured (profiles/csrilu0_bench.txt, the sweep; DESIGN.md 4 "ILU(0)"), fp64, G = 1 / 2 / 4 / 8 / 16 / 32 / 64:
+// a 5-point grid of 2000 x 2000 (the rule: 8) 45.9 / 30.4 / 26.3 / 26.7 / 28.4 / 32.0 / 40.9 ms, a 7-point grid of 128^3 (the rule: 8)
+// 6.53 / 4.13 / 3.33 / 3.12 / 3.35 / 3.88 / 5.49 ms.
 static int ilu_group(int32_t rows, int32_t nnz)
 {
-#ifdef MSPMV_TUNING
-    // development library only: the sweep of tools/csrilu0_bench.py
-    if (const char *e = getenv("MSPMV_CSRILU0_GROUP")) {
-        const int g = atoi(e);
-        if (g >= 1 && g <= 64 && (g & (g - 1)) == 0) return g;
-    }
-#endif
-    if (rows <= 0) return 1;
-    const long long mean = ((long long) nnz + rows - 1) / rows;
-    int g = 1;
-    while (g < 64 && g < mean) g <<= 1;
-    return g;
+    return lv_group(rows > 0 ? ((long long) nnz + rows - 1) / rows : 1, "MSPMV_CSRILU0_GROUP");
 }
-
-static size_t ilu_temp_bytes(int32_t rows) { return std::max<size_t>(16, ((size_t) rows * 4 + 15) & ~size_t(15)); }
 
 template <typename V>
 int ilu_factor(const mspmv_csrsv_plan *p, void *d_temp, size_t *temp_bytes, const V *vals, V *lu, const int32_t *off, const int32_t *cols,
                int32_t *d_pivot, hipStream_t stream, int debug_sync)
 {
-    if (!p || p->info.uplo != MSPMV_CSRSV_LOWER || !temp_bytes) return hipErrorInvalidValue;
-    const int rows = p->info.rows, nnz = p->info.nnz;
-    const size_t need = ilu_temp_bytes(rows);
-    if (!d_temp) { *temp_bytes = need; return hipSuccess; }
-    if (*temp_bytes < need || (reinterpret_cast<uintptr_t>(d_temp) & 15) != 0) return hipErrorInvalidValue;
-    if (nnz > 0 && (!vals || !lu || !off || !cols)) return hipErrorInvalidValue;
-    unsigned *pivot = reinterpret_cast<unsigned *>(d_pivot);
-    if (pivot && hipMemsetAsync(pivot, 0xff, 4, stream) != hipSuccess) return hipErrorInvalidValue;      // all ones: -1, no row yet
-    if (rows == 0) return hipSuccess;
-    if (nnz == 0) { vals = nullptr; lu = nullptr; off = nullptr; cols = nullptr; }
-    const int G = ilu_group(rows, nnz);
-    int *dpos = static_cast<int *>(d_temp);
-    const unsigned pgrid = ilu_grid(std::max(rows, nnz), 256);
-    hipLaunchKernelGGL((ilu0_prologue_kernel<V>), dim3(pgrid), dim3(256), 0, stream, vals, lu, off, cols, rows, nnz, dpos, pivot);
-    if (int e = ilu_launched(stream, debug_sync, "ilu0_prologue_kernel", pgrid, 256, G)) return e;
-    for (const mspmv_csrsv_plan::Segment &s : p->segments) {
-        if (s.narrow) {
-            hipLaunchKernelGGL((ilu0_narrow_kernel<V>), dim3(1), dim3(ILU_NARROW_BLOCK), 0, stream, p->d_order, p->d_level_offsets, s.level_lo,
-                               s.level_hi, G, off, cols, dpos, lu, pivot);
-            if (int e = ilu_launched(stream, debug_sync, "ilu0_narrow_kernel", 1, ILU_NARROW_BLOCK, G)) return e;
-        } else {
-            const int n = s.row_hi - s.row_lo;
-            const unsigned g = ilu_grid(n, ILU_BLOCK / G);
-            hipLaunchKernelGGL((ilu0_level_kernel<V>), dim3(g), dim3(ILU_BLOCK), 0, stream, p->d_order + s.row_lo, n, G, off, cols, dpos, lu, pivot);
-            if (int e = ilu_launched(stream, debug_sync, "ilu0_level_kernel", g, ILU_BLOCK, G)) return e;
-        }
-    }
-    return hipSuccess;
+    return lv_factor<V>(
+        p, d_temp, temp_bytes, vals, lu, off, cols, d_pivot, stream, ilu_group,
+        [&](const LvFactor<V> &f, unsigned grid) {
+            hipLaunchKernelGGL((ilu0_prologue_kernel<V>), dim3(grid), dim3(LV_BLOCK), 0, stream, f.vals, f.out, f.off, f.cols, f.rows, f.nnz, f.dpos,
+                               f.pivot);
+            return lv_launched(stream, debug_sync, "ilu0_prologue_kernel", grid, LV_BLOCK, f.G);
+        },
+        [&](const LvFactor<V> &f, const mspmv_csrsv_plan::Segment &s) {
+            hipLaunchKernelGGL((ilu0_narrow_kernel<V>), dim3(1), dim3(LV_NARROW_BLOCK), 0, stream, p->d_order, p->d_level_offsets, s.level_lo,
+                               s.level_hi, f.G, f.off, f.cols, f.dpos, f.out, f.pivot);
+            return lv_launched(stream, debug_sync, "ilu0_narrow_kernel", 1, LV_NARROW_BLOCK, f.G);
+        },
+        [&](const LvFactor<V> &f, const mspmv_csrsv_plan::Segment &s, unsigned grid) {
+            hipLaunchKernelGGL((ilu0_level_kernel<V>), dim3(grid), dim3(LV_BLOCK), 0, stream, p->d_order + s.row_lo, s.row_hi - s.row_lo, f.G, f.off,
+                               f.cols, f.dpos, f.out, f.pivot);
+            return lv_launched(stream, debug_sync, "ilu0_level_kernel", grid, LV_BLOCK, f.G);
+        },
+        [](const LvFactor<V> &) { return 0; });
 }
 
 }  // namespace

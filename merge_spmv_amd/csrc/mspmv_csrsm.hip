@@ -11,48 +11,29 @@
 // at one address and gathers X[c, j .. j + P) in one coalesced request.  All index arithmetic on B and X is 64-bit.
 //
 // Schedule.  A level of n rows is narrow for this k when n * P <= narrow_lanes.  A maximal run of consecutive narrow levels is one
-// launch of ONE workgroup of 1024 threads that walks its levels with __syncthreads() between them (a thread takes the pairs (row, j)
-// numbered tid, tid + 1024, ...: 1024 is a multiple of P, so its j never changes; the level offsets are staged in LDS; the first row of
-// the next level and its bounds are loaded before the barrier); every other level is one launch of ceil(n * P / 256) workgroups.  The
-// cut depends on P, so it is made from the plan's host copy of the level offsets while the solve walks them.  X is read and written
-// by the same kernel: it is not __restrict__ and goes through the ordinary loads.  A solve allocates nothing, reads nothing back and
-// launches the same kernels whatever the values.
+// launch of ONE workgroup that walks its levels (mspmv_levels.hpp: lv_walk_ahead; a thread takes the pairs (row, j) numbered tid,
+// tid + 1024, ...: 1024 is a multiple of P, so its j never changes); every other level is one launch of ceil(n * P / 256) workgroups.
+// The cut depends on P, so it is made from the plan's host copy of the level offsets while the solve walks them.  X is read and
+// written by the same kernel: it is not __restrict__ and goes through the ordinary loads.  A solve allocates nothing, reads nothing
+// back and launches the same kernels whatever the values.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "../../include/mspmv.h"
-#include "mspmv_csrsv_plan.hpp"
+#include "mspmv_levels.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int SM_BLOCK = 256;               // a wide level: P lanes per row
-constexpr int SM_NARROW_BLOCK = 1024;       // a run of narrow levels: one workgroup
-constexpr int SM_LEVEL_CHUNK = 1024;        // level offsets staged in LDS at a time
+using namespace mspmv;
+
 constexpr int SM_MAX_LANES = 64;            // the lanes of one row at most: one wave
 // The lane budget up to which a level is narrow: the 256 lanes of csrsv's W = 256, so that k = 1 launches what csrsv launches.
 // DESIGN.md 4 "Triangular solve, several right-hand sides" holds the sweep.
 constexpr int SM_NARROW_LANES = 256;
-
-static int sm_launched(hipStream_t stream, int debug_sync, const char *name, unsigned grid, int block)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int) e;
-    if (debug_sync) { printf("mspmv: %s<<<%u, %d>>>\n", name, grid, block); fflush(stdout); e = hipStreamSynchronize(stream); }
-    return (int) e;
-}
-
-__device__ __forceinline__ bool sm_strict(int upper, int r, int c) { return upper ? c > r : c < r; }
-
-__device__ __forceinline__ void sm_bounds(const int *__restrict__ off, int r, int &e0, int &e1)
-{
-    e0 = 0; e1 = 0;
-    if (off) { e0 = off[r]; e1 = off[r + 1]; }                      // (off may be NULL only when the matrix has no entries)
-}
 
 // row r, its entries [e0, e1), the right-hand sides j, j + 64, ... < k, one pass each:
 // s = +0; s = s + a[e] * X[c, jj] over the strict triangle in stored order; X[r, jj] = (alpha * B[r, jj] - s) [/ d]
@@ -64,7 +45,7 @@ __device__ __forceinline__ void sm_row(int r, int e0, int e1, const V *__restric
         V s = V(0), d = V(1);
         for (int e = e0; e < e1; ++e) {
             const int c = cols[e];
-            if (sm_strict(upper, r, c)) {
+            if (lv_strict(upper, r, c)) {
                 const V p = vals[e] * x[(long long) c * ldx + jj];
                 s = s + p;
             } else if (c == r) {
@@ -80,61 +61,33 @@ __device__ __forceinline__ void sm_row(int r, int e0, int e1, const V *__restric
 
 // one level, P = 1 << logp lanes per row: rows order[0 .. n)
 template <typename V>
-__global__ __launch_bounds__(SM_BLOCK) void sm_level_kernel(const int *__restrict__ order, int n, const V *__restrict__ vals,
+__global__ __launch_bounds__(LV_BLOCK) void sm_level_kernel(const int *__restrict__ order, int n, const V *__restrict__ vals,
                                                             const int *__restrict__ off, const int *__restrict__ cols, V alpha, const V *b,
                                                             long long ldb, V *x, long long ldx, int k, int logp, int upper, int unit)
 {
-    const long long t = (long long) blockIdx.x * SM_BLOCK + threadIdx.x;
+    const long long t = (long long) blockIdx.x * LV_BLOCK + threadIdx.x;
     const long long i = t >> logp;
     if (i >= n) return;
     const int j = (int) (t & ((1 << logp) - 1));
     const int r = order[i];
     int e0, e1;
-    sm_bounds(off, r, e0, e1);
+    lv_bounds(off, r, e0, e1);
     sm_row<V>(r, e0, e1, vals, cols, alpha, b, ldb, x, ldx, j, k, upper, unit);
 }
 
 // levels [level_lo, level_hi), every one of at most narrow_lanes / P rows: ONE workgroup, a barrier between two levels.  Every trip
 // count that encloses a barrier is the same in every thread, and no thread leaves early (a lane with j >= k has no pass to make).
 template <typename V>
-__global__ __launch_bounds__(SM_NARROW_BLOCK) void sm_narrow_kernel(const int *__restrict__ order, const int *__restrict__ level_offsets,
+__global__ __launch_bounds__(LV_NARROW_BLOCK) void sm_narrow_kernel(const int *__restrict__ order, const int *__restrict__ level_offsets,
                                                                     int level_lo, int level_hi, const V *__restrict__ vals,
                                                                     const int *__restrict__ off, const int *__restrict__ cols, V alpha,
                                                                     const V *b, long long ldb, V *x, long long ldx, int k, int logp, int upper,
                                                                     int unit)
 {
-    __shared__ int s_lo[SM_LEVEL_CHUNK + 1];
-    const int tid = (int) threadIdx.x;
     // pair tid + m * 1024 of a level is (row (tid >> logp) + m * (1024 >> logp), right-hand side tid & (P - 1))
-    const int j = tid & ((1 << logp) - 1), sub = tid >> logp, step = SM_NARROW_BLOCK >> logp;
-    for (int base = level_lo; base < level_hi; base += SM_LEVEL_CHUNK) {
-        const int n = min(SM_LEVEL_CHUNK, level_hi - base);
-        for (int i = tid; i <= n; i += SM_NARROW_BLOCK) s_lo[i] = level_offsets[base + i];
-        __syncthreads();
-        // this thread's first row of the level and its bounds: loaded one level ahead (they do not depend on X)
-        int i = s_lo[0] + sub, r = 0, e0 = 0, e1 = 0;
-        bool have = i < s_lo[1];
-        if (have) { r = order[i]; sm_bounds(off, r, e0, e1); }
-        for (int l = 0; l < n; ++l) {
-            const int hi = s_lo[l + 1];
-            if (have) {
-                sm_row<V>(r, e0, e1, vals, cols, alpha, b, ldb, x, ldx, j, k, upper, unit);
-                for (i += step; i < hi; i += step) {
-                    r = order[i];
-                    sm_bounds(off, r, e0, e1);
-                    sm_row<V>(r, e0, e1, vals, cols, alpha, b, ldb, x, ldx, j, k, upper, unit);
-                }
-            }
-            have = false;
-            if (l + 1 < n) {
-                i = hi + sub;
-                have = i < s_lo[l + 2];
-                if (have) { r = order[i]; sm_bounds(off, r, e0, e1); }
-            }
-            __syncthreads();                                        // level l's X is written before level l + 1 reads it
-        }
-        // (the barrier that ended the last level also ends the reads of s_lo)
-    }
+    const int tid = (int) threadIdx.x, j = tid & ((1 << logp) - 1);
+    lv_walk_ahead(order, level_offsets, level_lo, level_hi, off, tid >> logp, LV_NARROW_BLOCK >> logp,
+                  [=](int r, int e0, int e1) { sm_row<V>(r, e0, e1, vals, cols, alpha, b, ldb, x, ldx, j, k, upper, unit); });
 }
 
 static int sm_narrow_lanes()
@@ -153,25 +106,6 @@ static int sm_log2_lanes(int k)
     return logp;
 }
 
-// the launches of one solve for P lanes per row: a maximal run of narrow levels is one segment, every other level its own.
-// launch(first level, one past the last, narrow) returns 0 or an error, which ends the walk.
-template <typename F>
-static int sm_walk(const mspmv_csrsv_plan &p, int logp, int budget, F launch)
-{
-    const std::vector<int32_t> &lo = p.h_level_offsets;
-    const int L = lo.empty() ? 0 : (int) lo.size() - 1;
-    auto narrow = [&](int l) { return ((long long) (lo[l + 1] - lo[l]) << logp) <= (long long) budget; };
-    for (int l = 0; l < L;) {
-        int m = l + 1;
-        const bool nar = narrow(l);
-        if (nar)
-            while (m < L && narrow(m)) ++m;
-        if (int e = launch(l, m, nar)) return e;
-        l = m;
-    }
-    return 0;
-}
-
 template <typename V>
 int sm_solve(mspmv_csrsv_plan *p, const V *vals, const int32_t *off, const int32_t *cols, V alpha, const V *b, int32_t ldb, V *x, int32_t ldx,
              int32_t k, hipStream_t stream, int debug_sync)
@@ -184,17 +118,17 @@ int sm_solve(mspmv_csrsv_plan *p, const V *vals, const int32_t *off, const int32
     if (p->info.nnz == 0) { vals = nullptr; off = nullptr; cols = nullptr; }
     const int logp = sm_log2_lanes(k);
     const std::vector<int32_t> &lo = p->h_level_offsets;
-    return sm_walk(*p, logp, sm_narrow_lanes(), [&](int l, int m, bool narrow) -> int {
+    return mspmv_levels_cut(lo, logp, sm_narrow_lanes(), [&](int l, int m, bool narrow) -> int {
         if (narrow) {
-            hipLaunchKernelGGL((sm_narrow_kernel<V>), dim3(1), dim3(SM_NARROW_BLOCK), 0, stream, p->d_order, p->d_level_offsets, l, m, vals, off,
+            hipLaunchKernelGGL((sm_narrow_kernel<V>), dim3(1), dim3(LV_NARROW_BLOCK), 0, stream, p->d_order, p->d_level_offsets, l, m, vals, off,
                                cols, alpha, b, (long long) ldb, x, (long long) ldx, k, logp, upper, unit);
-            return sm_launched(stream, debug_sync, "sm_narrow_kernel", 1, SM_NARROW_BLOCK);
+            return lv_launched(stream, debug_sync, "sm_narrow_kernel", 1, LV_NARROW_BLOCK);
         }
         const int n = lo[m] - lo[l];
-        const unsigned g = (unsigned) ((((long long) n << logp) + SM_BLOCK - 1) / SM_BLOCK);
-        hipLaunchKernelGGL((sm_level_kernel<V>), dim3(g), dim3(SM_BLOCK), 0, stream, p->d_order + lo[l], n, vals, off, cols, alpha, b,
+        const unsigned g = (unsigned) ((((long long) n << logp) + LV_BLOCK - 1) / LV_BLOCK);
+        hipLaunchKernelGGL((sm_level_kernel<V>), dim3(g), dim3(LV_BLOCK), 0, stream, p->d_order + lo[l], n, vals, off, cols, alpha, b,
                            (long long) ldb, x, (long long) ldx, k, logp, upper, unit);
-        return sm_launched(stream, debug_sync, "sm_level_kernel", g, SM_BLOCK);
+        return lv_launched(stream, debug_sync, "sm_level_kernel", g, LV_BLOCK);
     });
 }
 
@@ -211,7 +145,7 @@ int mspmv_csrsm_info(const mspmv_csrsv_plan_t *plan, int32_t k, mspmv_csrsm_info
     info->lanes_per_row = 1 << logp;
     info->passes = (k + SM_MAX_LANES - 1) / SM_MAX_LANES;
     info->narrow_lanes = sm_narrow_lanes();
-    (void) sm_walk(*plan, logp, info->narrow_lanes, [&](int, int, bool) -> int { ++launches; return 0; });
+    (void) mspmv_levels_cut(plan->h_level_offsets, logp, info->narrow_lanes, [&](int, int, bool) -> int { ++launches; return 0; });
     info->launches = launches;
     return hipSuccess;
 }

@@ -21,11 +21,9 @@
 //
 // Solve.  One lane adds one row's sum, left to right in stored order, every operation rounded on its own; x[r] is a function of the
 // row's entries, the x of its dependencies, alpha and b[r] alone.  A maximal run of levels of at most W rows each is one launch of ONE
-// workgroup of 1024 threads that walks its levels with __syncthreads() between them (a thread takes rows tid, tid + 1024, ...; the
-// level offsets are staged in LDS; the first row of the next level and its bounds are loaded before the barrier, which do not depend
-// on x); every other level is one launch of ceil(rows of the level / 256) workgroups.  x is read and written by the same kernel: it
-// is not __restrict__ and goes through the ordinary loads.  A solve allocates nothing, reads nothing back and launches the same
-// kernels whatever the values.
+// workgroup that walks its levels (mspmv_levels.hpp: lv_walk_ahead; a thread takes rows tid, tid + 1024, ...); every other level is
+// one launch of ceil(rows of the level / 256) workgroups.  x is read and written by the same kernel: it is not __restrict__ and goes
+// through the ordinary loads.  A solve allocates nothing, reads nothing back and launches the same kernels whatever the values.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -33,8 +31,7 @@
 #include <vector>
 
 #include "../../include/mspmv.h"
-#include "mspmv_internal.hpp"
-#include "mspmv_csrsv_plan.hpp"
+#include "mspmv_levels.hpp"
 
 #pragma clang fp contract(off)
 
@@ -44,11 +41,8 @@ using namespace mspmv;
 
 #include "mspmv_scan.hpp"
 
-#include "mspmv_radix.hpp"     // tr_fill_kernel, grid_for
+#include "mspmv_radix.hpp"     // tr_fill_kernel
 
-constexpr int SV_BLOCK = 256;               // a wide level: one lane per row
-constexpr int SV_NARROW_BLOCK = 1024;       // a run of narrow levels: one workgroup
-constexpr int SV_LEVEL_CHUNK = 1024;        // level offsets staged in LDS at a time
 constexpr int SV_PEEL_CAP = 4096;           // analysis: a frontier of at most this many rows is peeled inside one workgroup
 // W, the rows up to which a level is narrow.  Measured (profiles/csrsv_bench.txt, the sweep; DESIGN.md 4 "Triangular solve"), fp64, W =
 // 64 / 256 / 1024 / 2048 / 4096: the lower part of a 5-point grid of 2000 x 2000 16.6 / 16.2 / 18.9 / 39.0 / 39.0 ms, of a 7-point grid of
@@ -57,16 +51,6 @@ constexpr int SV_PEEL_CAP = 4096;           // analysis: a frontier of at most t
 constexpr int SV_NARROW_ROWS = 256;
 
 enum { ST_COUNT = 0, ST_BAD = 1, ST_USED = 2 /* and 3 */, ST_NEXT = 4, ST_LEVEL = 5, ST_WHICH = 6, ST_WORDS = 8 };
-
-static int sv_launched(hipStream_t stream, int debug_sync, const char *name, unsigned grid, int block)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int) e;
-    if (debug_sync) { printf("mspmv: %s<<<%u, %d>>>\n", name, grid, block); fflush(stdout); e = hipStreamSynchronize(stream); }
-    return (int) e;
-}
-
-__device__ __forceinline__ bool sv_strict(int upper, int r, int c) { return upper ? c > r : c < r; }
 
 // ---- analysis ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sv_iota_kernel(int *__restrict__ out, long long n)
@@ -86,7 +70,7 @@ __global__ __launch_bounds__(256) void sv_count_kernel(const int *__restrict__ o
     int deg = 0, dg = 0;
     for (int e = off[r], e1 = off[r + 1]; e < e1; ++e) {
         const int c = cols[e];
-        deg += sv_strict(upper, r, c) ? 1 : 0;
+        deg += lv_strict(upper, r, c) ? 1 : 0;
         dg += c == r ? 1 : 0;
     }
     indeg[r] = deg;
@@ -102,7 +86,7 @@ __global__ __launch_bounds__(256) void sv_count_kernel(const int *__restrict__ o
 __device__ __forceinline__ void sv_release_one(int r, int c, int upper, int *__restrict__ indeg, int *__restrict__ level, int lvl,
                                                int *next, int *next_count)
 {
-    if (!sv_strict(upper, r, c)) return;
+    if (!lv_strict(upper, r, c)) return;
     if (atomicSub(&indeg[r], 1) == 1) {
         level[r] = lvl + 1;
         next[atomicAdd(next_count, 1)] = r;
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(256) void sv_peel_wide_kernel(const int *__restrict
 // ONE workgroup: level after level, while the frontier is neither empty nor larger than cap; a barrier between two levels.  On exit
 // state[ST_NEXT] = the size of the frontier it stopped at, state[ST_LEVEL] = that frontier's level, state[ST_WHICH] = 1 when it lies
 // in f1.  The frontier arrays are not __restrict__: what one level writes the next one reads.
-__global__ __launch_bounds__(SV_NARROW_BLOCK) void sv_peel_narrow_kernel(const int *__restrict__ off_t, const int *__restrict__ cols_t,
+__global__ __launch_bounds__(LV_NARROW_BLOCK) void sv_peel_narrow_kernel(const int *__restrict__ off_t, const int *__restrict__ cols_t,
                                                                          int upper, int *__restrict__ indeg, int *__restrict__ level,
                                                                          int *f0, int *f1, int n, int lvl, int cap,
                                                                          int *__restrict__ state)
@@ -156,7 +140,7 @@ __global__ __launch_bounds__(SV_NARROW_BLOCK) void sv_peel_narrow_kernel(const i
     do {                                                            // (n and lvl are the same in every thread)
         if (tid == 0) s_next = 0;
         __syncthreads();
-        for (int base = 0; base < n; base += SV_NARROW_BLOCK) {
+        for (int base = 0; base < n; base += LV_NARROW_BLOCK) {
             const bool have = base + tid < n;
             sv_release(have, have ? cur[base + tid] : 0, off_t, cols_t, upper, indeg, level, lvl, next, &s_next);
         }
@@ -171,12 +155,6 @@ __global__ __launch_bounds__(SV_NARROW_BLOCK) void sv_peel_narrow_kernel(const i
 }
 
 // ---- solve ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sv_bounds(const int *__restrict__ off, int r, int &e0, int &e1)
-{
-    e0 = 0; e1 = 0;
-    if (off) { e0 = off[r]; e1 = off[r + 1]; }                      // (off may be NULL only when the matrix has no entries)
-}
-
 // row r, its entries [e0, e1): s = +0; s = s + a[e] * x[c] over the strict triangle in stored order; x[r] = (alpha * b[r] - s) [/ d]
 template <typename V>
 __device__ __forceinline__ void sv_row(int r, int e0, int e1, const V *__restrict__ vals, const int *__restrict__ cols, V alpha, const V *b,
@@ -185,7 +163,7 @@ __device__ __forceinline__ void sv_row(int r, int e0, int e1, const V *__restric
     V s = V(0), d = V(1);
     for (int e = e0; e < e1; ++e) {
         const int c = cols[e];
-        if (sv_strict(upper, r, c)) {
+        if (lv_strict(upper, r, c)) {
             const V p = vals[e] * x[c];
             s = s + p;
         } else if (c == r) {
@@ -200,56 +178,29 @@ __device__ __forceinline__ void sv_row(int r, int e0, int e1, const V *__restric
 
 // one level (or a stretch of one), one lane per row: rows order[0 .. n)
 template <typename V>
-__global__ __launch_bounds__(SV_BLOCK) void sv_level_kernel(const int *__restrict__ order, int n, const V *__restrict__ vals,
+__global__ __launch_bounds__(LV_BLOCK) void sv_level_kernel(const int *__restrict__ order, int n, const V *__restrict__ vals,
                                                             const int *__restrict__ off, const int *__restrict__ cols, V alpha, const V *b,
                                                             V *x, int upper, int unit)
 {
-    const long long i = (long long) blockIdx.x * SV_BLOCK + threadIdx.x;
+    const long long i = (long long) blockIdx.x * LV_BLOCK + threadIdx.x;
     if (i >= n) return;
     const int r = order[i];
     int e0, e1;
-    sv_bounds(off, r, e0, e1);
+    lv_bounds(off, r, e0, e1);
     sv_row<V>(r, e0, e1, vals, cols, alpha, b, x, upper, unit);
 }
 
 // levels [level_lo, level_hi), every one of at most W rows: ONE workgroup, a barrier between two levels.  Every trip count that
 // encloses a barrier is the same in every thread.
 template <typename V>
-__global__ __launch_bounds__(SV_NARROW_BLOCK) void sv_narrow_kernel(const int *__restrict__ order, const int *__restrict__ level_offsets,
+__global__ __launch_bounds__(LV_NARROW_BLOCK) void sv_narrow_kernel(const int *__restrict__ order, const int *__restrict__ level_offsets,
                                                                     int level_lo, int level_hi, const V *__restrict__ vals,
                                                                     const int *__restrict__ off, const int *__restrict__ cols, V alpha,
                                                                     const V *b, V *x, int upper, int unit)
 {
-    __shared__ int s_lo[SV_LEVEL_CHUNK + 1];
     const int tid = (int) threadIdx.x;
-    for (int base = level_lo; base < level_hi; base += SV_LEVEL_CHUNK) {
-        const int n = min(SV_LEVEL_CHUNK, level_hi - base);
-        for (int i = tid; i <= n; i += SV_NARROW_BLOCK) s_lo[i] = level_offsets[base + i];
-        __syncthreads();
-        // this thread's first row of the level and its bounds: loaded one level ahead (they do not depend on x)
-        int i = s_lo[0] + tid, r = 0, e0 = 0, e1 = 0;
-        bool have = i < s_lo[1];
-        if (have) { r = order[i]; sv_bounds(off, r, e0, e1); }
-        for (int l = 0; l < n; ++l) {
-            const int hi = s_lo[l + 1];
-            if (have) {
-                sv_row<V>(r, e0, e1, vals, cols, alpha, b, x, upper, unit);
-                for (i += SV_NARROW_BLOCK; i < hi; i += SV_NARROW_BLOCK) {
-                    r = order[i];
-                    sv_bounds(off, r, e0, e1);
-                    sv_row<V>(r, e0, e1, vals, cols, alpha, b, x, upper, unit);
-                }
-            }
-            have = false;
-            if (l + 1 < n) {
-                i = hi + tid;
-                have = i < s_lo[l + 2];
-                if (have) { r = order[i]; sv_bounds(off, r, e0, e1); }
-            }
-            __syncthreads();                                        // level l's x is written before level l + 1 reads it
-        }
-        // (the barrier that ended the last level also ends the reads of s_lo)
-    }
+    lv_walk_ahead(order, level_offsets, level_lo, level_hi, off, tid, LV_NARROW_BLOCK,
+                  [=](int r, int e0, int e1) { sv_row<V>(r, e0, e1, vals, cols, alpha, b, x, upper, unit); });
 }
 
 static int sv_read(void *h, const void *d, size_t bytes, hipStream_t stream)
@@ -268,25 +219,16 @@ static int sv_narrow_rows()
     return SV_NARROW_ROWS;
 }
 
-// the launches of one solve from the level offsets: a maximal run of narrow levels is one segment, every other level its own
+// the launches of one solve from the level offsets: the cut for one lane per row and W rows
 static void sv_segments(mspmv_csrsv_plan &p, const std::vector<int32_t> &lo)
 {
-    const int W = p.info.narrow_rows, L = p.info.levels;
     p.segments.clear();
     p.info.max_level_rows = 0;
-    for (int l = 0; l < L;) {
-        const int n = lo[l + 1] - lo[l];
-        if (n <= W) {
-            int m = l;
-            while (m < L && lo[m + 1] - lo[m] <= W) ++m;
-            p.segments.push_back({l, m, lo[l], lo[m], true});
-            l = m;
-        } else {
-            p.segments.push_back({l, l + 1, lo[l], lo[l + 1], false});
-            ++l;
-        }
-    }
-    for (int l = 0; l < L; ++l) p.info.max_level_rows = std::max(p.info.max_level_rows, lo[l + 1] - lo[l]);
+    (void) mspmv_levels_cut(lo, 0, p.info.narrow_rows, [&](int l, int m, bool narrow) {
+        p.segments.push_back({l, m, lo[l], lo[m], narrow});
+        return 0;
+    });
+    for (int l = 0; l < p.info.levels; ++l) p.info.max_level_rows = std::max(p.info.max_level_rows, lo[l + 1] - lo[l]);
     p.info.launches = (int32_t) p.segments.size();
 }
 
@@ -306,7 +248,7 @@ static int sv_analyse(mspmv_csrsv_plan &p, const int32_t *d_off, const int32_t *
     if (nnz == 0) {
         // every row is level 0; without a stored diagonal, row 0 is already a bad one
         hipLaunchKernelGGL(sv_iota_kernel, dim3(rgrid), dim3(256), 0, stream, p.d_order, (long long) rows);
-        if (int e = sv_launched(stream, debug_sync, "sv_iota_kernel", rgrid, 256)) return e;
+        if (int e = lv_launched(stream, debug_sync, "sv_iota_kernel", rgrid, 256)) return e;
         p.info.levels = 1;
         p.info.bad_diagonal_row = nonunit ? 0 : -1;
         h_lo = {0, rows};
@@ -339,7 +281,7 @@ static int sv_analyse(mspmv_csrsv_plan &p, const int32_t *d_off, const int32_t *
         if (hipMemsetAsync(state, 0, ST_WORDS * 4, stream) != hipSuccess) return hipErrorInvalidValue;
         if (hipMemsetAsync(state + ST_BAD, 0xff, 4, stream) != hipSuccess) return hipErrorInvalidValue;
         hipLaunchKernelGGL(sv_count_kernel, dim3(rgrid), dim3(256), 0, stream, d_off, d_cols, rows, upper, nonunit, indeg, level, f[0], state);
-        if (int e = sv_launched(stream, debug_sync, "sv_count_kernel", rgrid, 256)) return e;
+        if (int e = lv_launched(stream, debug_sync, "sv_count_kernel", rgrid, 256)) return e;
         int h[ST_WORDS];
         if (int e = sv_read(h, state, sizeof(h), stream)) return e;
         p.info.bad_diagonal_row = (unsigned) h[ST_BAD] == 0xffffffffu ? -1 : h[ST_BAD];
@@ -350,9 +292,9 @@ static int sv_analyse(mspmv_csrsv_plan &p, const int32_t *d_off, const int32_t *
         while (n > 0) {
             done += n;
             if (n <= SV_PEEL_CAP) {
-                hipLaunchKernelGGL(sv_peel_narrow_kernel, dim3(1), dim3(SV_NARROW_BLOCK), 0, stream, off_t, cols_t, upper, indeg, level, f[which],
+                hipLaunchKernelGGL(sv_peel_narrow_kernel, dim3(1), dim3(LV_NARROW_BLOCK), 0, stream, off_t, cols_t, upper, indeg, level, f[which],
                                    f[which ^ 1], n, lvl, SV_PEEL_CAP, state);
-                if (int e = sv_launched(stream, debug_sync, "sv_peel_narrow_kernel", 1, SV_NARROW_BLOCK)) return e;
+                if (int e = lv_launched(stream, debug_sync, "sv_peel_narrow_kernel", 1, LV_NARROW_BLOCK)) return e;
                 if (int e = sv_read(h, state, sizeof(h), stream)) return e;
                 n = h[ST_NEXT]; lvl = h[ST_LEVEL]; which ^= h[ST_WHICH];
             } else {
@@ -360,7 +302,7 @@ static int sv_analyse(mspmv_csrsv_plan &p, const int32_t *d_off, const int32_t *
                 if (hipMemsetAsync(state + ST_NEXT, 0, 4, stream) != hipSuccess) return hipErrorInvalidValue;
                 hipLaunchKernelGGL(sv_peel_wide_kernel, dim3(g), dim3(256), 0, stream, off_t, cols_t, upper, indeg, level, f[which], f[which ^ 1], n,
                                    lvl, state + ST_NEXT);
-                if (int e = sv_launched(stream, debug_sync, "sv_peel_wide_kernel", g, 256)) return e;
+                if (int e = lv_launched(stream, debug_sync, "sv_peel_wide_kernel", g, 256)) return e;
                 if (int e = sv_read(h, state, sizeof(h), stream)) return e;
                 n = h[ST_NEXT]; ++lvl; which ^= 1;
             }
@@ -372,7 +314,7 @@ static int sv_analyse(mspmv_csrsv_plan &p, const int32_t *d_off, const int32_t *
         p.info.device_bytes += ((uint64_t) lvl + 1) * 4;
         const unsigned igrid = grid_for((long long) rows + 1, 256);
         hipLaunchKernelGGL(sv_iota_kernel, dim3(igrid), dim3(256), 0, stream, iota, (long long) rows + 1);
-        if (int e = sv_launched(stream, debug_sync, "sv_iota_kernel", igrid, 256)) return e;
+        if (int e = lv_launched(stream, debug_sync, "sv_iota_kernel", igrid, 256)) return e;
         tb = tb2;
         if (int e = mspmv_csr_transpose_f32(temp, &tb, nullptr, iota, level, rows, lvl, rows, nullptr, p.d_level_offsets, p.d_order, nullptr, cstream,
                                             debug_sync))
@@ -402,15 +344,15 @@ int sv_solve(mspmv_csrsv_plan *p, const V *vals, const int32_t *off, const int32
     if (p->info.nnz == 0) { vals = nullptr; off = nullptr; cols = nullptr; }
     for (const mspmv_csrsv_plan::Segment &s : p->segments) {
         if (s.narrow) {
-            hipLaunchKernelGGL((sv_narrow_kernel<V>), dim3(1), dim3(SV_NARROW_BLOCK), 0, stream, p->d_order, p->d_level_offsets, s.level_lo,
+            hipLaunchKernelGGL((sv_narrow_kernel<V>), dim3(1), dim3(LV_NARROW_BLOCK), 0, stream, p->d_order, p->d_level_offsets, s.level_lo,
                                s.level_hi, vals, off, cols, alpha, b, x, upper, unit);
-            if (int e = sv_launched(stream, debug_sync, "sv_narrow_kernel", 1, SV_NARROW_BLOCK)) return e;
+            if (int e = lv_launched(stream, debug_sync, "sv_narrow_kernel", 1, LV_NARROW_BLOCK)) return e;
         } else {
             const int n = s.row_hi - s.row_lo;
-            const unsigned g = grid_for(n, SV_BLOCK);
-            hipLaunchKernelGGL((sv_level_kernel<V>), dim3(g), dim3(SV_BLOCK), 0, stream, p->d_order + s.row_lo, n, vals, off, cols, alpha, b, x, upper,
+            const unsigned g = grid_for(n, LV_BLOCK);
+            hipLaunchKernelGGL((sv_level_kernel<V>), dim3(g), dim3(LV_BLOCK), 0, stream, p->d_order + s.row_lo, n, vals, off, cols, alpha, b, x, upper,
                                unit);
-            if (int e = sv_launched(stream, debug_sync, "sv_level_kernel", g, SV_BLOCK)) return e;
+            if (int e = lv_launched(stream, debug_sync, "sv_level_kernel", g, LV_BLOCK)) return e;
         }
     }
     return hipSuccess;

@@ -35,7 +35,7 @@ using namespace mspmv;
 
 #include "mspmv_scan.hpp"      // row_of, block_row_range, the three scan kernels
 
-#include "mspmv_radix.hpp"     // launched, grid_for, scan_table, tr_fill_kernel, TR_TILE
+#include "mspmv_radix.hpp"     // launched, scan_table, tr_fill_kernel, TR_TILE
 
 #include "mspmv_coo.hpp"       // coo_layout, coo_temp_bytes, coo_run, dup_layout, sum_duplicates_impl
 

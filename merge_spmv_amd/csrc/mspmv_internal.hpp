@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #if defined(MSPMV_DEV) && !defined(MSPMV_TUNING)
 #define MSPMV_TUNING 1      // the experiment build includes the tuning overrides
 #endif
@@ -55,5 +57,8 @@ uint64_t csrmv_temp_bytes(int32_t rows, int32_t nnz, int32_t value_bytes);
 constexpr long long MAX_ITEMS = 0x7fffffffLL - 65536;
 
 static inline uint64_t align256(uint64_t v) { return (v + 255) & ~uint64_t(255); }
+
+// the workgroups of a launch over n items, per_block of them each (at least one: a launch of no workgroups is an error)
+static inline unsigned grid_for(long long n, int per_block) { return (unsigned) std::max<long long>(1, (n + per_block - 1) / per_block); }
 
 }  // namespace mspmv

@@ -10,7 +10,7 @@
 //              out so that every digit's run is one contiguous store stream.
 // Every output position is a function of the input alone.  Also here: the finishing kernel that turns sorted keys into offsets by
 // boundary detection, and the small fill / gather kernels both users launch.  Included inside an anonymous namespace of each
-// translation unit, after mspmv_scan.hpp.
+// translation unit, after mspmv_scan.hpp and `using namespace mspmv` (grid_for is mspmv_internal.hpp's).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -205,8 +205,6 @@ static int launched(hipStream_t stream, int debug_sync, const char *name, unsign
     if (debug_sync) { printf("mspmv: %s<<<%u, 256>>>\n", name, grid); fflush(stdout); e = hipStreamSynchronize(stream); }
     return (int) e;
 }
-
-static unsigned grid_for(long long n, int per_block) { return (unsigned) std::max<long long>(1, (n + per_block - 1) / per_block); }
 
 // the three launches that turn the digit x tile table of a pass into its exclusive scan
 static int scan_table(const int *counts, long long table, int *bsum, int *offs, hipStream_t stream, int debug_sync)

@@ -45,7 +45,7 @@ using namespace mspmv;
 
 #include "mspmv_scan.hpp"      // row_of, block_row_range
 
-#include "mspmv_radix.hpp"     // launched, grid_for
+#include "mspmv_radix.hpp"     // launched
 
 constexpr int SDDMM_BLOCK = 256, SDDMM_WAVES = SDDMM_BLOCK / 64, SDDMM_IPT = 2, SDDMM_TILE = SDDMM_BLOCK * SDDMM_IPT;
 constexpr int SDDMM_WORDS = 8;                          // 16-byte words per chunk of k: 128 bytes

@@ -28,7 +28,7 @@ using namespace mspmv;
 
 #include "mspmv_scan.hpp"      // row_of, block_row_range, the three scan kernels
 
-#include "mspmv_radix.hpp"     // the pass kernels (upsweep, downsweep), the offsets / fill / gather kernels, Items, launched, grid_for
+#include "mspmv_radix.hpp"     // the pass kernels (upsweep, downsweep), the offsets / fill / gather kernels, Items, launched
 
 struct TrLayout {
     int passes, sets;
