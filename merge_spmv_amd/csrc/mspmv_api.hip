@@ -52,7 +52,7 @@ static int small_max_tiles()
 }
 #define SMALL_MAX_TILES (small_max_tiles())
 // Closed tiles of the one-launch kernel whose rows average at most this many nonzeros take the lean row-by-row reduction
-// (mspmv_kernels.hpp: consume_tile_rows); MSPMV_LEAN_AVG in the environment overrides it (read once: a re-tuning aid), 0 = never
+// (mspmv_reduce.hpp: consume_tile_rows); MSPMV_LEAN_AVG in the environment overrides it (read once: a re-tuning aid), 0 = never
 // (8 until round 5.  12: the reference's --dense=9 ... 12 inputs at 16 M nonzeros in fp64 0.0350 / 0.0347 / 0.0340 -> 0.0318 / 0.0317 / 0.0314 ms --
 //  rocSPARSE 0.0334 / 0.0329 / 0.0328 --, fp32 0.0240 -> 0.0231, a 1 M-nonzero --dense=10 5.5 -> 3.7 us per call (its tiles reach the compact
 //  front end's fast lane), nothing else in the sweep moves; 16: rows of 16 lose -- 0.0331 -> 0.0422; profiles/r05_lean_avg.txt)
@@ -71,7 +71,7 @@ static int compact_max_tiles(int value_bytes)
     (void) value_bytes;
     return v >= 0 ? v : 2304;
 }
-// block -> tile map of the compact launches (mspmv_kernels.hpp: compact_tile): 1 = one contiguous tile range per XCD, 0 = tile = block;
+// block -> tile map of the compact launches (mspmv_stage.hpp: compact_tile): 1 = one contiguous tile range per XCD, 0 = tile = block;
 // MSPMV_COMPACT_MAP in the environment overrides it (read once: a re-tuning aid)
 static int compact_tile_map()
 {
@@ -325,7 +325,7 @@ static inline void prof_mark(hipStream_t stream, int slot, int which)
 
 #define MSPMV_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
 
-// per-call tag of the published carries (LookBack, mspmv_kernels.hpp): a counter from a random start through a
+// per-call tag of the published carries (LookBack, mspmv_reduce.hpp): a counter from a random start through a
 // 64-bit mixer, so that neither a previous call nor whatever another process left in recycled memory can look current
 static unsigned long long next_call_tag()
 {
@@ -382,7 +382,8 @@ static int resident_blocks(K kernel, int block, std::atomic<int> (&cache)[64])
     return blocks_per_cu(kernel, block, 2, cache[di.slot]) * di.cus;
 }
 // Runtime bools -> template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a generic
-// lambda can name the kernel instantiation its flags select.  Every combination of the bools is instantiated, none else.
+// lambda can name the kernel instantiation its flags select (as variant tags: OutputIf, StreamsIf, BandsIf of mspmv_types.hpp).
+// Every combination of the bools is instantiated, none else.
 template <typename F>
 static inline auto with_bools(F &&f) { return f(); }
 template <typename F, typename... Rest>
@@ -406,7 +407,7 @@ static int safe_chunk_log2(int wanted_log2, int resident)
 #ifdef MSPMV_DEV
 // ---- development variants of the tile kernel (libmspmv_dev.so only; `make -C merge_spmv_amd dev`) ----
 // tuning bits, all rejected by the product library:
-//   bit 0        one contiguous tile range per XCD, persistent form (the old XCD_REMAP experiment)
+//   bit 0        one contiguous tile range per XCD, persistent form (DevSweep<REMAP>: the old XCD_REMAP experiment)
 //   bits  8..15  persistent form: resident blocks per CU (grid = that x CUs)
 //   bits 20..23  persistent form: tiles per block
 //   bits 16..18  1 = staging only (WRONG results, timing ablation), 6 = per-phase cycle stamps written to the
@@ -422,8 +423,8 @@ static bool launch_dev_variant(const Layout &L, const Params<V> &p, bool axpby, 
     const bool remap = !axpby && (L.flags & 1) != 0;
     const int ablate = axpby ? 0 : (L.flags >> 16) & 7;
     if (!(tpb_flag || forced || remap || ablate)) return false;
-    auto launch = [&](auto ax, auto rm, auto ntf, auto abl) {
-        auto kernel = tile_kernel_vec<V, BLOCK, IPT, ax.value, rm.value, ntf.value, abl.value, true>;
+    auto launch = [&](auto body, auto out, auto streams) {
+        auto kernel = tile_kernel_vec<V, BLOCK, IPT, decltype(body), decltype(out), decltype(streams)>;
         static std::atomic<int> resident{0};      /* one per kernel variant */
         const int per_cu = forced ? forced : blocks_per_cu(kernel, BLOCK, 4, resident);
         long long want = (long long) per_cu * device_info().cus;
@@ -431,12 +432,12 @@ static bool launch_dev_variant(const Layout &L, const Params<V> &p, bool axpby, 
         const unsigned pgrid = (unsigned) std::min<long long>(L.num_tiles, want);
         hipLaunchKernelGGL(kernel, dim3(pgrid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), stream, p, coords, carries, L.num_tiles, chunk_log2, no_bands());
     };
-    constexpr std::false_type no{}; constexpr std::true_type yes{};
-    if (ablate == 1) launch(no, no, yes, std::integral_constant<int, 1>{});
-    else if (ablate == 6) launch(no, no, yes, std::integral_constant<int, 6>{});
-    else if (ablate == 7) launch(no, no, yes, std::integral_constant<int, 7>{});
-    else if (remap) with_bools([&](auto ntf) { launch(no, yes, ntf, std::integral_constant<int, 0>{}); }, nt);
-    else with_bools([&](auto ax, auto ntf) { launch(ax, no, ntf, std::integral_constant<int, 0>{}); }, axpby, nt);
+    constexpr bool REMAP = true, NO_REMAP = false;
+    if (ablate == 1) launch(DevSweep<NO_REMAP, 1>{}, Assign{}, Streamed{});
+    else if (ablate == 6) launch(DevSweep<NO_REMAP, 6>{}, Assign{}, Streamed{});
+    else if (ablate == 7) launch(DevSweep<NO_REMAP, 7>{}, Assign{}, Streamed{});
+    else if (remap) with_bools([&](auto ntf) { launch(DevSweep<REMAP, 0>{}, Assign{}, StreamsIf<ntf.value>{}); }, nt);
+    else with_bools([&](auto ax, auto ntf) { launch(DevSweep<NO_REMAP, 0>{}, OutputIf<ax.value>{}, StreamsIf<ntf.value>{}); }, axpby, nt);
     return true;
 }
 #endif
@@ -639,9 +640,9 @@ static hipError_t one_launch_stage(const Stage<V, MV> &c)
         // (dev library: MSPMV_SNAP_MAP in the environment, read once: 30 = one contiguous tile range per XCD for every one-launch call, 0 .. 8 = that run length)
         static const int env_map = env_int("MSPMV_SNAP_MAP", -1);
         const int chunk_log2 = pl.tile_map ? pl.tile_map : env_map == TILE_MAP_CONTIGUOUS_CODE ? env_map
-                             : safe_chunk_log2(env_map >= 0 && env_map <= 8 ? env_map : pl.chunk_log2, resident_blocks(tile_kernel_snap<V, BLOCK, IPT, true, true, false, MV>, BLOCK, snap_cache));
+                             : safe_chunk_log2(env_map >= 0 && env_map <= 8 ? env_map : pl.chunk_log2, resident_blocks(tile_kernel_snap<V, BLOCK, IPT, General, Axpby, Streamed, MV>, BLOCK, snap_cache));
         launched = with_bools([&](auto ax, auto ntf) {
-            return launch_exact(tile_kernel_snap<V, BLOCK, IPT, ax.value, ntf.value, false, MV>, dim3(grid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), c.stream,
+            return launch_exact(tile_kernel_snap<V, BLOCK, IPT, General, OutputIf<ax.value>, StreamsIf<ntf.value>, MV>, dim3(grid), dim3(BLOCK), (size_t) p.x_lds * sizeof(V), c.stream,
                                 c.coords, c.rstart, L.num_tiles, chunk_log2, p, c.carries, lb, pl.lean_avg);
         }, c.axpby, pl.nt);
     }
@@ -664,7 +665,7 @@ static BandArgs band_setup(const Stage<V, MV> &c)
         // ~35 000 blocks of the launch that only return would queue up behind the work instead of draining beside it
         // (C2 fp32, blocks per CU 8 / 6 / 4 / 3: 0.857 / 0.842 / 0.832 / 0.843 ms; fp64, 5 / 4.4 / 3.1 / 2.5: 1.297 / 1.296 / 1.36 / 1.50)
         static std::atomic<int> resident{0};
-        const int band_resident_per_cu = blocks_per_cu(tile_kernel_vec<V, BLOCK, IPT, true, false, true, 0, false, true>, BLOCK, 4, resident);
+        const int band_resident_per_cu = blocks_per_cu(tile_kernel_vec<V, BLOCK, IPT, Bands, Axpby, Streamed>, BLOCK, 4, resident);
         const DeviceInfo di = device_info();
         const int band_per_cu = std::min(band_resident_per_cu, sizeof(V) == 4 ? 4 : 5);
         long long want = std::min<long long>(L.num_tiles, (long long) band_per_cu * di.cus);
@@ -708,7 +709,7 @@ static hipError_t classic_tiles_stage(const Stage<V, MV> &c, const BandArgs &ba)
     const unsigned grid = (unsigned) L.num_tiles;
     if (!pl.vec) {
         with_bools([&](auto ax) {
-            hipLaunchKernelGGL((tile_kernel<V, BLOCK, IPT, ax.value, MV>), dim3(grid), dim3(BLOCK), 0, c.stream, p, c.coords, c.carries, L.num_tiles);
+            hipLaunchKernelGGL((tile_kernel<V, BLOCK, IPT, OutputIf<ax.value>, MV>), dim3(grid), dim3(BLOCK), 0, c.stream, p, c.coords, c.carries, L.num_tiles);
         }, c.axpby);
         return after_launch(c.stream, c.debug_sync, "tile_kernel", grid, BLOCK);
     }
@@ -724,7 +725,7 @@ static hipError_t classic_tiles_stage(const Stage<V, MV> &c, const BandArgs &ba)
     if constexpr (band_shape(BLOCK, IPT, (int) sizeof(V)) && std::is_same<V, MV>::value) {
         if (ba.grid > 0 && !launched) {
             with_bools([&](auto ax, auto ntf, auto td) {
-                hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, ax.value, false, ntf.value, 0, false, true, td.value>), dim3(grid), dim3(BLOCK), xl, c.stream,
+                hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, BandsIf<td.value>, OutputIf<ax.value>, StreamsIf<ntf.value>>), dim3(grid), dim3(BLOCK), xl, c.stream,
                                    p, c.coords, c.carries, L.num_tiles, pl.chunk_log2, ba);
             }, c.axpby, pl.nt, pl.tdm_shift > 0);
             launched = true;
@@ -732,7 +733,7 @@ static hipError_t classic_tiles_stage(const Stage<V, MV> &c, const BandArgs &ba)
     }
     if (!launched)
         with_bools([&](auto ax, auto ntf) {
-            hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, ax.value, false, ntf.value, 0, false, false, false, MV>), dim3(grid), dim3(BLOCK), xl, c.stream,
+            hipLaunchKernelGGL((tile_kernel_vec<V, BLOCK, IPT, Sweep, OutputIf<ax.value>, StreamsIf<ntf.value>, MV>), dim3(grid), dim3(BLOCK), xl, c.stream,
                                p, c.coords, c.carries, L.num_tiles, pl.chunk_log2, ba);
         }, c.axpby, pl.nt);
     return after_launch(c.stream, c.debug_sync, "tile_kernel_vec", grid, BLOCK);
@@ -1013,13 +1014,13 @@ static hipError_t run_mm_group(const MMLayout &L, char *base, MMParams<T> p, int
     constexpr int mm_chunk = MM_CHUNK_LOG2;
     if constexpr (LANE) {
         with_bools([&](auto ax, auto ntf) {
-            hipLaunchKernelGGL((spmm_lane_kernel<T, K, mm_lane_vec<T, K>(), MM_LANE_BLOCK, 256 * MM_LANE_IPT / MM_LANE_BLOCK, ax.value, ntf.value>), dim3(grid), dim3(MM_LANE_BLOCK), 0, stream,
+            hipLaunchKernelGGL((spmm_lane_kernel<T, K, mm_lane_vec<T, K>(), MM_LANE_BLOCK, 256 * MM_LANE_IPT / MM_LANE_BLOCK, OutputIf<ax.value>, StreamsIf<ntf.value>>), dim3(grid), dim3(MM_LANE_BLOCK), 0, stream,
                                p, coords, carries, num_tiles, groups, mm_chunk);
         }, axpby, nt);
         MSPMV_CHECK(after_launch(stream, debug_sync, "spmm_lane_kernel", grid, MM_LANE_BLOCK));
     } else {
         with_bools([&](auto ax, auto ntf) {
-            hipLaunchKernelGGL((spmm_tile_kernel<T, K, S::BLOCK, S::IPT, ax.value, ntf.value>), dim3(grid), dim3(S::BLOCK), 0, stream, p, coords, carries, num_tiles, groups, mm_chunk);
+            hipLaunchKernelGGL((spmm_tile_kernel<T, K, S::BLOCK, S::IPT, OutputIf<ax.value>, StreamsIf<ntf.value>>), dim3(grid), dim3(S::BLOCK), 0, stream, p, coords, carries, num_tiles, groups, mm_chunk);
         }, axpby, nt);
         MSPMV_CHECK(after_launch(stream, debug_sync, "spmm_tile_kernel", grid, S::BLOCK));
     }
@@ -1478,7 +1479,7 @@ int mspmv_mg_apply_carries(void *d_y_local, const void *d_carries, const int64_t
 }  // extern "C"
 
 #ifdef MSPMV_DEV
-// development: where tile_kernel_vec<..., ABLATE = 6> writes its cycle stamps (device pointer, 16*8 u64 per block)
+// development: where tile_kernel_vec<.., DevSweep<.., 6>, ..> writes its cycle stamps (device pointer, 16*8 u64 per block)
 extern "C" int mspmv_dev_set_trace(void *d_buf)
 {
     unsigned long long *ptr = static_cast<unsigned long long *>(d_buf);

@@ -26,7 +26,7 @@
 //        search_kernel : one WAVE per boundary, 64-ary search (option)
 //      (the same kernels fill in the hints of tile_kernel_snap ahead of time: mspmv_csrmv_prepare)
 //   2. tile_kernel_vec : the same tile body on stored coordinates, one (row, partial) carry per tile
-//      tile_kernel_vec<.., BAND> : the same kernel with the column-band passes compiled in (run_band_passes): when 64
+//      tile_kernel_vec<.., Bands> : the same kernel with the column-band passes compiled in (run_band_passes): when 64
 //                      sampled windows of column indices (band_detect_block, riding on the coordinate launch) say the
 //                      columns are spread uniformly over an x several times L2, the first 4-5 blocks per CU stream the
 //                      matrix once per band of x instead (C2 fp32: 1.22 -> 0.83 ms); otherwise the ordinary body runs
@@ -39,2018 +39,31 @@
 //                      multi-level and atomic options.
 // Development variants of tile_kernel_vec (persistent grid, ablations, cycle stamps) compile only with -DMSPMV_DEV.
 // mspmv_spmm.hpp builds the SpMM kernels on the same pieces.
+// Which variant of a tile kernel runs is spelled by tag types (mspmv_types.hpp), so a launch site and a profile both say it:
+//   tile_kernel_vec<float, 256, 11, Clocked, Assign, Streamed>     body Sweep | Bands | Clocked (-DMSPMV_DEV: DevSweep<..>)
+//   tile_kernel_snap<double, 256, 7, Compact, Axpby, Cached>       body General | Compact
+//   output Assign (y = A x) | Axpby (y = alpha A x + beta y); streams Cached | Streamed (non-temporal loads of the CSR arrays)
+//
+// This header is the map.  What the kernels are built from lies in the headers below, each including the one before it:
+//   mspmv_types.hpp     Coord, Carry, Params, the variant tags, the tagged records (rec_announce, rec_store, rec_take), BoundaryOut
+//   mspmv_coords.hpp    merge-path search, band detection, search_kernel / coords_scatter_kernel / coords_interp_kernel
+//   mspmv_wave.hpp      wave primitives (DPP segmented scan, block reduce-by-key); streaming loads (Vec4, widen, ld_stream4*)
+//   mspmv_reduce.hpp    in-tile reductions: consume_tile_lds, LookBack, consume_tile_flags, consume_tile_rows, CompactChain
+//   mspmv_stage.hpp     tile_kernel; 16-byte staging: TileRegs, issue_nonzero_loads, stage_tile*, x in LDS, block -> tile maps
+//   mspmv_tdm.hpp       TdmArgs, stage_tile_tdm: the staging of the clock-scheduled column bands (on mspmv_stage.hpp)
+// and below them, here: BandArgs, run_band_passes, tile_kernel_vec; the fix-up kernels; wave_merge_path_guess, the compact front
+// end, tile_kernel_snap; probe_read_kernel, launch_exact, mg_apply_kernel.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <tuple>
-#include <type_traits>
-#include <utility>
+#include "mspmv_types.hpp"
+#include "mspmv_coords.hpp"
+#include "mspmv_wave.hpp"
+#include "mspmv_reduce.hpp"
+#include "mspmv_stage.hpp"
+#include "mspmv_tdm.hpp"
 
 namespace mspmv {
 
-constexpr int WAVE = 64;
-
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef double double2v __attribute__((ext_vector_type(2)));
-
-struct Coord {
-    int x;  // row-ends consumed   (list A index)
-    int y;  // nonzeros consumed   (list B index)
-};
-
-template <typename V> struct Carry;
-template <> struct alignas(8) Carry<float> { int key; float value; };
-template <> struct alignas(16) Carry<double> { int key; int pad; double value; };
-
-// MV: the type the matrix values are STORED in (mixed precision: float values in a double product, bf16 values in a float one).  Every
-// value is widened to V in registers right before its multiply (widen<V>); x, y, alpha, beta, the products and every sum are V.
-struct bf16 { unsigned short bits; };         // the upper 16 bits of an IEEE fp32
-template <typename V, typename MV = V>
-struct Params {
-    const MV *__restrict__ values;
-    const int *__restrict__ row_end;  // d_row_offsets + 1 (device_spmv.cuh:148)
-    const int *__restrict__ cols;
-    const V *__restrict__ x;
-    V *__restrict__ y;
-    int rows;
-    int nnz;
-    V alpha;
-    V beta;
-    int x_lds;                        // > 0: x has this many entries and the tile kernels gather it from LDS
-    // column-band passes (BAND kernels only): this launch multiplies the nonzeros whose column lies in
-    // [band_lo, band_lo + band_len) and treats the others as zeros; band_pass > 0 adds its carries to the stored ones
-    int band_lo, band_len, band_pass;
-};
-
-// ---------------------------------------------------------------------------
-// Tagged records: how blocks of ONE launch hand each other 64 bits (tile_kernel_snap).  A record is two
-// 64-bit words, each carrying half of a per-call tag beside 32 bits of payload, written and read with relaxed agent-scope
-// atomics (visible across the XCDs' L2s without a cache flush).  A word is valid when its tag half matches, so no ordering
-// between the two is needed, and stale or uninitialised memory is told apart by the 63 tag bits.
-// EVERY RECORD SLOT IS CLEAN (0, 0) WHEN THE LAUNCH ENDS -- whoever acts on a slot LAST leaves it clean -- so no record outlives
-// its call and a captured call replays with the same tags, even after the matrix changed.  A slot goes through
-//     (anything) --publisher ANNOUNCES--> PENDING --publisher stores the record--> RECORD --consumer takes it--> (0, 0)
-//   * a publisher ANNOUNCES itself as soon as it knows it will publish -- an atomic exchange of a marker into word 0, issued before
-//     the tile's reduction, its answer looked at only when the sum is there: nothing waits for it -- and later stores the record
-//     with two plain atomic stores;
-//   * the one consumer every record has takes it (both tags match) and clears it;
-//   * NOTHING DEPENDS ON ANOTHER WORKGROUP BEING DISPATCHED -- only on workgroups that HAVE STARTED running to their stores (a block that
-//     has announced itself and is then preempted for good or faults hangs its consumer, as it would hang any kernel).  Polling for a
-//     publisher that has not started is bounded; a consumer whose poll runs out -- the awaited block
-//     has not been dispatched: possible only when far fewer blocks are resident than mspmv_api.hip assumed (a CU-masked stream, a
-//     long kernel beside this one, several processes on the device) AND the resident ones are all waiting -- CANCELS the slot by an
-//     atomic exchange.  What comes back decides: the RECORD (it arrived between the last look and now) -> taken like any other;
-//     PENDING -> the publisher is RUNNING (it announced itself); a plain publisher waits for nothing, a group LEADER (below) only --
-//     bounded, or for plain publishers that have started -- for its 63 predecessors: a chain of depth two, no cycle, so the record
-//     comes in finite time whatever else the device does: the consumer goes on polling for it WITHOUT a bound; anything else -> the publisher has not
-//     started: the cancellation stays, the block computes the missing sum itself from the matrix (recompute_row_head), and the
-//     publisher, whose announcement brings the cancellation back, wipes the slot instead of publishing.
-// (Until round 5 a cancelled slot's late record stayed where it was and an EPOCH word, bumped by the recomputing consumer and mixed
-//  into the tags, was to keep a replayed launch from mistaking it for its own.  That left two holes: a publisher dispatched AFTER the
-//  bump tagged its record with the NEW epoch -- the one the next replay reads at its start --, and blocks of one launch that read the
-//  epoch before and after a bump disagreed about every tag between them, each such pair costing a full poll budget.  A publisher
-//  that EXCHANGES its record in and cleans up when it finds a cancellation was measured first: correct, but the answer of the
-//  exchange sits on the critical path of a tile that does nothing after publishing -- BASELINE config 4, 23 800 such tiles: +7.5 %.)
-// The reference's fp64 fix-up spins without bound on the same residency assumption (single_pass_scan_operators.cuh:620-639);
-// here a broken assumption costs time, never the result.  Every interleaving of these operations under relaxed ordering -- one
-// publisher and one consumer, and the publisher -> leader -> consumer chain, every poll budget, clean and stale slots -- is
-// enumerated by tests/test_record_protocol_model.py (payload or recompute; slot (0, 0) at the end; no wait that nothing ends;
-// the unbounded wait only for a publisher that has started).  What the invariant excludes: a slot that already holds THIS call's
-// marker when the launch starts (a launch killed between announce and store, then replayed with the same tags).
-// ---------------------------------------------------------------------------
-constexpr int REC_MAX_POLLS = 1 << 17;      // x ~1 us: ~0.1 s before a consumer gives up on a record and computes the sum itself
-// (markers carry the call's tag with its low bit CLEARED: never a valid record tag, tag_a | 1)
-__device__ __forceinline__ unsigned long long rec_cancel_word(unsigned tag_a) { return ((unsigned long long) (tag_a & ~1u) << 32) | 0x0CA9CE11ull; }
-__device__ __forceinline__ unsigned long long rec_pending_word(unsigned tag_a) { return ((unsigned long long) (tag_a & ~1u) << 32) | 0x9E0D1D61ull; }
-// the publisher's announcement; the returned word goes to rec_store when the sum is there
-__device__ __forceinline__ unsigned long long rec_announce(unsigned long long *rec, unsigned tag_a)
-{
-    return __hip_atomic_exchange(rec, rec_pending_word(tag_a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rec_store(unsigned long long *rec, unsigned tag_a, unsigned tag_b, unsigned p0, unsigned p1, unsigned long long announced)
-{
-    if (announced == rec_cancel_word(tag_a)) {      // the one consumer of this slot gave up before this block started: nobody will take the record
-        __hip_atomic_store(rec, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(rec + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    __hip_atomic_store(rec + 1, ((unsigned long long) tag_b << 32) | p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(rec, ((unsigned long long) tag_a << 32) | p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// waits (bounded) until both words carry this call's tag, clears the record; false = the slot is cancelled (payload undefined)
-__device__ __forceinline__ bool rec_take(unsigned long long *rec, unsigned tag_a, unsigned tag_b, unsigned &p0, unsigned &p1, int max_polls)
-{
-    for (int polls = 0; polls < max_polls; ++polls) {
-        const unsigned long long w0 = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long w1 = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned) (w0 >> 32) == tag_a && (unsigned) (w1 >> 32) == tag_b) {
-            __hip_atomic_store(rec, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(rec + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            p0 = (unsigned) w0; p1 = (unsigned) w1;
-            return true;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
-    // give up on this slot: cancel it -- unless its publisher has at least started
-    unsigned long long w0 = __hip_atomic_exchange(rec, rec_cancel_word(tag_a), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((unsigned) (w0 >> 32) != tag_a && w0 != rec_pending_word(tag_a)) return false;       // not started: the publisher will find the cancellation
-    // The record's word 0 (its word 1 was stored before it by the same thread and is on its way), or the announcement of a publisher
-    // that is running and waits for nothing (its record overwrites the cancellation): a wait for stores of a block that HAS started
-    // (the exchange REPLACED word 0: a record's word 0 is the one it brought back; after an announcement the publisher's store will
-    //  overwrite the cancellation)
-    const bool have_w0 = (unsigned) (w0 >> 32) == tag_a;
-    unsigned long long w1;
-    for (;;) {
-        if (!have_w0) w0 = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        w1 = __hip_atomic_load(rec + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned) (w0 >> 32) == tag_a && (unsigned) (w1 >> 32) == tag_b) break;
-        __builtin_amdgcn_s_sleep(2);
-    }
-    __hip_atomic_store(rec, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(rec + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    p0 = (unsigned) w0; p1 = (unsigned) w1;
-    return max_polls > 0;                   // (max_polls == 0, the "never look" testing aid: the slot is cleaned, the record discarded -- every such tile recomputes)
-}
-
-// Where a coordinate pass puts what it finds about tile boundary t -- the merge-path point (x, y) of diagonal t * TILE:
-//   coords[t] = (x, y)                       what the tile kernels read; mspmv_debug_read_tiles
-//   rstart[t] = row_offsets[x]               the first nonzero of the row the boundary falls in (tile_kernel_snap; nullptr: not wanted)
-struct BoundaryOut {
-    Coord *coords;
-    int *rstart;
-};
-__device__ __forceinline__ void emit_boundary(const BoundaryOut &o, int t, int x, int y, int row_start)
-{
-    Coord c; c.x = x; c.y = y;
-    o.coords[t] = c;
-    if (o.rstart) o.rstart[t] = row_start;
-}
-
-// A tiny x (the reference's --dense=<cols> inputs: 5 or 32 entries) is copied to LDS once per block and
-// gathered there: the x gather then costs LDS reads instead of 12 vector-memory instructions per thread --
-// as many as the whole CSR stream needs.  Bounded so that residency barely changes.
-constexpr int X_LDS_MAX_BYTES = 4096;
-
-// ---------------------------------------------------------------------------
-// Merge-path diagonal search (reference
-// cub/thread/thread_search.cuh:53-84), wave-cooperative.
-//   smallest p in [lo, hi] with p == hi or row_end[p] + p + 1 > diagonal.
-// row_end[p] + p is strictly increasing, so the predicate is monotone; each
-// round the wave's 64 lanes probe the last element of 64 equal chunks of the
-// candidate range and a ballot picks the chunk: range / 64 per dependent load.
-// All lanes return the same coordinate.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ Coord wave_merge_path_search(int diagonal, const int *__restrict__ row_end,
-                                                        int rows, int nnz)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    int lo = diagonal - nnz; lo = lo < 0 ? 0 : lo;
-    int hi = diagonal < rows ? diagonal : rows;
-    while (lo < hi) {
-        const int n = hi - lo;
-        const int step = (n + WAVE - 1) / WAVE;
-        const int chunk_lo = lo + lane * step;          // may exceed hi for trailing lanes
-        int q = chunk_lo + step; q = (q < hi ? q : hi) - 1;
-        bool pred = false;                               // lanes whose chunk is empty abstain
-        if (chunk_lo < hi) pred = (row_end[q] + q + 1 > diagonal);
-        const unsigned long long mask = __ballot(pred);
-        if (mask == 0ull) { lo = hi; break; }            // no row-end beyond the diagonal in range
-        const int f = __ffsll((long long) mask) - 1;     // first chunk whose last element is past
-        const int new_lo = lo + f * step;
-        int new_hi = new_lo + step; new_hi = (new_hi < hi ? new_hi : hi) - 1;
-        lo = new_lo; hi = new_hi;                        // answer in [new_lo, q_f]
-    }
-    Coord c; c.x = lo < rows ? lo : rows; c.y = diagonal - lo;
-    return c;
-}
-
-// The same search as the self-searching tiles of small problems do it: round 1 probes 64 FIXED samples
-// (k + 1) * rows / 64 -- the same addresses for every block, so they come from L2 --, round 2 probes 64 CONSECUTIVE
-// rows around the point linear interpolation inside that bracket predicts (two cache lines); on a matrix whose row
-// lengths vary smoothly that finishes it: two dependent loads instead of four, ~1.5 us less before a block's first
-// nonzero is requested.  Whatever is left of the bracket goes through 64-ary rounds.  Exact; all lanes return the
-// same coordinate.  M(p) = row_end[p] + p + 1 (strictly increasing), M(rows) = +inf; the point of diagonal d is
-// (p, d - p) for the first p with M(p) > d.
-__device__ __forceinline__ Coord wave_merge_path_search_interp(int diagonal, const int *__restrict__ row_end, int rows, int nnz)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int inf = rows + nnz + 1;                              // < 2^31
-    auto m_of = [&](int p) { return p < rows ? row_end[p] + p + 1 : inf; };
-    const int pk = (int) ((long long) (lane + 1) * rows / WAVE);  // lane 63: rows
-    const int mk = m_of(pk);
-    unsigned long long mask = __ballot(mk > diagonal);            // monotone; lane 63 is always set
-    int f = __ffsll((long long) mask) - 1;
-    int b = __shfl(pk, f, WAVE);
-    const int m_hi = __shfl(mk, f, WAVE);
-    const int p_lo = f == 0 ? -1 : __shfl(pk, f - 1, WAVE);
-    const int m_lo = f == 0 ? 0 : __shfl(mk, f - 1, WAVE);
-    int a = p_lo + 1;                                             // M(p) <= diagonal for p < a;  M(b) > diagonal
-    if (a < b) {
-        const long long g = p_lo + 1 + (long long) ((double) (diagonal - m_lo) * (double) (b - p_lo - 1) / (double) (m_hi - m_lo));
-        int w0 = (int) g - WAVE / 2;
-        const int w_max = b - (WAVE - 1) > a ? b - (WAVE - 1) : a;
-        w0 = w0 < a ? a : w0 > w_max ? w_max : w0;               // window [w0, w0 + 63], inside [a, b] where possible
-        const int p = w0 + lane;
-        const bool pred = p >= b ? true : m_of(p) > diagonal;
-        mask = __ballot(pred);
-        f = __ffsll((long long) mask) - 1;
-        if (mask == 0ull) a = w0 + WAVE;                          // the answer lies beyond the window
-        else if (f == 0 && w0 > a) b = w0;                        // ... at or before its first row
-        else a = b = w0 + f;                                      // found
-        while (a < b) {                                           // 64-ary rounds over [a, b), M(b) > diagonal
-            const int n = b - a;
-            const int step = (n + WAVE - 1) / WAVE;
-            const int chunk_lo = a + lane * step;
-            int q = chunk_lo + step; q = (q < b ? q : b) - 1;
-            bool pr = false;
-            if (chunk_lo < b) pr = m_of(q) > diagonal;
-            const unsigned long long mm = __ballot(pr);
-            if (mm == 0ull) { a = b; break; }
-            const int ff = __ffsll((long long) mm) - 1;
-            const int na = a + ff * step;
-            int nb = na + step; nb = (nb < b ? nb : b) - 1;
-            a = na; b = nb;
-        }
-    }
-    Coord c; c.x = b < rows ? b : rows; c.y = diagonal - b;
-    return c;
-}
-
-// ref: DeviceSpmvSearchKernel, dispatch_spmv_orig.cuh:104-143 (there: one
-// thread per boundary, binary search).  coords has num_tiles+1 entries.
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void search_kernel(const int *__restrict__ row_end, int rows, int nnz,
-                                                       int tile_items, int num_tiles, BoundaryOut out)
-{
-    const int wave_in_block = threadIdx.x / WAVE;
-    const int boundary = blockIdx.x * (BLOCK / WAVE) + wave_in_block;
-    if (boundary > num_tiles) return;
-    const long long total = (long long) rows + nnz;
-    long long d = (long long) boundary * tile_items;
-    const int diagonal = (int) (d < total ? d : total);
-    const Coord c = wave_merge_path_search(diagonal, row_end, rows, nnz);
-    if ((threadIdx.x & (WAVE - 1)) == 0) emit_boundary(out, boundary, c.x, c.y, c.x > 0 ? row_end[c.x - 1] : 0);
-}
-
-// ---------------------------------------------------------------------------
-// Column-band passes (no counterpart in the reference).  A matrix whose columns are spread
-// uniformly over an x several times the 4 MiB of an XCD's L2 is gather-bound at the Infinity-Cache rate
-// (C2: 100 M gathers in 1.2 ms, the CSR stream alone takes 0.14 ms).  Streaming the matrix B times, each
-// pass multiplying only the nonzeros of one column band -- an x slice that stays in L2 -- is faster: C2
-// fp32 0.83 ms with B = 3.  Whether the columns ARE spread like that is not known to the host, and a
-// stateless, asynchronous call cannot wait for the answer: 64 extra blocks of the coordinate pass sample 64
-// windows of 2048 consecutive nonzeros, and the tile kernel (its BAND variant) reads the 64 verdicts and runs
-// either its ordinary body or the passes (run_band_passes).
-// ---------------------------------------------------------------------------
-constexpr int BAND_WINDOWS = WAVE;         // one verdict per lane of the wave that reads them
-constexpr int BAND_WINDOW = 2048;          // consecutive nonzeros per window
-constexpr int BAND_MAJORITY = 56;          // windows that must look uniform
-constexpr int BAND_BITMAP_WORDS = 2048;    // 65 536 bits, one per 128-byte line of x modulo 8 MiB
-// set bits expected from d distinct lines hashed uniformly: m (1 - exp(-d / m)); d = 0.93 * 2048 -> 1877
-constexpr int BAND_MIN_BITS = 1877;
-constexpr int BAND_COUNTER_STRIDE = 64;    // ints between the 8 claim counters of run_band_passes (they follow the verdicts)
-
-__device__ __forceinline__ bool band_mode(const int *__restrict__ verdict)      // wave-uniform
-{
-    const int v = verdict[threadIdx.x & (WAVE - 1)];
-    return __popcll(__ballot(v != 0)) >= BAND_MAJORITY;
-}
-
-struct BandDetectArgs {
-    const int *cols; int nnz, num_cols;
-    int line_shift;            // column index -> 128-byte line of x: 5 (fp32), 4 (fp64)
-    int *verdict;              // BAND_WINDOWS verdicts, then the claim counters
-};
-
-// verdict[w] = 1 when window w touches (almost) as many distinct 128-byte lines of x as it has nonzeros -- no
-// short-range reuse for a cache to exploit: R-MAT windows reach 0.6-0.88 of that, stencils and bands a few percent,
-// uniform columns 0.975-0.99 -- AND spans at least 3/4 of the columns.  Block `w` of BAND_WINDOWS; BLOCK threads.
-template <int BLOCK>
-__device__ __forceinline__ void band_detect_block(const BandDetectArgs &a, int w)
-{
-    constexpr int NW = BLOCK / WAVE;
-    __shared__ unsigned s_bits[BAND_BITMAP_WORDS];
-    __shared__ int s_red[3][NW];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < BAND_BITMAP_WORDS; i += BLOCK) s_bits[i] = 0u;
-    __syncthreads();
-    const long long start = a.nnz > BAND_WINDOW ? (long long) w * (a.nnz - BAND_WINDOW) / (BAND_WINDOWS - 1) : 0;
-    const int len = a.nnz < BAND_WINDOW ? a.nnz : BAND_WINDOW;
-    int fresh = 0, lo = 0x7fffffff, hi = -1;
-    for (int j = tid; j < len; j += BLOCK) {
-        const int c = a.cols[start + j];
-        lo = c < lo ? c : lo; hi = c > hi ? c : hi;
-        const unsigned line = ((unsigned) c >> a.line_shift) & (BAND_BITMAP_WORDS * 32u - 1u);
-        const unsigned bit = 1u << (line & 31u);
-        fresh += (atomicOr(&s_bits[line >> 5], bit) & bit) ? 0 : 1;
-    }
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) {
-        fresh += __shfl_xor(fresh, d, WAVE);
-        const int l2 = __shfl_xor(lo, d, WAVE), h2 = __shfl_xor(hi, d, WAVE);
-        lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi;
-    }
-    if ((tid & (WAVE - 1)) == 0) { s_red[0][tid / WAVE] = fresh; s_red[1][tid / WAVE] = lo; s_red[2][tid / WAVE] = hi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < NW; ++k) {
-            fresh += s_red[0][k];
-            lo = s_red[1][k] < lo ? s_red[1][k] : lo; hi = s_red[2][k] > hi ? s_red[2][k] : hi;
-        }
-        const bool wide = 4LL * ((long long) hi - lo) >= 3LL * a.num_cols;
-        a.verdict[w] = (len == BAND_WINDOW && fresh >= BAND_MIN_BITS && wide) ? 1 : 0;
-        if (w < 8) a.verdict[BAND_WINDOWS + w * BAND_COUNTER_STRIDE] = 0;        // the claim counters of run_band_passes
-    }
-}
-
-// stand-alone form (calls that do not run the scatter coordinate pass: prepared calls, >= 10 M rows)
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void band_detect_kernel(BandDetectArgs a)
-{
-    band_detect_block<BLOCK>(a, (int) blockIdx.x);
-}
-
-// ---------------------------------------------------------------------------
-// The same coordinates by ONE coalesced pass over the row offsets instead of
-// num_tiles independent searches (each 4 dependent, scattered loads): the
-// merge position of row-end r is m_r = r + row_end[r] (r row-ends and
-// row_end[r] nonzeros precede it -- ties go to the row end, Appendix B.1), and
-// the point of diagonal d has x(d) = #{r : m_r < d}.  So thread r owns exactly
-// the tile boundaries d = t*tile_items with m_{r-1} < d <= m_r and writes
-// (r, d - r) for them; thread `rows` owns the boundaries past the last row end.
-// Usually a thread owns 0 or 1 boundary; a row longer than a tile owns many, and
-// a wave then fills one such row's run of boundaries cooperatively (a giant row
-// of 2^26 nonzeros owns ~37 000 of them).  Measured on MI355X: 3-15 us where
-// the search kernel took 27-52 us.
-// ---------------------------------------------------------------------------
-template <int BLOCK, int TILE_ITEMS, bool VEC>
-__device__ __forceinline__ void coords_scatter_block(const int *__restrict__ row_offsets, int rows, int nnz, int num_tiles,
-                                                     const BoundaryOut &out, unsigned block)
-{
-    // With M(i) = (i - 1) + row_offsets[i] (i >= 1; the merge position of row-end i - 1) and
-    // M(0) = -1, row r owns the boundaries t with M(r) < t*TILE_ITEMS <= M(r + 1); row index
-    // `rows` owns the ones past M(rows).  A thread takes 4 consecutive r (one 16-byte load).
-    // A boundary owned by row r lies INSIDE row r (r row-ends consumed, between row_offsets[r] and
-    // row_offsets[r + 1] nonzeros), so the row's first nonzero is o[j] -- what tile_kernel_snap wants to know.
-    const int lane = threadIdx.x & (WAVE - 1);
-    const long long gid = (long long) block * BLOCK + threadIdx.x;
-    const int total = rows + nnz;                              // < 2^31
-    const long long base = gid * 4;                            // first r of this thread
-    int o[5];                                                  // row_offsets[base .. base + 4]
-    if (VEC && base + 4 <= rows) {
-        const int4v v = *reinterpret_cast<const int4v *>(row_offsets + base);
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; o[4] = row_offsets[base + 4];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 5; ++j) o[j] = base + j <= rows ? row_offsets[base + j] : 0;
-    }
-    int t_lo[4], t_hi[4];
-    bool any_long = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const long long r = base + j;
-        t_lo[j] = 1; t_hi[j] = 0;
-        if (r <= rows) {
-            const int m_lo = r == 0 ? -1 : (int) r - 1 + o[j];
-            t_lo[j] = m_lo < 0 ? 0 : m_lo / TILE_ITEMS + 1;
-            t_hi[j] = r < rows ? ((int) r + o[j + 1]) / TILE_ITEMS : num_tiles;
-            const int count = t_hi[j] - t_lo[j] + 1;
-            if (count > 0 && count <= 2) {
-                for (int t = t_lo[j]; t <= t_hi[j]; ++t) {
-                    const long long d = (long long) t * TILE_ITEMS;
-                    emit_boundary(out, t, (int) r, (int) (d < total ? d : total) - (int) r, o[j]);
-                }
-            }
-            any_long |= count > 2;
-        }
-    }
-    // rows longer than two tiles: the wave fills each such run of boundaries together
-    if (__ballot(any_long) == 0ull) return;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        unsigned long long pending = __ballot(t_hi[j] - t_lo[j] + 1 > 2);
-        while (pending) {
-            const int src = __ffsll((long long) pending) - 1;
-            pending &= pending - 1;
-            const int lo = __shfl(t_lo[j], src, WAVE), hi = __shfl(t_hi[j], src, WAVE);
-            const int rr = (int) __shfl((int) base, src, WAVE) + j;
-            const int rs = __shfl(o[j], src, WAVE);
-            for (int t = lo + lane; t <= hi; t += WAVE) {
-                const long long d = (long long) t * TILE_ITEMS;
-                emit_boundary(out, t, rr, (int) (d < total ? d : total) - rr, rs);
-            }
-        }
-    }
-}
-
-template <int BLOCK, int TILE_ITEMS, bool VEC, bool DETECT = false>
-__global__ __launch_bounds__(BLOCK) void coords_scatter_kernel(const int *__restrict__ row_offsets, int rows, int nnz,
-                                                               int num_tiles, BoundaryOut out, BandDetectArgs da)
-{
-    // DETECT: the first BAND_WINDOWS blocks of the grid sample the column windows (column-band passes, above) -- first, so
-    // that their two dependent memory round trips run under the coordinate work instead of after it
-    if constexpr (DETECT) {
-        if ((int) blockIdx.x < BAND_WINDOWS) { band_detect_block<BLOCK>(da, (int) blockIdx.x); return; }
-    }
-    coords_scatter_block<BLOCK, TILE_ITEMS, VEC>(row_offsets, rows, nnz, num_tiles, out, DETECT ? blockIdx.x - BAND_WINDOWS : blockIdx.x);
-}
-
-// ---------------------------------------------------------------------------
-// The same coordinates WITHOUT reading every row offset: one THREAD per tile boundary, interpolation search.
-// With M(p) = row_end[p] + p + 1 (the merge position just past row-end p; strictly increasing) and
-// M(rows) = +inf, the point of diagonal d is (p, d - p) for the first p in [0, rows] with M(p) > d (for
-// p > d or p < d - nnz the predicate holds / fails by itself, so the search bounds of Appendix B.2 are implied).
-//   1. every block loads the same K + 1 samples M(k * rows / K) into LDS (L2 hits after the first block);
-//   2. a thread finds its bracket among them (10 LDS steps) and runs up to four secant steps -- evaluate M at the
-//      linearly interpolated point, shrink the bracket -- then a short walk; on a matrix whose row lengths vary
-//      smoothly (grids, bands, dense blocks, uniform random rows) that ends within a row or two of the first guess;
-//   3. otherwise (a giant row, a power-law neighbourhood) an exact binary search over what is left of the bracket.
-// Always exact -- the result is bit for bit the scatter pass's.  The kernel is latency-bound: its time is that of
-// its slowest thread, ~2-8 us on regular matrices and <= 17 us (a full binary search of a bracket) on any matrix,
-// whatever the row count, where the scatter pass reads all of row_offsets: 8 us at 3 M rows, 12 at 8 M, 20-23 at
-// 16.8 M.  The dispatcher therefore uses it from 10 M rows up (measured: band5 19.1 -> 7.5 us, C4 22.7 -> 11.5,
-// grid2d-4096 20.3 -> 16.5; below that size the scatter pass is at least as fast on irregular matrices).
-// ---------------------------------------------------------------------------
-constexpr int INTERP_SAMPLES = 1024;
-// s_m: SAMPLES + 1 ints of LDS (M values fit 32 bits: rows + nnz + 1 < 2^31); has a barrier inside
-template <int BLOCK, int SAMPLES = INTERP_SAMPLES>
-__device__ __forceinline__ void coords_interp_block(const int *__restrict__ row_end, int rows, int nnz, int tile_items, int num_tiles,
-                                                    const BoundaryOut &out, unsigned block, int *s_m)
-{
-    static_assert(SAMPLES % BLOCK == 0, "whole rounds of sample loads");
-    const int total = rows + nnz;
-    auto sample_pos = [&](int k) { return (int) ((long long) k * rows / SAMPLES); };
-    auto m_of = [&](int p) { return p < rows ? row_end[p] + p + 1 : total + 1; };
-    for (int k = threadIdx.x; k < SAMPLES; k += BLOCK) s_m[k] = m_of(sample_pos(k));
-    if (threadIdx.x == 0) s_m[SAMPLES] = total + 1;          // M(rows) = +inf
-    __syncthreads();
-    const long long boundary_ll = (long long) block * BLOCK + threadIdx.x;
-    if (boundary_ll > num_tiles) return;
-    const int boundary = (int) boundary_ll;
-    long long dl = (long long) boundary * tile_items;
-    const int d = (int) (dl < total ? dl : total);
-    // bracket: first sample k with M(p_k) > d  (k = SAMPLES always qualifies)
-    int klo = 0, khi = SAMPLES;
-    while (klo < khi) { const int mid = (klo + khi) >> 1; if (s_m[mid] > d) khi = mid; else klo = mid + 1; }
-    int b = sample_pos(klo);                                       // M(b) = m_hi > d
-    int m_hi = s_m[klo];
-    int p_lo = klo == 0 ? -1 : sample_pos(klo - 1);                // M(p_lo) = m_lo <= d   (p_lo = -1: nothing below)
-    int m_lo = klo == 0 ? 0 : s_m[klo - 1];
-    // secant steps: evaluate M at the interpolated point, keep the half that holds the answer
-    for (int it = 0; it < 4 && b - p_lo > 1; ++it) {
-        long long g = p_lo + 1 + (long long) ((double) (d - m_lo) * (double) (b - p_lo - 1) / (double) (m_hi - m_lo));
-        const int p = (int) (g <= p_lo ? p_lo + 1 : g >= b ? b - 1 : g);
-        const int mp = m_of(p);
-        if (mp > d) { b = p; m_hi = mp; } else { p_lo = p; m_lo = mp; }
-    }
-    // short walk from both ends, then an exact binary search over what is left (nothing, on a smooth matrix)
-    int a = p_lo + 1;                                              // M(p) <= d for p < a;  M(b) > d
-    for (int step = 0; step < 2 && a < b; ++step) { if (m_of(a) > d) b = a; else ++a; }
-    for (int step = 0; step < 2 && a < b; ++step) { if (m_of(b - 1) > d) --b; else a = b; }
-    while (a < b) { const int mid = (int) (((long long) a + b) >> 1); if (m_of(mid) > d) b = mid; else a = mid + 1; }
-    const int x = b < rows ? b : rows;
-    emit_boundary(out, boundary, x, d - b, x > 0 ? row_end[x - 1] : 0);
-}
-
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void coords_interp_kernel(const int *__restrict__ row_end, int rows, int nnz, int tile_items,
-                                                              int num_tiles, BoundaryOut out)
-{
-    __shared__ int s_m[INTERP_SAMPLES + 1];
-    coords_interp_block<BLOCK>(row_end, rows, nnz, tile_items, num_tiles, out, blockIdx.x, s_m);
-}
-
-// ---------------------------------------------------------------------------
-// wave64 inclusive segmented (reduce-by-key) scan over one (key, value) pair
-// per lane.  Keys are non-decreasing across lanes (rows along the merge
-// path), so "same key" == "same segment"; the combine is the reference's
-// ReduceByKeyOp<Sum> (thread_operators.cuh:291-301).
-// ---------------------------------------------------------------------------
-// Data-parallel-primitive (DPP) moves: cross-lane operands delivered inside the VALU
-// instead of through the LDS crossbar (__shfl_up lowers to ds_bpermute_b32, ~100 cycles
-// of dependent latency per step; a DPP move costs a VALU slot).  Lanes that receive
-// nothing (out of the row for row_shr, rows masked off for the broadcasts) keep `old`.
-//   row_shr:n   = 0x110 + n   shift right by n inside each row of 16 lanes
-//   row_bcast15 = 0x142       lane 15 of each row -> all lanes of the next row
-//   row_bcast31 = 0x143       lane 31 -> lanes 32..63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_move(int old, int src)
-{
-    return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, 0xf, false);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_move(float old, float src)
-{
-    return __builtin_bit_cast(float, dpp_move<CTRL, ROW_MASK>(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src)));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_move(double old, double src)
-{
-    const long long o = __builtin_bit_cast(long long, old), v = __builtin_bit_cast(long long, src);
-    const int lo = dpp_move<CTRL, ROW_MASK>((int) o, (int) v);
-    const int hi = dpp_move<CTRL, ROW_MASK>((int) (o >> 32), (int) (v >> 32));
-    return __builtin_bit_cast(double, ((long long) hi << 32) | (unsigned) lo);
-}
-
-template <typename V, int CTRL, int ROW_MASK>
-__device__ __forceinline__ void rbk_step(int key, V &val)
-{
-    const int k2 = dpp_move<CTRL, ROW_MASK>(-1, key);       // -1: "no source lane", never equals a key
-    const V v2 = dpp_move<CTRL, ROW_MASK>((V) 0, val);
-    val += k2 == key ? v2 : (V) 0;
-}
-
-template <typename V>
-__device__ __forceinline__ V wave_segmented_inclusive_sum(int key, V val)
-{
-    // keys are >= 0 and non-decreasing across lanes: equal key == same segment
-    rbk_step<V, 0x111, 0xf>(key, val);      // row_shr:1
-    rbk_step<V, 0x112, 0xf>(key, val);      // row_shr:2
-    rbk_step<V, 0x114, 0xf>(key, val);      // row_shr:4
-    rbk_step<V, 0x118, 0xf>(key, val);      // row_shr:8   -> inclusive within each 16-lane row
-    rbk_step<V, 0x142, 0xa>(key, val);      // row_bcast15 into rows 1 and 3
-    rbk_step<V, 0x143, 0xc>(key, val);      // row_bcast31 into rows 2 and 3
-    return val;
-}
-
-// Block-wide exclusive reduce-by-key scan of one pair per thread.
-//   in : (key, val) of this thread, keys non-decreasing with threadIdx.x
-//   out: carry_in  = sum of val over preceding threads whose key equals the
-//                    key of the thread just before this one, restricted to
-//                    that trailing equal-key run (0 for thread 0);
-//        returns the block aggregate (key, sum) in agg_* for the LAST thread.
-// s_wave_key/s_wave_val: LDS scratch, one slot per wave.
-template <typename V, int BLOCK>
-__device__ __forceinline__ void block_exclusive_rbk(int key, V val, int *s_wave_key, V *s_wave_val,
-                                                    int &prev_key, V &carry_in, int &agg_key, V &agg_val)
-{
-    constexpr int NW = BLOCK / WAVE;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int wave = threadIdx.x / WAVE;
-    const V incl = wave_segmented_inclusive_sum<V>(key, val);
-    if (lane == WAVE - 1) { s_wave_key[wave] = key; s_wave_val[wave] = incl; }
-    __syncthreads();
-    // fold the aggregates of the preceding waves, in order
-    int pk = -1; V pv = 0; bool have = false;
-#pragma unroll
-    for (int w = 0; w < NW - 1; ++w) {
-        if (w < wave) {
-            const int k = s_wave_key[w]; const V v = s_wave_val[w];
-            pv = (have && pk == k) ? pv + v : v; pk = k; have = true;
-        }
-    }
-    // exclusive within the wave
-    int ek = __shfl_up(key, 1, WAVE);
-    V ev = __shfl_up(incl, 1, WAVE);
-    if (lane == 0) { prev_key = pk; carry_in = have ? pv : (V) 0; }
-    else { prev_key = ek; carry_in = (have && pk == ek) ? pv + ev : ev; }
-    // aggregate as seen by this thread (meaningful for the last thread)
-    agg_key = key; agg_val = (have && pk == key) ? pv + incl : incl;
-}
-
-// ---------------------------------------------------------------------------
-// Streaming loads.  The nonzero arrays and the row offsets are read exactly
-// once per SpMV: load them non-temporally so they do not evict x from the
-// XCD's 4 MiB L2 (measured: -7 % time on the 12.5 MB-x gather), 16 bytes per
-// lane (a dword-per-lane stream tops out at 4.0 TB/s on MI355X, 16 B/lane at
-// 6.4 TB/s).
-// ---------------------------------------------------------------------------
-// NT = false: ordinary loads.  A matrix that fits the 256 MB Infinity Cache stays there
-// between SpMVs of an iterative solver when it is read with ordinary loads (measured +9-10 %
-// at 58 MB and 272 MB), while for larger matrices the non-temporal form wins (+3-6 %): the
-// dispatcher picks per call from the matrix's byte size.
-template <bool NT, typename T>
-__device__ __forceinline__ T ld_stream(const T *p) { return NT ? __builtin_nontemporal_load(p) : *p; }
-
-template <typename T> struct Vec4;
-template <> struct Vec4<int> { int4v v; __device__ __forceinline__ int get(int i) const { return v[i]; } };
-template <> struct Vec4<float> { float4v v; __device__ __forceinline__ float get(int i) const { return v[i]; } };
-template <> struct Vec4<double> { double2v a, b; __device__ __forceinline__ double get(int i) const { return i < 2 ? a[i] : b[i - 2]; } };
-
-template <> struct Vec4<bf16> {
-    int2v v;
-    __device__ __forceinline__ bf16 get(int i) const { bf16 r; r.bits = (unsigned short) ((unsigned) v[i >> 1] >> (16 * (i & 1))); return r; }
-};
-// matrix value -> compute type: exact (every fp32 is an fp64, every bf16 an fp32), so a mixed call's products are those of the widened matrix
-template <typename V> __device__ __forceinline__ V widen(V v) { return v; }
-template <typename V> __device__ __forceinline__ V widen(bf16 v) { return __builtin_bit_cast(float, (unsigned) v.bits << 16); }
-template <typename V, typename = typename std::enable_if<sizeof(V) == 8>::type> __device__ __forceinline__ V widen(float v) { return (V) v; }
-
-template <bool NT>
-__device__ __forceinline__ bf16 ld_stream(const bf16 *p) { bf16 r; r.bits = ld_stream<NT>(&p->bits); return r; }
-template <bool NT>
-__device__ __forceinline__ Vec4<bf16> ld_stream4(const bf16 *p)       // 8 bytes per chunk
-{
-    Vec4<bf16> r; const int2v *q = reinterpret_cast<const int2v *>(p);
-    r.v = NT ? __builtin_nontemporal_load(q) : *q; return r;
-}
-template <bool NT>
-__device__ __forceinline__ Vec4<int> ld_stream4(const int *p)
-{
-    Vec4<int> r; const int4v *q = reinterpret_cast<const int4v *>(p);
-    r.v = NT ? __builtin_nontemporal_load(q) : *q; return r;
-}
-template <bool NT>
-__device__ __forceinline__ Vec4<float> ld_stream4(const float *p)
-{
-    Vec4<float> r; const float4v *q = reinterpret_cast<const float4v *>(p);
-    r.v = NT ? __builtin_nontemporal_load(q) : *q; return r;
-}
-template <bool NT>
-__device__ __forceinline__ Vec4<double> ld_stream4(const double *p)
-{
-    Vec4<double> r; const double2v *q = reinterpret_cast<const double2v *>(p);
-    r.a = NT ? __builtin_nontemporal_load(q) : q[0];
-    r.b = NT ? __builtin_nontemporal_load(q + 1) : q[1];
-    return r;
-}
-__device__ __forceinline__ void zero4(Vec4<float> &r) { r.v = float4v{0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ void zero4(Vec4<double> &r) { r.a = double2v{0.0, 0.0}; r.b = r.a; }
-__device__ __forceinline__ void st_lds4(float *p, const float (&v)[4])
-{ float4v w; w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3]; *reinterpret_cast<float4v *>(p) = w; }
-__device__ __forceinline__ void st_lds4(double *p, const double (&v)[4])
-{
-    double2v a, b; a.x = v[0]; a.y = v[1]; b.x = v[2]; b.y = v[3];
-    *reinterpret_cast<double2v *>(p) = a; *(reinterpret_cast<double2v *>(p) + 1) = b;
-}
-__device__ __forceinline__ void st_lds4(int *p, const int (&v)[4])
-{ int4v w; w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3]; *reinterpret_cast<int4v *>(p) = w; }
-// Tile-relative row ends as the flag/scan reduction keeps them: 16 bits each (a tile has < 65536
-// nonzeros; entries of rows outside the tile are never read, so truncating them is harmless).
-// LDS is what limits the resident blocks per CU, and residency is worth more than anything else
-// here: 6 KB per 256x11 tile.
-typedef unsigned short end16_t;
-__device__ __forceinline__ void st_lds4(end16_t *p, const int (&v)[4])
-{
-    int2v w;
-    w.x = (v[0] & 0xffff) | (v[1] << 16);
-    w.y = (v[2] & 0xffff) | (v[3] << 16);
-    *reinterpret_cast<int2v *>(p) = w;
-}
-template <bool FL> struct EndType { typedef int type; };
-template <> struct EndType<true> { typedef end16_t type; };
-
-// LDS index swizzle of the staged products.  Thread t of the walk reads products around index
-// t*IPT - (rows before it); when rows have a regular length the per-lane stride resonates with
-// the 32 banks (dense 32-nnz rows, IPT = 11: lanes l, l+3, l+6 ... hit one bank, an 11-way
-// conflict: SQ_LDS_BANK_CONFLICT was 56 % of all LDS cycles).  XOR-ing index bits 2..4 with
-// bits 5..7 keeps every 4-element chunk contiguous and 16-byte aligned (the staging writes
-// whole chunks) and moves indices 32 apart to different banks.
-__device__ __forceinline__ int swz_prod(int i) { return i ^ (((i >> 5) & 7) << 2); }
-
-// ---------------------------------------------------------------------------
-// The reference's in-tile algorithm (agent_spmv_orig.cuh:539-634,906-913), tuned for CDNA4:
-// per-thread merge-path search on diagonal tid*IPT, the IPT-step path walk, the block-wide
-// carry scan, the y stores and the tile's carry-out.  Used by the dword-per-lane fallback
-// kernel (tile_kernel) and selectable in tile_kernel_vec for comparison (tuning flag 0x70000);
-// the production kernels use consume_tile_flags below.  Everything is tile-relative
-// (row 0 == c0.x, nonzero 0 == c0.y).
-//   s_end[r]  = tile-relative nonzero index where tile row r ends (r <
-//               tile_rows), +inf for the row left open at the tile end (the
-//               reference instead loads row_end[tile_rows] -- one past the
-//               array for the last tile);
-//   s_prod[j] = values[j] * x[cols[j]] for the tile's nonzeros.
-// ---------------------------------------------------------------------------
-template <typename V, int BLOCK, int IPT, bool AXPBY, bool SWZ = false, typename MV = V>
-__device__ __forceinline__ void consume_tile_lds(const Params<V, MV> &p, const Coord c0, int tile_rows, int tile_nnz,
-                                                 const int *s_end, const V *s_prod, V *s_y, int *s_wave_key,
-                                                 V *s_wave_val, Carry<V> *__restrict__ carry_out, int pshift = 0)
-{
-    // s_y (tile_rows entries) may alias the memory behind s_prod.  SWZ: s_prod is the raw
-    // (unshifted) array, product j lives at swz_prod(pshift + j).
-    // Straight-line code throughout: divergent branches in the search and the walk made
-    // every wave execute both sides of each step (measured 15-23 % of the kernel on
-    // short-row matrices).  Requirements on the staging: s_end[r] = +inf for every
-    // r >= tile_rows and s_prod[j] = 0 for every j >= tile_nnz, up to TILE + IPT + 3.
-    const int tid = threadIdx.x;
-    const int tile_items = tile_rows + tile_nnz;
-    int diag = tid * IPT; diag = diag < tile_items ? diag : tile_items;
-
-    // ---- in-tile merge-path search: x(diag) = #{r < tile_rows : s_end[r] + r < diag}
-    // (the predicate is monotone in r, Appendix B.2; the bounds max(diag - nnz, 0) and
-    // min(diag, rows) of the reference's search are implied by it).  Uniform trip count.
-    int row = 0;
-    for (int step = 1 << (31 - __builtin_clz(tile_rows | 1)); step > 0; step >>= 1) {
-        const int q = row + step;                      // candidate count
-        const int e = s_end[q - 1 < tile_rows ? q - 1 : tile_rows];   // clamped: slot tile_rows holds +inf
-        row = (q <= tile_rows && e + (q - 1) < diag) ? q : row;
-    }
-    const int first_row = row;                         // the row this thread starts in
-    const int nz = diag - row;
-
-    // ---- walk IPT path items, latency-free form.
-    // The reference's walk (agent_spmv_orig.cuh:557-578) reads LDS once per step with the
-    // address depending on the previous step: IPT dependent LDS round trips.  Here the
-    // <= IPT row ends this thread can reach are read in one batch; row-end j sits at path
-    // item (s_end[first_row + j] - nz) + j of this thread, which gives a bit mask of the
-    // items that are row ends; the k-th item is then nonzero nz + k - popcount(mask below
-    // k), so all products are read in a second batch and the segmented sum runs in registers.
-    unsigned mask = 0;
-#pragma unroll
-    for (int j = 0; j < IPT; ++j) {
-        const int pos = s_end[row + j] - nz + j;       // +inf sentinel (2^30) stays out of range
-        mask |= pos < IPT ? 1u << pos : 0u;
-    }
-    V prod[IPT];
-    {
-        int cnt = 0;
-#pragma unroll
-        for (int k = 0; k < IPT; ++k) {
-            prod[k] = SWZ ? s_prod[swz_prod(pshift + nz + k - cnt)] : s_prod[nz + k - cnt];
-            cnt += (mask >> k) & 1u;
-        }
-    }
-    // segmented sum in registers: ended[k] = total of the row that ends at item k
-    V ended[IPT];
-    V total = 0;
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        const bool end = (mask >> k) & 1u;
-        ended[k] = total;
-        total = end ? (V) 0 : total + prod[k];
-    }
-    const int done_all = __builtin_popcount(mask);
-    // ---- carry between threads: block-wide exclusive reduce-by-key scan (has a barrier
-    //      inside: after it every thread has finished reading s_prod, which s_y aliases)
-    int prev_key, agg_key; V carry_in, agg_val;
-    block_exclusive_rbk<V, BLOCK>(row + done_all, total, s_wave_key, s_wave_val, prev_key, carry_in, agg_key, agg_val);
-    // ---- row totals -> LDS (scattered 4/8-byte LDS writes are cheap; scattered global
-    //      stores were not: ~1.3 rows per L2 write request, as many requests as the
-    //      whole read stream on a 5-nnz/row matrix), then one coalesced copy to y.
-    {
-        // prev_key == first_row whenever tid > 0 (the previous thread ended in the row this
-        // thread started in); thread 0 has no in-tile carry.
-        const V first_carry = (tid > 0 && prev_key == first_row) ? carry_in : (V) 0;
-        int done = 0;
-#pragma unroll
-        for (int k = 0; k < IPT; ++k) {
-            if ((mask >> k) & 1u) {
-                s_y[row + done] = done == 0 ? ended[k] + first_carry : ended[k];
-                ++done;
-            }
-        }
-    }
-    if (tid == BLOCK - 1) {
-        // the row left open at the tile end (ref: agent_spmv_orig.cuh:906-913)
-        Carry<V> c; c.key = c0.x + agg_key; c.value = agg_val;
-        *carry_out = c;
-    }
-    __syncthreads();
-    V *__restrict__ y = p.y + c0.x;
-    for (int r = tid; r < tile_rows; r += BLOCK) {
-        if (AXPBY) y[r] = p.alpha * s_y[r] + (p.beta == (V) 0 ? (V) 0 : p.beta * y[r]);
-        else y[r] = s_y[r];
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Carries without a second launch (tile_kernel_snap, for the rows its boundary snapping leaves open).  The per-tile carries
-// are LOCAL partial sums -- no tile needs another tile's result to compute its own -- so the fix-up "y[row] += carries of
-// the tiles before the one in which the row ends" can be done by that tile itself.  A tile that leaves a row open PUBLISHES
-// its partial sum as soon as its scan is done.  The tile in which the row ENDS knows exactly which earlier tiles hold
-// pieces of it: the row's first nonzero is path item r + row_offsets[r], i.e. it lies in tile (r + row_offsets[r]) / TILE,
-// so the pieces are the carries of tiles [that tile, this tile).  It takes exactly those records (one lane each: up to 64 by
-// wave 0 alone while the other waves run the row phase, longer lists by the whole block), adds them to its first row in a
-// fixed order and clears them.  There is no chain of waits (a waiting tile waits for blocks that wait for nobody before
-// publishing), and workgroups are dispatched in order: an awaited block is running or done (mspmv_api.hip:
-// safe_chunk_log2 keeps that true under the XCD-chunked tile order).  The reference's fp64 fix-up relies on the same
-// property (decoupled look-back, agent_segment_fixup.cuh:262-341 with single_pass_scan_operators.cuh); unlike it,
-// nothing here spins on a chain -- and when the property does not hold (fewer resident blocks than assumed) the waiting
-// tile computes the sum itself after a bounded poll (recompute_row_head).  Records: rec_store / rec_take above.
-// ---------------------------------------------------------------------------
-struct LookBack {
-    unsigned long long *rec;      // 2 words per tile; nullptr = off (the fix-up launch adds the carries)
-    unsigned tag_a, tag_b;        // tag_a is never 0 (a cleared word is never valid)
-    int *error;                   // two words of the call's temp storage: [0] receives call_tag when a poll ran out and the consumer computed the
-                                  // sum itself (a diagnostic: debug_sync reports it), [1] counts such episodes (was: an epoch mixed into the tags)
-    unsigned call_tag;            // what the host compares word [0] with
-    int max_polls;                // how often a consumer looks for a record before it computes the sum itself (REC_MAX_POLLS; tests: 1, or 0 = never looks)
-    int group_base;               // record index of the first GROUP record (= the launch's number of tiles): see LB_GROUP
-};
-// GROUP RECORDS: a row spanning thousands of tiles (BASELINE config 4: one row of 67 M nonzeros = 23 800 tiles) left its last tile
-// 23 800 records to take -- 24 rounds of memory latency by ONE block, 50 us at the end of a 130 us launch while the chip idles.
-// So every LB_GROUP-th piece of a long row is a group LEADER: a tile without a row end, tile % LB_GROUP == LB_GROUP - 1, whose row
-// began at or before the group's first tile.  The leader takes its LB_GROUP - 1 predecessors' records (one wave, one round), adds its
-// own partial sum and publishes the total as group record tile / LB_GROUP -- instead of a record of its own.  The tile in which
-// the row ends derives the same set of leaders from the same two numbers (the row's first piece, its own index) and takes the
-// group records of the complete groups plus the single records before the first and after the last of them: at most
-// 2 * (LB_GROUP - 1) + pieces / LB_GROUP records.  Every record still has exactly one taker, which clears it; the order of the
-// additions is fixed by the tile indices alone; and nothing depends on a record arriving -- a leader whose poll runs out
-// computes its group's sum from the matrix, like any consumer.
-constexpr int LB_GROUP = 64;
-template <typename V> struct LbBits;
-template <> struct LbBits<float> {
-    static __device__ __forceinline__ void split(float v, unsigned &p0, unsigned &p1) { p0 = __builtin_bit_cast(unsigned, v); p1 = 0u; }
-    static __device__ __forceinline__ float join(unsigned p0, unsigned) { return __builtin_bit_cast(float, p0); }
-};
-template <> struct LbBits<double> {
-    static __device__ __forceinline__ void split(double v, unsigned &p0, unsigned &p1)
-    { const unsigned long long b = __builtin_bit_cast(unsigned long long, v); p0 = (unsigned) (b >> 32); p1 = (unsigned) b; }
-    static __device__ __forceinline__ double join(unsigned p0, unsigned p1)
-    { return __builtin_bit_cast(double, ((unsigned long long) p0 << 32) | p1); }
-};
-template <typename V>
-__device__ __forceinline__ void lb_publish(const LookBack &lb, int slot, V value, unsigned long long announced)
-{
-    unsigned p0, p1; LbBits<V>::split(value, p0, p1);
-    rec_store(lb.rec + 2 * (size_t) slot, lb.tag_a, lb.tag_b, p0, p1, announced);
-}
-__device__ __forceinline__ unsigned long long lb_announce(const LookBack &lb, int slot) { return rec_announce(lb.rec + 2 * (size_t) slot, lb.tag_a); }
-// the carry tile s published: waits (bounded) until both words carry this call's tag, then clears the record
-template <typename V>
-__device__ __forceinline__ V lb_take(const LookBack &lb, int s, bool &ok)
-{
-    unsigned p0, p1;
-    if (rec_take(lb.rec + 2 * (size_t) s, lb.tag_a, lb.tag_b, p0, p1, lb.max_polls)) return LbBits<V>::join(p0, p1);
-    ok = false;                             // the caller computes the sum itself (recompute_row_head)
-    return (V) 0;
-}
-// Sum of the carries of tiles [tile - count, tile) -- the pieces of this tile's first row held by earlier tiles --
-// taken by the lanes of ONE wave (count <= 64), nearest tile on lane 0; fixed butterfly order; wave-uniform result.
-template <typename V>
-__device__ __forceinline__ V lb_take_wave(const LookBack &lb, int tile, int count, bool &ok)
-{
-    const int lane = threadIdx.x & (WAVE - 1);
-    V part = lane < count ? lb_take<V>(lb, tile - 1 - lane, ok) : (V) 0;
-    if (count > 1) {
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) part += __shfl_xor(part, d, WAVE);
-    } else part = __shfl(part, 0, WAVE);
-    return part;
-}
-// The same for a long list (a row spanning more than 64 tiles), by the whole block: thread j takes tiles tile-1-j,
-// tile-1-j-BLOCK, ... in that order; wave butterflies; the wave partials in wave order.  Block-uniform call (it has a
-// barrier); the result is valid on thread 0.
-template <typename V, int BLOCK, int U, typename SlotOf>
-__device__ __forceinline__ V lb_take_block(const LookBack &lb, int count, V *s_wave_val, bool &ok, SlotOf slot_of)
-{   // (slot_of(i): the record index of the i-th of the `count` records to take)
-    // U records per thread and round are requested before any is looked at (a round costs one memory latency whatever its
-    // width: with U = 4 a row spanning 37 000 tiles is 37 rounds); one that is not there yet -- only ever among the nearest
-    // tiles -- is then polled for.  The order of the additions is fixed by (thread, round, slot).  (U is what the register
-    // budget of the calling kernel allows.)
-    V part = 0;
-    for (int i0 = threadIdx.x; i0 < count; i0 += U * BLOCK) {
-        unsigned long long w0[U], w1[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * BLOCK;
-            w0[u] = w1[u] = 0ull;
-            if (i < count) {
-                unsigned long long *r = lb.rec + 2 * (size_t) slot_of(i);
-                w0[u] = __hip_atomic_load(r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                w1[u] = __hip_atomic_load(r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * BLOCK;
-            if (i < count) {
-                if (lb.max_polls > 0 && (unsigned) (w0[u] >> 32) == lb.tag_a && (unsigned) (w1[u] >> 32) == lb.tag_b) {
-                    unsigned long long *r = lb.rec + 2 * (size_t) slot_of(i);
-                    __hip_atomic_store(r, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(r + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    part += LbBits<V>::join((unsigned) w0[u], (unsigned) w1[u]);
-                } else part += lb_take<V>(lb, slot_of(i), ok);
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) part += __shfl_xor(part, d, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) s_wave_val[threadIdx.x / WAVE] = part;
-    __syncthreads();
-    V total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / WAVE; ++w) total += s_wave_val[w];
-    return total;
-}
-
-// What the records of tiles [first piece, this tile) add up to, computed from the matrix instead: the products of the
-// nonzeros [j0, j1) of the row that ends in this tile (from the row's first nonzero to the tile's first) -- the path of a
-// consumer whose poll ran out.  Whole block (barriers inside); fixed order; the result on every thread.
-template <typename V, int BLOCK, typename MV = V>
-__device__ __forceinline__ V recompute_row_head(const Params<V, MV> &p, int j0, int j1, V *s_wave_val)
-{
-    V part = 0;
-    for (int j = j0 + (int) threadIdx.x; j < j1; j += BLOCK) part += widen<V>(p.values[j]) * p.x[p.cols[j]];
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) part += __shfl_xor(part, d, WAVE);
-    __syncthreads();                                   // (s_wave_val may still be read by a take that preceded)
-    if ((threadIdx.x & (WAVE - 1)) == 0) s_wave_val[threadIdx.x / WAVE] = part;
-    __syncthreads();
-    V total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / WAVE; ++w) total += s_wave_val[w];
-    return total;
-}
-
-// ---------------------------------------------------------------------------
-// In-tile reduction of the production kernels: head flags + segmented scan.
-//
-// The reference walks the tile's merge path thread by thread (a binary search per
-// thread, then ITEMS dependent LDS reads, agent_spmv_orig.cuh:539-578); consume_tile_lds
-// above is that algorithm.  On CDNA4 it costs ~100 instructions per path item, which is what
-// bounds a streaming CsrMV here (39 lane-operations per fp32 nonzero are available at the HBM
-// peak).  The same tile result is obtained with no per-thread search and no dependent walk:
-//   * staging sets one bit per row START in a bit array over the tile's nonzeros (row r ends
-//     at tile-relative nonzero e => the next row starts at e: bit e, when e < tile_nnz; several
-//     empty rows set the same bit), plus the bit of the tile's first nonzero;
-//   * NONZERO PHASE: thread t owns the NPT consecutive staged products [t*NPT, (t+1)*NPT) (16-byte
-//     LDS reads), runs the segmented inclusive sum over them in registers, one block-wide
-//     segmented scan of (has-flag, running-sum) supplies the sum flowing in from the threads
-//     before it, and S[j] = "sum of the row containing nonzero j, up to j" is written back in place;
-//   * ROW PHASE: thread r of the tile's rows reads S at its row's last nonzero (0 for an empty
-//     row) and stores y[r] straight from registers, coalesced.  The row left open at the tile
-//     end is S at the tile's last nonzero: the carry.
-// Path items still bound a tile (rows + nonzeros <= BLOCK*IPT), tiles/carries/fix-up are
-// unchanged; only the association order inside a tile differs (sequential inside a thread's
-// NPT nonzeros, scan tree across threads), as it already did from the reference's.
-// Raw LDS positions outside [pshift, pshift + tile_nnz) may hold anything (the interior
-// staging path does not clear them): the bit at pshift isolates what precedes the tile and
-// nothing reads S past the tile's last nonzero.
-// ---------------------------------------------------------------------------
-// 16-byte units of the staged products are XOR-swizzled when a thread of the nonzero phase
-// owns 2 or 4 of them (lanes 8 or 4 apart would otherwise start in the same banks).
-template <typename V, int CPT>
-__device__ __forceinline__ int prod_unit(int u)
-{
-    constexpr int UPT = CPT * 4 * (int) sizeof(V) / 16;
-    // UPT == 6 (fp64, 12 products per thread): lanes 8 apart start 48 units apart = the same banks
-    return UPT == 4 ? u ^ ((u >> 4) & 3) : UPT == 2 ? u ^ ((u >> 4) & 1) : UPT == 6 ? u ^ ((u / 48) & 1) : u;
-}
-template <typename V, int CPT>
-__device__ __forceinline__ int prod_slot(int e)      // element index (>= 0) in raw order -> LDS element index
-{
-    constexpr int EPU = 16 / (int) sizeof(V);
-    return prod_unit<V, CPT>(e / EPU) * EPU + (e % EPU);
-}
-// (plain: the lean row phase of short-row tiles, consume_tile_rows, reads the products of a row at consecutive addresses)
-template <typename V, int CPT>
-__device__ __forceinline__ int prod_unit(int u, bool plain) { return plain ? u : prod_unit<V, CPT>(u); }
-template <typename V, int CPT>
-__device__ __forceinline__ int prod_slot(int e, bool plain) { return plain ? e : prod_slot<V, CPT>(e); }
-template <int CPT>
-__device__ __forceinline__ void st_prod_chunk(float *s_prod_raw, int chunk, const float (&v)[4], bool plain = false)
-{
-    st_lds4(&s_prod_raw[4 * prod_unit<float, CPT>(chunk, plain)], v);
-}
-template <int CPT>
-__device__ __forceinline__ void st_prod_chunk(double *s_prod_raw, int chunk, const double (&v)[4], bool plain = false)
-{
-    double2v a, b; a.x = v[0]; a.y = v[1]; b.x = v[2]; b.y = v[3];
-    *reinterpret_cast<double2v *>(&s_prod_raw[2 * prod_unit<double, CPT>(2 * chunk, plain)]) = a;
-    *reinterpret_cast<double2v *>(&s_prod_raw[2 * prod_unit<double, CPT>(2 * chunk + 1, plain)]) = b;
-}
-__device__ __forceinline__ void ld_unit(const float *p, float *out)
-{ const float4v w = *reinterpret_cast<const float4v *>(p); out[0] = w.x; out[1] = w.y; out[2] = w.z; out[3] = w.w; }
-__device__ __forceinline__ void ld_unit(const double *p, double *out)
-{ const double2v w = *reinterpret_cast<const double2v *>(p); out[0] = w.x; out[1] = w.y; }
-__device__ __forceinline__ void st_unit(float *p, const float *in)
-{ float4v w; w.x = in[0]; w.y = in[1]; w.z = in[2]; w.w = in[3]; *reinterpret_cast<float4v *>(p) = w; }
-__device__ __forceinline__ void st_unit(double *p, const double *in)
-{ double2v w; w.x = in[0]; w.y = in[1]; *reinterpret_cast<double2v *>(p) = w; }
-
-// one Kogge-Stone step of the wave's inclusive segmented sum over (flag, value) pairs
-template <typename V, int CTRL, int ROW_MASK>
-__device__ __forceinline__ void seg_step(int &f, V &v)
-{
-    const int f2 = dpp_move<CTRL, ROW_MASK>(0, f);
-    const V v2 = dpp_move<CTRL, ROW_MASK>((V) 0, v);
-    v += f ? (V) 0 : v2;
-    f |= f2;
-}
-// Block-wide EXCLUSIVE segmented sum: returns the sum of `val` over the threads before this
-// one back to (and including) the nearest preceding thread with flag set.  One barrier inside.
-template <typename V, int BLOCK>
-__device__ __forceinline__ V block_exclusive_segsum(bool flag, V val, int *s_wave_flag, V *s_wave_val, int tid_in = -1)
-{
-    constexpr int NW = BLOCK / WAVE;
-    const unsigned tidu = tid_in < 0 ? threadIdx.x : (unsigned) tid_in;       // (tid_in: see tile_kernel_band)
-    const int lane = tidu & (WAVE - 1);
-    const int wave = tidu / WAVE;
-    int f = flag ? 1 : 0;
-    V v = val;
-    seg_step<V, 0x111, 0xf>(f, v);      // row_shr:1
-    seg_step<V, 0x112, 0xf>(f, v);      // row_shr:2
-    seg_step<V, 0x114, 0xf>(f, v);      // row_shr:4
-    seg_step<V, 0x118, 0xf>(f, v);      // row_shr:8
-    seg_step<V, 0x142, 0xa>(f, v);      // row_bcast15 into rows 1 and 3
-    seg_step<V, 0x143, 0xc>(f, v);      // row_bcast31 into rows 2 and 3
-    if (lane == WAVE - 1) { s_wave_flag[wave] = f; s_wave_val[wave] = v; }
-    __syncthreads();
-    V pv = 0;                           // segmented sum of the preceding waves, in order
-#pragma unroll
-    for (int w = 0; w < NW - 1; ++w) {
-        if (w < wave) { const V wv = s_wave_val[w]; pv = s_wave_flag[w] ? wv : pv + wv; }
-    }
-    const int ef = __shfl_up(f, 1, WAVE);
-    const V ev = __shfl_up(v, 1, WAVE);
-    return lane == 0 ? pv : (ef ? ev : pv + ev);
-}
-
-template <typename V, int BLOCK, int IPT, bool AXPBY, int LB_BATCH = 1, typename MV = V>
-__device__ __forceinline__ void consume_tile_flags(const Params<V, MV> &p, const Coord c0, int tile_rows, int tile_nnz,
-                                                   const end16_t *s_end, V *s_prod_raw, unsigned *s_flag,
-                                                   int *s_wave_flag, V *s_wave_val, Carry<V> *__restrict__ carry_out,
-                                                   int pshift, unsigned long long *tr = nullptr, const LookBack *lb = nullptr,
-                                                   int tile = 0, bool publish = false, int first_row_tile = 0, int tid_in = -1,
-                                                   int first_row_start = 0)
-{
-    constexpr int TAKE_BATCH = LB_BATCH;
-    constexpr int CPT = IPT / 4 + 1;
-    constexpr int NPT = CPT * 4;                  // staged products per thread
-    constexpr int EPU = 16 / (int) sizeof(V);     // elements per 16-byte unit
-    constexpr int UPT = NPT / EPU;
-    constexpr int FLAG_WORDS = CPT * BLOCK * 4 / 32 + 1;
-    static_assert(NPT <= 16 && FLAG_WORDS <= BLOCK, "flag word handling");
-    const int tid = tid_in < 0 ? (int) threadIdx.x : tid_in;
-
-    // one-launch path: a tile that will publish ANNOUNCES itself now -- the thread that will store the record exchanges a marker into
-    // the slot; the answer is looked at when the sum is there (rec_store), by then it has long arrived ("EVERY RECORD SLOT IS CLEAN")
-    // (a group leader -- "GROUP RECORDS"; first_row_tile < tile only when the tile begins inside a row that began in an earlier one --
-    //  publishes the group's slot, by thread 0; a piece without a row end its own, by the thread that holds its last nonzero; a tile
-    //  with row ends its own, by the last thread)
-    const bool leader = lb != nullptr && publish && tile_rows == 0 && tile % LB_GROUP == LB_GROUP - 1 && first_row_tile <= tile - (LB_GROUP - 1);
-    unsigned long long announced = 0ull;
-    if (lb != nullptr && publish) {
-        const int pub_thread = tile_rows > 0 ? BLOCK - 1 : leader ? 0 : tile_nnz > 0 ? (pshift + tile_nnz - 1) / NPT : 0;
-        if (tid == pub_thread) announced = lb_announce(*lb, leader ? lb->group_base + tile / LB_GROUP : tile);
-    }
-
-    // ---- nonzero phase
-    V s[NPT];
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) ld_unit(&s_prod_raw[prod_unit<V, CPT>(tid * UPT + u) * EPU], &s[u * EPU]);
-    const int base = tid * NPT;
-    const unsigned lo = s_flag[base >> 5], hi = s_flag[(base >> 5) + 1];
-    const unsigned m = (unsigned) ((((unsigned long long) hi << 32) | lo) >> (base & 31)) & ((1u << NPT) - 1u);
-    V run = 0;
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        run = ((m >> k) & 1u) ? s[k] : run + s[k];
-        s[k] = run;
-    }
-    if (tr && tid == 0) tr[6] = clock64();
-    const V carry_in = block_exclusive_segsum<V, BLOCK>(m != 0u, run, s_wave_flag, s_wave_val, tid_in);
-    const unsigned lead = (m & (0u - m)) - 1u;    // bits below the first row start (all ones when none)
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) s[k] += ((lead >> k) & 1u) ? carry_in : (V) 0;
-    if (tile_rows == 0) {
-        // block-uniform: no row ends in this tile (a slice of one long row): only the running sum
-        // at the tile's last nonzero is needed -- the carry.  No write-back, no third barrier.
-        if (tid < FLAG_WORDS) s_flag[tid] = 0u;
-        const int last = pshift + tile_nnz - 1;
-        if (tile_nnz > 0 ? tid == last / NPT : tid == 0) {
-            V v = 0;
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) v = (tile_nnz > 0 && k == last % NPT) ? s[k] : v;
-            Carry<V> c; c.key = c0.x; c.value = v;
-            if (p.band_pass > 0) c.value += carry_out->value;      // later column-band pass: same tile, same key
-            *carry_out = c;
-            if (lb && publish && !leader) lb_publish<V>(*lb, tile, v, announced);   // (only when some tile will take it)
-            if (leader) s_wave_val[0] = v;
-        }
-        if (leader) {
-            // (block-uniform) the group's total: the LB_GROUP - 1 records before this tile, by one wave, + this tile's own sum
-            __syncthreads();
-            const V own = s_wave_val[0];
-            bool ok = true;
-            V before = 0;
-            if (tid < WAVE) before = lb_take_wave<V>(*lb, tile, LB_GROUP - 1, ok);
-            if (__syncthreads_or(ok ? 0 : 1)) {
-                // a poll ran out: the nonzeros of the group's earlier tiles, from the matrix (they are the row's, one tile's worth each --
-                // or from the row's first nonzero, when the group begins with the row's first piece)
-                const int j0 = first_row_tile == tile - (LB_GROUP - 1) ? first_row_start : c0.y - (LB_GROUP - 1) * (BLOCK * IPT);
-                before = recompute_row_head<V, BLOCK>(p, j0, c0.y, s_wave_val);
-                if (tid == 0 && lb->error) {
-                    __hip_atomic_store(lb->error, (int) lb->call_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_fetch_add(lb->error + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            if (tid == 0) lb_publish<V>(*lb, lb->group_base + tile / LB_GROUP, before + own, announced);
-        }
-        return;
-    }
-#pragma unroll
-    for (int u = 0; u < UPT; ++u) st_unit(&s_prod_raw[prod_unit<V, CPT>(tid * UPT + u) * EPU], &s[u * EPU]);
-    __syncthreads();
-    if (tr && tid == 0) tr[7] = clock64();
-    if (tid < FLAG_WORDS) s_flag[tid] = 0u;       // clean for the next tile's staging (after the loop's barrier)
-
-    // ---- the row left open at the tile end (ref: agent_spmv_orig.cuh:906-913): the carry.  Written -- and, on the
-    //      single-launch path, published for the tile in which that row ends -- BEFORE the row phase, as early as it exists
-    if (tid == BLOCK - 1) {
-        const int e_last = tile_rows > 0 ? s_end[tile_rows - 1] : 0;
-        Carry<V> c; c.key = c0.x + tile_rows;
-        c.value = tile_nnz > e_last ? s_prod_raw[prod_slot<V, CPT>(pshift + tile_nnz - 1)] : (V) 0;
-        if (p.band_pass > 0) c.value += carry_out->value;
-        *carry_out = c;
-        if (lb && publish) lb_publish<V>(*lb, tile, c.value, announced);
-    }
-    // single-launch path: the pieces of this tile's first row held by tiles [first_row_tile, tile) (thread 0 stores row 0).
-    // Up to 64 of them: wave 0 alone, while the other waves go on with the row phase; more: the whole block.
-    V first_row_carry = 0;
-    if (lb) {
-        const int pieces = tile - first_row_tile;            // block-uniform
-        if (pieces > 0) {
-            bool ok = true;
-            // the complete groups among the pieces [first_row_tile, tile): their leaders folded them into group records
-            const int g_first = (first_row_tile + LB_GROUP - 1) / LB_GROUP, g_end = tile / LB_GROUP;
-            if (g_first < g_end) {
-                const int n_tail = tile - g_end * LB_GROUP, n_groups = g_end - g_first, n_head = g_first * LB_GROUP - first_row_tile;
-                const int gb = lb->group_base;
-                // nearest first: the single records after the last complete group, the group records, the singles before the first
-                first_row_carry = lb_take_block<V, BLOCK, TAKE_BATCH>(*lb, n_tail + n_groups + n_head, s_wave_val, ok, [=](int i) {
-                    return i < n_tail ? tile - 1 - i : i < n_tail + n_groups ? gb + g_end - 1 - (i - n_tail) : g_first * LB_GROUP - 1 - (i - n_tail - n_groups); });
-            } else if (pieces > WAVE) first_row_carry = lb_take_block<V, BLOCK, TAKE_BATCH>(*lb, pieces, s_wave_val, ok, [=](int i) { return tile - 1 - i; });
-            else if (tid < WAVE) first_row_carry = lb_take_wave<V>(*lb, tile, pieces, ok);
-            // a poll ran out (see "NOTHING DEPENDS ON A RECORD ARRIVING" above): the whole block computes the sum from the
-            // matrix -- the row's nonzeros before this tile (its cancelled slots are wiped by their publishers when those come)
-            if (__syncthreads_or(ok ? 0 : 1)) {
-                first_row_carry = recompute_row_head<V, BLOCK>(p, first_row_start, c0.y, s_wave_val);
-                if (tid == 0 && lb->error) {
-                    __hip_atomic_store(lb->error, (int) lb->call_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_fetch_add(lb->error + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-    }
-
-    // ---- row phase
-    V *__restrict__ y = p.y + c0.x;
-    for (int r = tid; r < tile_rows; r += BLOCK) {
-        const int e = s_end[r];
-        const int e0 = r > 0 ? s_end[r - 1] : 0;
-        V sum = e > e0 ? s_prod_raw[prod_slot<V, CPT>(pshift + e - 1)] : (V) 0;
-        if (r == 0) sum += first_row_carry;
-        if (AXPBY) y[r] = p.alpha * sum + (p.beta == (V) 0 ? (V) 0 : p.beta * y[r]);
-        else y[r] = sum;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// LEAN in-tile reduction for tiles of short rows (tile_kernel_snap): when a row-snapped tile is CLOSED -- it starts at the
-// first nonzero of a row and ends with the last nonzero of a row: nothing flows in, nothing is left open -- and its rows
-// are short on average, the flag bits, the per-thread running sums, the block-wide segmented scan, the write-back of the
-// running sums and two of the three barriers of consume_tile_flags buy nothing: a thread takes a whole row and adds
-// up its products straight from LDS.  What bounds a matrix of 4-7 nonzeros per row that lives in the Infinity Cache (the
-// reference's --dense=5, the 5/7-point grids) is VALU issue, not bytes (profiles/r03_short_rows/): the general reduction
-// costs ~290 vector instructions per wave and tile, this one ~60 on such a tile.
-//   * products were staged at their RAW positions (prod_unit(u, plain = true)), so row r's products are the consecutive
-//     LDS elements [pshift + e0, pshift + e1), read with immediate offsets from one address per row;
-//   * summation order: strictly left to right from +0.0 -- for every row of at most LEAN_SERIAL nonzeros that IS the order of
-//     the reference's SpmvGold (gpu_spmv.cu:262-278: partial = 0; partial += v * x, one product at a time), so such rows
-//     are bit for bit the sequential definition's; longer rows (rare in a tile that qualifies) are summed by the 16 lanes
-//     of a DPP row, strided, then folded: another fixed order;
-//   * which reduction a tile takes depends only on its boundaries (closed, nonzeros <= lean_avg * rows), i.e. on the
-//     matrix and the tile shape -- never on hints, timing or the device.
-// ---------------------------------------------------------------------------
-// which tile shapes take the branch likelihoods below: the small ones (what a small problem runs on).  In the fp64 256x11 kernel the
-// same hints changed nothing on a full device (dense5, the grids, dense32, circuit, Orkut-sized within +-0.5 %), in the fp32 one
-// they cost spills.
-template <typename V, int IPT> constexpr bool layout_hints() { return IPT <= 7; }
-#define MSPMV_LIKELY(on, c) ((on) ? __builtin_expect(!!(c), 1) : !!(c))      // (on: a constant -- which tile shapes take the hint)
-#define MSPMV_UNLIKELY(on, c) ((on) ? __builtin_expect(!!(c), 0) : !!(c))
-// acc += v[j] for j < len - base, j = 0 .. 7, left to right, under a SHRINKING EXEC MASK: v_cmpx + v_add per product -- the lanes
-// leave as their row ends -- instead of compare + select(s) + add (3 instructions per product in fp32, 4 in fp64).  The same additions
-// in the same order as `acc = j < len ? acc + v[j] : acc`; EXEC is restored.  (The lean reductions of short-row tiles are bound by
-// VALU issue, not bytes: profiles/r04_short_rows/.)
-template <typename V> struct CompactChain;
-template <> struct CompactChain<double> {
-    // the first half alone: rows of at most four products (the caller knows that no lane of the wave has more)
-    static __device__ __forceinline__ void add4(double &acc, const double (&v)[4], int len)
-    {
-        unsigned long long sv;
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 0, %[l]\n\tv_add_f64 %[a], %[a], %[v0]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 1, %[l]\n\tv_add_f64 %[a], %[a], %[v1]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 2, %[l]\n\tv_add_f64 %[a], %[a], %[v2]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 3, %[l]\n\tv_add_f64 %[a], %[a], %[v3]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(sv)
-                     : [l] "v"(len), [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3])
-                     : "vcc");
-    }
-    // acc (+0.0 on entry) += v[j] for j < len, left to right, lanes leaving as their row ends (EXEC restored)
-    static __device__ __forceinline__ void add8(double &acc, const double (&v)[8], int len, int base)
-    {
-        unsigned long long sv;
-        const int l = len - base;
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 0, %[l]\n\tv_add_f64 %[a], %[a], %[v0]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 1, %[l]\n\tv_add_f64 %[a], %[a], %[v1]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 2, %[l]\n\tv_add_f64 %[a], %[a], %[v2]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 3, %[l]\n\tv_add_f64 %[a], %[a], %[v3]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 4, %[l]\n\tv_add_f64 %[a], %[a], %[v4]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 5, %[l]\n\tv_add_f64 %[a], %[a], %[v5]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 6, %[l]\n\tv_add_f64 %[a], %[a], %[v6]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 7, %[l]\n\tv_add_f64 %[a], %[a], %[v7]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(sv)
-                     : [l] "v"(l), [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [v4] "v"(v[4]), [v5] "v"(v[5]), [v6] "v"(v[6]), [v7] "v"(v[7])
-                     : "vcc");
-    }
-};
-template <> struct CompactChain<float> {
-    // the first half alone: rows of at most four products (the caller knows that no lane of the wave has more)
-    static __device__ __forceinline__ void add4(float &acc, const float (&v)[4], int len)
-    {
-        unsigned long long sv;
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 0, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v0]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 1, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v1]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 2, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v2]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 3, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v3]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(sv)
-                     : [l] "v"(len), [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3])
-                     : "vcc");
-    }
-    static __device__ __forceinline__ void add8(float &acc, const float (&v)[8], int len, int base)
-    {
-        unsigned long long sv;
-        const int l = len - base;
-        asm volatile("s_mov_b64 %[sv], exec\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 0, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v0]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 1, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v1]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 2, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v2]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 3, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v3]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 4, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v4]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 5, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v5]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 6, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v6]\n\t"
-                     "v_cmpx_lt_i32_e32 vcc, 7, %[l]\n\tv_add_f32_e32 %[a], %[a], %[v7]\n\t"
-                     "s_mov_b64 exec, %[sv]"
-                     : [a] "+v"(acc), [sv] "=&s"(sv)
-                     : [l] "v"(l), [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]), [v4] "v"(v[4]), [v5] "v"(v[5]), [v6] "v"(v[6]), [v7] "v"(v[7])
-                     : "vcc");
-    }
-};
-constexpr int LEAN_SERIAL = 16;        // rows up to this long are summed by one thread
-constexpr int LEAN_GROUP_MAX = 256;    // rows up to this long (and longer than LEAN_SERIAL) are summed by the 16 lanes of one DPP row; longer ones by the wave
-// Rows of a lean tile that are longer than LEAN_SERIAL -- every lane of the wave calls this with ITS row's first product position
-// `pos` (LDS element index), length `len` (0: no row) and running sum `acc`; the owners of such rows get their row's total in `acc`.
-//   * LEAN_SERIAL < len <= LEAN_GROUP_MAX: four rows at a time, each by the 16 lanes of one DPP row -- lane j adds products j, j + 16, ...
-//     from +0.0, the 16 partial sums are folded left to right (row_shr 1, 2, 4, 8): summation depth <= len / 16 + 4 <= 20;
-//   * longer rows (a closed lean tile can hold ONE row of ~2000-3000 nonzeros next to hundreds of empty ones): one at a time by the
-//     whole wave -- lane j keeps FOUR running sums, over products j + 64 u + 256 r (u = 0 .. 3), adds them pairwise, and the 64
-//     totals are folded by row_shr 1, 2, 4, 8, row_bcast 15 and 31: depth <= len / 256 + 2 + 6 <= 20 for any row a tile can hold.
-//     (Until round 5 these rows went to a 16-lane group as well: depth len / 16 + 4, ~150 for such a row -- beyond the
-//      2 (ceil(log2(len + 1)) + items_per_thread + 8) of the stated bound, which the tests then only met statistically.)
-// A fixed order either way; shared by consume_tile_rows and the compact front end, so the two write the same bits.
-template <typename V>
-__device__ __forceinline__ void lean_long_rows(const V *s_prod, int pos, int len, int lane, V &acc)
-{
-    unsigned long long pending = __ballot(len > LEAN_SERIAL && len <= LEAN_GROUP_MAX);
-    while (pending != 0ull) {                                           // wave-uniform
-        int owner[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            owner[g] = pending != 0ull ? __ffsll((long long) pending) - 1 : -1;
-            pending &= pending - 1ull;                                  // (0 stays 0)
-        }
-        const int grp = lane >> 4, j = lane & 15;
-        const int own = grp == 0 ? owner[0] : grp == 1 ? owner[1] : grp == 2 ? owner[2] : owner[3];
-        // (both shuffles by ALL lanes, the selection afterwards: a lane switched off by a branch cannot be read from)
-        const int g_pos = __shfl(pos, own < 0 ? 0 : own, WAVE);
-        const int g_len_any = __shfl(len, own < 0 ? 0 : own, WAVE);
-        const int g_len = own < 0 ? 0 : g_len_any;
-        const V *gsrc = s_prod + g_pos;
-        V part = (V) 0;
-        for (int k = j; __ballot(k < g_len) != 0ull; k += 64) {
-            V u4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) u4[u] = k + 16 * u < g_len ? gsrc[k + 16 * u] : (V) 0;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) part += u4[u];
-        }
-        part += dpp_move<0x111, 0xf>((V) 0, part);                     // row_shr:1
-        part += dpp_move<0x112, 0xf>((V) 0, part);                     // row_shr:2
-        part += dpp_move<0x114, 0xf>((V) 0, part);                     // row_shr:4
-        part += dpp_move<0x118, 0xf>((V) 0, part);                     // row_shr:8  -> lane 15 of every row holds its total
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const V total = __shfl(part, 16 * g + 15, WAVE);
-            if (lane == owner[g]) acc = total;
-        }
-    }
-    pending = __ballot(len > LEAN_GROUP_MAX);
-    while (pending != 0ull) {                                           // wave-uniform: one row per round, by the whole wave
-        const int own = __ffsll((long long) pending) - 1;
-        pending &= pending - 1ull;
-        const int g_pos = __shfl(pos, own, WAVE), g_len = __shfl(len, own, WAVE);
-        const V *gsrc = s_prod + g_pos;
-        V a4[4] = {(V) 0, (V) 0, (V) 0, (V) 0};
-        for (int k = lane; k < g_len; k += 4 * WAVE) {                  // (the lanes leave as the row runs out: no ballot needed, nothing is exchanged inside)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a4[u] += k + WAVE * u < g_len ? gsrc[k + WAVE * u] : (V) 0;
-        }
-        V part = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-        part += dpp_move<0x111, 0xf>((V) 0, part);                     // row_shr:1
-        part += dpp_move<0x112, 0xf>((V) 0, part);                     // row_shr:2
-        part += dpp_move<0x114, 0xf>((V) 0, part);                     // row_shr:4
-        part += dpp_move<0x118, 0xf>((V) 0, part);                     // row_shr:8  -> lane 15 of every row of 16 holds that row's total
-        part += dpp_move<0x142, 0xa>((V) 0, part);                     // row_bcast15 into rows 1 and 3
-        part += dpp_move<0x143, 0xc>((V) 0, part);                     // row_bcast31 into rows 2 and 3 -> lane 63 holds the total
-        const V total = __shfl(part, WAVE - 1, WAVE);
-        if (lane == own) acc = total;
-    }
-}
-
-constexpr int LEAN_BATCH = 8;          // products of a row requested before any is looked at
-template <typename V, int BLOCK, int IPT, bool AXPBY, typename MV = V>
-__device__ __forceinline__ void consume_tile_rows(const Params<V, MV> &p, const Coord c0, int tile_rows, const end16_t *s_end,
-                                                  const V *s_prod_raw, int pshift, Carry<V> *__restrict__ carry_out,
-                                                  unsigned long long *tr = nullptr)
-{
-    const int tid = threadIdx.x;
-#ifdef MSPMV_DEV
-#define MSPMV_LEAN_TR(i) do { if (tr && tid == 0) tr[i] = wall_clock64(); } while (0)
-#else
-#define MSPMV_LEAN_TR(i) do { } while (0)
-#endif
-    MSPMV_LEAN_TR(8);
-    if (tid == BLOCK - 1) { Carry<V> c; c.key = c0.x + tile_rows; c.value = (V) 0; *carry_out = c; }     // (nothing open: what mspmv_debug_read_tiles reports)
-    V *__restrict__ y = p.y + c0.x;
-    // Two rows per thread and iteration (r, r + BLOCK), and every LDS read of a step requested before the first is waited for:
-    // the row ends of both rows, then the first LEAN_BATCH products of both (read whether the row has them or not: they lie
-    // inside the LDS arrays for any lane, pshift + e0 + 15 < SLOTS) -- two LDS round trips per pair of rows instead of six.
-    for (int r0 = 0; r0 < tile_rows; r0 += 2 * BLOCK) {           // block-uniform trip count
-        int e0[2], len[2]; bool valid[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int r = r0 + h * BLOCK + tid;
-            valid[h] = r < tile_rows;
-            const int rr = valid[h] ? r : 0;                       // (row 0 exists: tile_rows > 0 here)
-            const int e1 = s_end[rr];
-            const int ep = s_end[rr > 0 ? rr - 1 : 0];             // (read whatever rr is: a select afterwards, not a branch around a second LDS round trip)
-            e0[h] = rr > 0 ? ep : 0;
-            len[h] = valid[h] ? e1 - e0[h] : 0;
-        }
-        if (r0 == 0) MSPMV_LEAN_TR(9);
-        // (a wave none of whose rows -- of this pair of rounds -- has more than four products reads and adds the first four of each only: the
-        //  row-strided product reads are bank-conflict-laden, 57 % of the LDS cycles of a 5-point grid's launch, and the LDS is busy for more
-        //  than half of such a kernel: profiles/r05_lds_counters.txt)
-        const bool more = __ballot(len[0] > LEAN_BATCH / 2 || len[1] > LEAN_BATCH / 2) != 0ull;      // wave-uniform
-        V v[2][LEAN_BATCH];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int j = 0; j < LEAN_BATCH / 2; ++j) v[h][j] = s_prod_raw[pshift + e0[h] + j];
-        V acc[2] = {(V) 0, (V) 0};
-        static_assert(LEAN_BATCH == 8, "CompactChain adds eight");
-        if (more) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int j = LEAN_BATCH / 2; j < LEAN_BATCH; ++j) v[h][j] = s_prod_raw[pshift + e0[h] + j];
-            // (all of them requested here, in one go: without this the compiler sinks a read into the branch of the first addition that uses it)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int j = 0; j < LEAN_BATCH; ++j) asm volatile("" : "+v"(v[h][j]));
-#pragma unroll
-            for (int h = 0; h < 2; ++h) CompactChain<V>::add8(acc[h], v[h], len[h], 0);
-        } else {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int j = 0; j < LEAN_BATCH / 2; ++j) asm volatile("" : "+v"(v[h][j]));
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { const V q[4] = {v[h][0], v[h][1], v[h][2], v[h][3]}; CompactChain<V>::add4(acc[h], q, len[h]); }
-        }
-        if (r0 == 0) MSPMV_LEAN_TR(10);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const V *src = s_prod_raw + (pshift + e0[h]);
-            // rows of LEAN_BATCH + 1 ... LEAN_SERIAL nonzeros: the same left-to-right order, continued
-            if (MSPMV_UNLIKELY((layout_hints<V, IPT>()), __ballot(len[h] > LEAN_BATCH) != 0ull)) {
-                V w[LEAN_SERIAL - LEAN_BATCH];
-#pragma unroll
-                for (int j = 0; j < LEAN_SERIAL - LEAN_BATCH; ++j) w[j] = src[LEAN_BATCH + j];
-                CompactChain<V>::add8(acc[h], w, len[h], LEAN_BATCH);
-            }
-            // rows longer than that: by 16-lane groups, the longest by the whole wave (lean_long_rows)
-            if (MSPMV_UNLIKELY((layout_hints<V, IPT>()), __ballot(len[h] > LEAN_SERIAL) != 0ull))
-                lean_long_rows<V>(s_prod_raw, pshift + e0[h], len[h], tid & (WAVE - 1), acc[h]);
-            if (r0 == 0 && h == 0) MSPMV_LEAN_TR(11);
-            if (valid[h]) {
-                const int r = r0 + h * BLOCK + tid;
-                if (AXPBY) y[r] = p.alpha * acc[h] + (p.beta == (V) 0 ? (V) 0 : p.beta * y[r]);
-                else y[r] = acc[h];
-            }
-        }
-    }
-    MSPMV_LEAN_TR(12);
-#undef MSPMV_LEAN_TR
-}
-
-// ---------------------------------------------------------------------------
-// One block per tile, dword-per-lane staging: the fallback for CSR arrays
-// whose base addresses are not 16-byte aligned and for tiny matrices.
-// ref: DeviceSpmvKernel / AgentSpmv::ConsumeTile, dispatch_spmv_orig.cuh:157-186,
-// agent_spmv_orig.cuh:413-639,856-914.
-// ---------------------------------------------------------------------------
-template <typename V, int BLOCK, int IPT, bool AXPBY, typename MV = V>
-__global__ __launch_bounds__(BLOCK) void tile_kernel(Params<V, MV> p, const Coord *__restrict__ coords,
-                                                     Carry<V> *__restrict__ carries, int num_tiles)
-{
-    constexpr int TILE = BLOCK * IPT;
-    constexpr int NW = BLOCK / WAVE;
-    constexpr int PAD = IPT + 4;
-    __shared__ int s_end[TILE + PAD];
-    __shared__ V s_prod[TILE + PAD];
-    __shared__ int s_wave_key[NW];
-    __shared__ V s_wave_val[NW];
-
-    const int tile = blockIdx.x;
-    const int tid = threadIdx.x;
-    const Coord c0 = coords[tile];
-    const Coord c1 = coords[tile + 1];
-    const int tile_rows = c1.x - c0.x;
-    const int tile_nnz = c1.y - c0.y;
-
-    const int *__restrict__ cols = p.cols + c0.y;
-    const MV *__restrict__ vals = p.values + c0.y;
-    int col_r[IPT];
-    MV val_r[IPT];
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        const int j = tid + k * BLOCK;
-        if (j < tile_nnz) { col_r[k] = cols[j]; val_r[k] = vals[j]; }
-    }
-    const int *__restrict__ row_end = p.row_end + c0.x;
-    for (int r = tid; r < TILE + PAD; r += BLOCK) s_end[r] = r < tile_rows ? row_end[r] - c0.y : 0x3fffffff;
-#pragma unroll
-    for (int k = 0; k < IPT; ++k) {
-        const int j = tid + k * BLOCK;
-        s_prod[j] = j < tile_nnz ? widen<V>(val_r[k]) * p.x[col_r[k]] : (V) 0;
-    }
-    if (tid < PAD) s_prod[TILE + tid] = (V) 0;
-    __syncthreads();
-    consume_tile_lds<V, BLOCK, IPT, AXPBY>(p, c0, tile_rows, tile_nnz, s_end, s_prod, s_prod, s_wave_key, s_wave_val,
-                                           carries + tile);
-}
-
-// ---------------------------------------------------------------------------
-// The production kernel: 16-byte streaming loads, LDS-staged products, flag/segmented-scan
-// reduction (consume_tile_flags).  PERSIST = false (default): one tile per block; the
-// hardware's block scheduler balances the load and de-phases the blocks of a CU.
-// PERSIST = true (tuning flags): a block walks tiles blockIdx.x, +gridDim.x, ... and requests
-// the NEXT tile's nonzeros (into the registers the current tile has just drained into LDS)
-// before the LDS phases of the current one.  The persistent form was the faster one while the
-// in-tile reduction was the per-thread path walk; measured with the present reduction a resident
-// grid is 7-10 % slower on streaming matrices and 2-4 tiles per block are within +-3 % of one
-// (tools/sweep.py with SWEEP_FLAGS=0x100000..0x800000), so the simpler launch is the default.
-// What bounds the kernel is the CU's vector-memory pipeline: cycle stamps (tools/trace_tiles.py)
-// show ~70 % of a block's life spent issuing into / waiting on it, and throughput follows the
-// number of cache lines requested per tile, not the instruction count of the LDS phases.
-//
-// Staging works on 4-element chunks aligned in ARRAY index space (the CSR
-// arrays are 16-byte aligned -- checked by the dispatcher -- but a tile starts
-// anywhere): chunk addresses are clamped to the last full chunk of the array
-// instead of being branched around, so every load is unconditional,
-// straight-line code (a branch per chunk made hipcc wait for each load before
-// issuing the next); elements outside the tile are predicated off, and the
-// <= 3 elements of a ragged array tail are read by scalar loads in a rarely
-// taken branch.  Nothing outside [0,nnz) / [0,rows] is ever read.
-// ---------------------------------------------------------------------------
-// Resident blocks per CU the vectorised tile kernels are compiled for: what their LDS
-// footprint admits (160 KiB per CU), at most 32 waves per CU.  Passed to __launch_bounds__ as
-// waves per SIMD: left alone, hipcc spent 92-104 VGPRs on these kernels (4-5 waves/SIMD); told
-// the target it fits 64-80 without spilling, which is what actually sets the residency.
-template <typename V, int BLOCK, int IPT, bool WIDE_ENDS = false>
-constexpr int tile_blocks_per_cu()
-{
-    constexpr int slots = (IPT / 4 + 1) * BLOCK * 4;
-    constexpr int lds = slots * ((WIDE_ENDS ? 4 : 2) + (int) sizeof(V)) + slots / 8 + 256;      // products, row ends (16-bit; 32 for the walk), flag bits
-    constexpr int by_lds = 163840 / lds;
-    constexpr int by_waves = 2048 / BLOCK;
-    return by_lds < by_waves ? (by_lds < 1 ? 1 : by_lds) : by_waves;
-}
-template <typename V, int BLOCK, int IPT, bool RELAX = false, bool WIDE_ENDS = false>
-constexpr int tile_waves_per_simd()
-{
-    // one wave less than the LDS footprint admits (never more than 6 for fp64): with both
-    // staging paths in the kernel the tighter budget spills 3 registers per lane, and the
-    // measured difference between the two choices is within noise
-    int w = (tile_blocks_per_cu<V, BLOCK, IPT, WIDE_ENDS>() * BLOCK + 255) / 256;
-    if (sizeof(V) == 8 && w > 6) w = 6;
-    if (w > 4 && (!RELAX || WIDE_ENDS)) w -= WIDE_ENDS && w > 5 ? 2 : 1;
-    return w;
-}
-
-// Column-band passes, fp64: the values of a chunk are fetched only when one of its four columns lies in the pass's band
-// (with sorted columns a band's nonzeros are a run inside each row: C2 fp64 skips 57 % of the 32-byte value loads per pass,
-// 1.447 -> 1.342 ms).  Not for fp32: the extra live state spills there (0.87 -> 0.95 ms, and the scratch set-up costs the
-// ordinary body of the same kernel 20 %).
-template <typename V, bool BAND> constexpr bool band_lazy_values() { return BAND && sizeof(V) == 8; }
-
-template <typename V, int BLOCK, int IPT, typename MV = V>
-struct TileRegs {
-    static constexpr int CPT = IPT / 4 + 1;   // 4-element chunks per thread: covers TILE + 3
-    Vec4<int> col[CPT];
-    Vec4<MV> val[CPT];                        // as stored: 16 bytes (fp32), 32 (fp64) or 8 (bf16) per chunk
-};
-
-// fp64 values of a 4-element chunk are 32 bytes: fetched as two 16-byte loads per lane, each load instruction of a wave would
-// touch every 128-byte line of the wave's 2 KB twice, half a line at a time -- and the second touch of a line read with a
-// non-temporal load is another request to L2 (measured: making the second half an ordinary load, which then hits the CU's
-// cache, is worth 5-9 % on dense32 / 7-point-grid streams, but gives the lines ordinary retention and costs the
-// gather-bound matrices 2-3 % of their x hits).  Instead the two loads are laid out line by line: in the first, lanes 0-31
-// fetch the first half of their own chunk and lanes 32-63 the SECOND half of the chunk of lane - 32 (8 whole lines); in the
-// second, lanes 0-31 fetch the first half of the chunk of lane + 32 and lanes 32-63 their own second half; four
-// v_permlane32_swap (gfx950) then hand every lane its own 32 bytes.  Wave-uniform control flow required.
-// (The swaps are a separate step, linewise_own, done by the staging right before the products: next to the loads the compiler
-//  waits for each pair before it requests the next one.)
-template <bool NT>
-__device__ __forceinline__ Vec4<double> ld_stream4_linewise(const double *base, int e_own, int e_partner, int tid)
-{
-    const bool hi = (tid & 32) != 0;
-    const double2v *pa = reinterpret_cast<const double2v *>(base + (hi ? e_partner + 2 : e_own));
-    const double2v *pb = reinterpret_cast<const double2v *>(base + (hi ? e_own + 2 : e_partner));
-    Vec4<double> r;
-    r.a = NT ? __builtin_nontemporal_load(pa) : *pa;
-    r.b = NT ? __builtin_nontemporal_load(pb) : *pb;
-    return r;
-}
-// what ld_stream4_linewise fetched -> every lane's own four values.  Wave-uniform control flow required.
-__device__ __forceinline__ Vec4<double> linewise_own(const Vec4<double> &w)
-{
-    typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-    uint4v ua = __builtin_bit_cast(uint4v, w.a), ub = __builtin_bit_cast(uint4v, w.b);
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        // lanes 32-63 of the first operand <-> lanes 0-31 of the second
-        const auto sw = __builtin_amdgcn_permlane32_swap(ua[d], ub[d], false, false);
-        ua[d] = sw[0]; ub[d] = sw[1];
-    }
-    Vec4<double> r; r.a = __builtin_bit_cast(double2v, ua); r.b = __builtin_bit_cast(double2v, ub);
-    return r;
-}
-__device__ __forceinline__ Vec4<float> linewise_own(const Vec4<float> &w) { return w; }
-__device__ __forceinline__ Vec4<bf16> linewise_own(const Vec4<bf16> &w) { return w; }
-// values as issue_nonzero_loads left them in the tile's registers -> the values of the lane's own chunk k
-// (MV: 8-byte STORED values only -- fp32 values of an fp64 product are one 16-byte load per chunk, the fp32 path's)
-template <typename V, bool NT, bool LAZY, typename MV = V>
-constexpr bool vals_linewise() { return sizeof(MV) == 8 && NT && !LAZY; }
-// WIRE staging (the production kernels): the values stay as ld_stream4_linewise fetched them -- val.a = the first half of the own chunk
-// (lanes 0-31) / the second half of the chunk 32 lanes down (lanes 32-63), val.b = the first half of the chunk 32 lanes up / the own
-// second half -- and the COLUMNS are swapped to match (two v_permlane32_swap instead of four): every lane then multiplies two pairs that
-// belong to two different chunks, and writes each pair where it belongs in the LDS tile.  Lanes 0-31 and 32-63 of one store
-// instruction together cover 1 KB of consecutive 16-byte units (a lane writing its own 32 bytes as two stores 32 bytes apart
-// collided two-way with the lane four further on).  cols[0..1] belong to val.a, cols[2..3] to val.b.
-__device__ __forceinline__ void wire_cols(const Vec4<int> &col, int (&c)[4])
-{
-    const auto s0 = __builtin_amdgcn_permlane32_swap((unsigned) col.v.x, (unsigned) col.v.z, false, false);
-    const auto s1 = __builtin_amdgcn_permlane32_swap((unsigned) col.v.y, (unsigned) col.v.w, false, false);
-    c[0] = (int) s0[0]; c[1] = (int) s1[0]; c[2] = (int) s0[1]; c[3] = (int) s1[1];
-}
-// chunk index (in units of 4 elements, relative to the tile's first chunk) and element offset inside it of the pair in val.a / val.b
-struct WirePos { int qa, qb, off; };
-__device__ __forceinline__ WirePos wire_pos(int q, int tid)
-{
-    const bool hi = (tid & 32) != 0;
-    WirePos w; w.qa = hi ? q - 32 : q; w.qb = hi ? q : q + 32; w.off = hi ? 2 : 0;
-    return w;
-}
-
-// (A wave-uniform skip of chunks that lie past the tile altogether -- one or two of the four waves of a short-row tile -- was built for
-//  the interior staging in round 5 and not kept: every branch around a group of loads makes the compiler wait at the join, and the
-//  result was mixed -- grid3d-200 -2.3 %, band5 -3 %, but the circuit-shaped matrix +8 %, dense32 fp64 +3.5 %, dense5 +2 %:
-//  profiles/r05_ab_wave_skip_general_kernel.txt.  The compact front end, whose loads are few and whose tiles share a CU in small
-//  numbers, keeps it.)
-template <typename V, int BLOCK, int IPT, bool NT, bool VALS = true, bool LINEWISE_OK = true, typename MV = V>
-__device__ __forceinline__ void issue_nonzero_loads(const Params<V, MV> &p, const Coord c0, const Coord c1,
-                                                    TileRegs<V, BLOCK, IPT, MV> &r, int tid_in = -1)
-{
-    const int tid = tid_in < 0 ? (int) threadIdx.x : tid_in;
-    constexpr int CPT = IPT / 4 + 1;
-    const int a0 = c0.y & ~3;
-    const int last_full = (p.nnz & ~3) - 4;        // first element of the array's last full chunk (nnz >= 4)
-    const int safe = a0 < last_full ? a0 : last_full;
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        int e0 = a0 + 4 * (tid + k * BLOCK);
-        // a chunk past the tile (it belongs to the next tile) or past the last full chunk of
-        // the array is not fetched: those lanes re-read the tile's first chunk instead (one
-        // cached address), so no byte of HBM traffic is spent on data this tile does not use
-        e0 = (e0 < c1.y && e0 <= last_full) ? e0 : safe;
-        r.col[k] = ld_stream4<NT>(p.cols + e0);
-        if constexpr (VALS && LINEWISE_OK && vals_linewise<V, NT, false, MV>()) {     // (ordinary loads: the second half hits the CU's cache anyway, and the swaps cost 3 % on dense5)
-            int e1 = a0 + 4 * ((tid ^ 32) + k * BLOCK);          // the chunk of the lane 32 away, by the same rule
-            e1 = (e1 < c1.y && e1 <= last_full) ? e1 : safe;
-            r.val[k] = ld_stream4_linewise<NT>(p.values, e0, e1, tid);
-        } else if constexpr (VALS) r.val[k] = ld_stream4<NT>(p.values + e0);      // (!VALS: column-band passes fetch the values later, by band)
-    }
-}
-
-// Stage one tile whose nonzeros are already in `regs` (requested earlier): row offsets
-// and x gathers are issued, tile-relative row ends and products land in LDS (every slot of
-// both arrays is written: +inf / 0 outside the tile), the ragged array tails are patched,
-// and the block is synchronised.
-// (after_gather: called once the x gathers have been requested -- scalar work of the caller that then runs in the shadow of their
-//  latency instead of after the staging barrier: the hint verdict of tile_kernel_snap)
-struct NoAfterGather { __device__ __forceinline__ void operator()() const {} };
-template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool XL = false, bool BAND = false, typename AG = NoAfterGather, typename MV = V>
-__device__ __forceinline__ void stage_tile_careful(const Params<V, MV> &p, const Coord c0, const Coord c1,
-                                           const TileRegs<V, BLOCK, IPT, MV> &regs, typename EndType<FL>::type *s_end_raw, V *s_prod_raw,
-                                           int last_full_nz, int last_full_ro, unsigned *s_flag, const V *s_x = nullptr, int tid_in = -1,
-                                           bool lean = false, AG after_gather = AG())
-{
-    // lean (block-uniform; FL only): the tile will be reduced row by row (consume_tile_rows) -- no row-start bits, products at their raw positions
-    constexpr int CPT = IPT / 4 + 1;
-    const int tid = tid_in < 0 ? (int) threadIdx.x : tid_in;
-    const int *__restrict__ row_offsets = p.row_end - 1;
-    const int tile_rows = c1.x - c0.x;
-    const int tile_nnz = c1.y - c0.y;
-    const int a0 = c0.y & ~3;
-    const int first = c0.x + 1;                // d_row_offsets index of the tile's first row end
-    const int i0 = first & ~3;
-    const int eshift = first - i0;
-    // ---- row ends of the current tile -> LDS (chunks of d_row_offsets)
-    Vec4<int> ro[CPT];
-    const int ro_chunks = (tile_rows + eshift + 3) / 4;           // chunks holding a row end of this tile
-    const int ro_safe = i0 < last_full_ro ? i0 : last_full_ro;
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int q = tid + k * BLOCK;
-        int i = i0 + 4 * q;
-        i = (q < ro_chunks && i <= last_full_ro) ? i : ro_safe;
-        ro[k] = ld_stream4<NT>(row_offsets + i);
-    }
-    // ---- gather x for the current tile (its nonzeros were requested one iteration ago)
-    V xv[CPT][4];
-    unsigned in_band = 0u;                     // BAND: one bit per staged nonzero of this thread (its column lies in the pass's band)
-    constexpr bool LAZY = band_lazy_values<V, BAND>();
-    Vec4<MV> bval[LAZY ? CPT : 1];              // LAZY: the values, fetched here and only for chunks with a nonzero of the band
-    constexpr bool WIRE = vals_linewise<V, NT, LAZY, MV>() && FL;
-    unsigned wire_in = 0u;                     // WIRE: one bit per held nonzero that lies in the tile
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int e0 = a0 + 4 * (tid + k * BLOCK);
-        if constexpr (WIRE) {
-            int gc[4]; wire_cols(regs.col[k], gc);
-            const WirePos wp = wire_pos(tid + k * BLOCK, tid);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int eb = a0 + 4 * (i < 2 ? wp.qa : wp.qb);             // first element of the chunk this value belongs to
-                const bool in = (unsigned) (eb + wp.off + (i & 1) - c0.y) < (unsigned) tile_nnz && eb <= last_full_nz;
-                wire_in |= in ? 1u << (4 * k + i) : 0u;
-                xv[k][i] = XL ? s_x[in ? gc[i] : 0] : p.x[in ? gc[i] : 0];
-            }
-            continue;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool in = (unsigned) (e0 + i - c0.y) < (unsigned) tile_nnz && e0 <= last_full_nz;
-            if (BAND) {
-                xv[k][i] = (V) 0;
-                if (in && (unsigned) (regs.col[k].get(i) - p.band_lo) < (unsigned) p.band_len) { xv[k][i] = p.x[regs.col[k].get(i)]; in_band |= 1u << (4 * k + i); }
-            } else xv[k][i] = XL ? s_x[in ? regs.col[k].get(i) : 0] : p.x[in ? regs.col[k].get(i) : 0];
-        }
-        if constexpr (LAZY) {
-            zero4(bval[k]);
-            if ((in_band >> (4 * k)) & 0xfu) bval[k] = ld_stream4<NT>(p.values + e0);     // (a bit set => a chunk of this tile, <= last_full_nz)
-        }
-    }
-    after_gather();
-    // ---- stage row ends
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int q = tid + k * BLOCK;
-        const int i = i0 + 4 * q;
-        int v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = 4 * q - eshift + j;
-            const bool in = r >= 0 && r < tile_rows && i <= last_full_ro;
-            v[j] = in ? ro[k].get(j) - c0.y : 0x3fffffff;
-            if (FL && !lean && (unsigned) v[j] < (unsigned) tile_nnz) {
-                const int b = (c0.y - a0) + v[j];
-                atomicOr(&s_flag[b >> 5], 1u << (b & 31));
-            }
-        }
-        st_lds4(&s_end_raw[4 * q], v);
-    }
-    if (FL && !lean && tid == 0) atomicOr(&s_flag[0], 1u << (c0.y - a0));
-    // ---- stage products
-    Vec4<MV> own_val[LAZY || WIRE ? 1 : CPT];
-    if constexpr (!LAZY && !WIRE) {
-#pragma unroll
-        for (int k = 0; k < CPT; ++k) own_val[k] = vals_linewise<V, NT, LAZY, MV>() ? linewise_own(regs.val[k]) : regs.val[k];
-    }
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int chunk = tid + k * BLOCK;
-        const int e0 = a0 + 4 * chunk;
-        if constexpr (WIRE) {
-            const WirePos wp = wire_pos(chunk, tid);
-            const V w[4] = {regs.val[k].get(0), regs.val[k].get(1), regs.val[k].get(2), regs.val[k].get(3)};
-            V pa[2], pb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                pa[i] = ((wire_in >> (4 * k + i)) & 1u) ? w[i] * xv[k][i] : (V) 0;
-                pb[i] = ((wire_in >> (4 * k + 2 + i)) & 1u) ? w[2 + i] * xv[k][2 + i] : (V) 0;
-            }
-            st_unit(&s_prod_raw[2 * prod_unit<V, CPT>(2 * wp.qa + (wp.off >> 1), lean)], pa);
-            st_unit(&s_prod_raw[2 * prod_unit<V, CPT>(2 * wp.qb + (wp.off >> 1), lean)], pb);
-            continue;
-        }
-        V prod[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool in = BAND ? ((in_band >> (4 * k + i)) & 1u) != 0u
-                                 : (unsigned) (e0 + i - c0.y) < (unsigned) tile_nnz && e0 <= last_full_nz;
-            if constexpr (LAZY) prod[i] = in ? bval[k].get(i) * xv[k][i] : (V) 0;
-            else prod[i] = in ? widen<V>(own_val[k].get(i)) * xv[k][i] : (V) 0;
-        }
-        if (FL) st_prod_chunk<CPT>(s_prod_raw, chunk, prod, lean);
-        else st_lds4(&s_prod_raw[swz_prod(4 * chunk)], prod);
-    }
-    // ---- ragged array tails (at most 3 elements each; only the tile that reaches the array
-    //      end).  Block-uniform branch; the barrier orders these writes after the zeros /
-    //      sentinels the chunk owners stored into the same slots above.
-    const bool nz_tail = c1.y > last_full_nz + 4;
-    const bool ro_tail = first + tile_rows > last_full_ro + 4;
-    if (nz_tail || ro_tail) {
-        __syncthreads();
-        const int j = last_full_nz + 4 + tid;                       // absolute nonzero index
-        if (nz_tail && j < c1.y && j >= c0.y) {
-            const int c = ld_stream<NT>(p.cols + j);
-            const bool inb = !BAND || (unsigned) (c - p.band_lo) < (unsigned) p.band_len;
-            s_prod_raw[FL ? prod_slot<V, CPT>(j - a0, lean) : swz_prod(j - a0)] = inb ? widen<V>(ld_stream<NT>(p.values + j)) * (XL ? s_x[c] : p.x[c]) : (V) 0;
-        }
-        const int i = last_full_ro + 4 + tid;                       // absolute d_row_offsets index
-        const int r = i - first;
-        if (ro_tail && r >= 0 && r < tile_rows) {
-            const int v = ld_stream<NT>(row_offsets + i) - c0.y;
-            s_end_raw[r + eshift] = (typename EndType<FL>::type) v;
-            if (FL && !lean && (unsigned) v < (unsigned) tile_nnz) atomicOr(&s_flag[((c0.y - a0) + v) >> 5], 1u << (((c0.y - a0) + v) & 31));
-        }
-    }
-    __syncthreads();
-}
-
-// Interior tiles (all but the handful whose chunk loads would touch the last, ragged chunk of
-// an array -- the matrix's final tile in particular): no per-element predicates at all.
-//  * every column index in a loaded chunk is a valid index even when the element belongs to
-//    the neighbouring tile, so x is gathered unconditionally;
-//  * products of elements outside the tile land in LDS slots the walk never reads as
-//    nonzeros (an item past the tile's nonzeros is always a row end there, and a row end's
-//    product slot is read but discarded by a select, so even a NaN cannot leak);
-//  * row offsets past the tile's last row are REAL offsets (>= the tile's nonzero count), which
-//    serve as the "+inf" the search and the walk need: a row end of a later tile lies at
-//    least IPT path items past every thread of a full tile.
-// Only whole chunks beyond the needed range are redirected to a cached address (no HBM bytes
-// for data the tile does not use).  This removes ~200 of the ~1100 instructions per wave per tile.
-template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool XL = false, bool BAND = false, typename AG = NoAfterGather, typename MV = V>
-__device__ __forceinline__ void stage_tile_interior(const Params<V, MV> &p, const Coord c0, const Coord c1,
-                                                    const TileRegs<V, BLOCK, IPT, MV> &regs,
-                                                    typename EndType<FL>::type *s_end_raw, V *s_prod_raw, unsigned *s_flag,
-                                                    const V *s_x = nullptr, int tid_in = -1, bool lean = false, AG after_gather = AG())
-{
-    constexpr int CPT = IPT / 4 + 1;
-    const int tid = tid_in < 0 ? (int) threadIdx.x : tid_in;
-    const int *__restrict__ row_offsets = p.row_end - 1;
-    const int tile_rows = c1.x - c0.x;
-    const int first = c0.x + 1;
-    const int i0 = first & ~3;
-    const int eshift = first - i0;
-    Vec4<int> ro[CPT];
-    // row ends of the tile (+ the IPT the per-thread walk may peek at)
-    const int ro_chunks = (tile_rows + eshift + (FL ? 0 : IPT) + 3) / 4;
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        // block-uniform: a tile of long rows needs one chunk per thread at most; every vector-memory
-        // instruction spared is a slot in the CU's memory pipeline, which is what this kernel queues on
-        if (k == 0 || k * BLOCK < ro_chunks) {
-            const int q = tid + k * BLOCK;
-            const int i = q < ro_chunks ? i0 + 4 * q : i0;
-            ro[k] = ld_stream4<NT>(row_offsets + (unsigned) i);
-        }
-    }
-    V xv[CPT][4];
-    unsigned in_band = 0u;                     // BAND: one bit per staged nonzero of this thread
-    constexpr bool LAZY = band_lazy_values<V, BAND>();
-    Vec4<MV> bval[LAZY ? CPT : 1];              // LAZY: the values, fetched here and only for chunks with a nonzero of the band
-    constexpr bool WIRE = vals_linewise<V, NT, LAZY, MV>() && FL;
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        if constexpr (WIRE) {
-            int gc[4]; wire_cols(regs.col[k], gc);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) xv[k][i] = XL ? s_x[(unsigned) gc[i]] : p.x[(unsigned) gc[i]];
-            continue;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (BAND) {
-                xv[k][i] = (V) 0;
-                if ((unsigned) (regs.col[k].get(i) - p.band_lo) < (unsigned) p.band_len) { xv[k][i] = p.x[(unsigned) regs.col[k].get(i)]; in_band |= 1u << (4 * k + i); }
-            } else xv[k][i] = XL ? s_x[(unsigned) regs.col[k].get(i)] : p.x[(unsigned) regs.col[k].get(i)];
-        }
-        if constexpr (LAZY) {
-            zero4(bval[k]);
-            if ((in_band >> (4 * k)) & 0xfu) {
-                // the address issue_nonzero_loads used for this chunk's columns (a chunk past the tile re-reads the tile's first)
-                const int a0 = c0.y & ~3, last_full = (p.nnz & ~3) - 4;
-                int e0 = a0 + 4 * (tid + k * BLOCK);
-                e0 = (e0 < c1.y && e0 <= last_full) ? e0 : (a0 < last_full ? a0 : last_full);
-                bval[k] = ld_stream4<NT>(p.values + e0);
-            }
-        }
-    }
-    after_gather();
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int q = tid + k * BLOCK;
-        if (q < ro_chunks) {
-            int v[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = ro[k].get(j) - c0.y;
-            st_lds4(&s_end_raw[4 * q], v);
-            if (FL && !lean) {
-                // row starts inside the tile (rows before the tile give v <= 0, rows after it
-                // v >= tile_nnz; v == 0 is the tile's first nonzero, flagged anyway)
-                const int tile_nnz = c1.y - c0.y, pshift = c0.y - (c0.y & ~3);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if ((unsigned) v[j] < (unsigned) tile_nnz) atomicOr(&s_flag[(pshift + v[j]) >> 5], 1u << ((pshift + v[j]) & 31));
-            }
-        }
-    }
-    if (FL && !lean && tid == 0) atomicOr(&s_flag[0], 1u << (c0.y - (c0.y & ~3)));
-    Vec4<MV> own_val[LAZY || WIRE ? 1 : CPT];
-    if constexpr (!LAZY && !WIRE) {
-#pragma unroll
-        for (int k = 0; k < CPT; ++k) own_val[k] = vals_linewise<V, NT, LAZY, MV>() ? linewise_own(regs.val[k]) : regs.val[k];
-    }
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int chunk = tid + k * BLOCK;
-        if constexpr (WIRE) {
-            const WirePos wp = wire_pos(chunk, tid);
-            V pa[2], pb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) { pa[i] = regs.val[k].get(i) * xv[k][i]; pb[i] = regs.val[k].get(2 + i) * xv[k][2 + i]; }
-            st_unit(&s_prod_raw[2 * prod_unit<V, CPT>(2 * wp.qa + (wp.off >> 1), lean)], pa);
-            st_unit(&s_prod_raw[2 * prod_unit<V, CPT>(2 * wp.qb + (wp.off >> 1), lean)], pb);
-            continue;
-        }
-        V prod[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (LAZY) prod[i] = ((in_band >> (4 * k + i)) & 1u) ? bval[k].get(i) * xv[k][i] : (V) 0;
-            else if constexpr (BAND) prod[i] = ((in_band >> (4 * k + i)) & 1u) ? own_val[k].get(i) * xv[k][i] : (V) 0;
-            else prod[i] = widen<V>(own_val[k].get(i)) * xv[k][i];
-        }
-        if (FL) st_prod_chunk<CPT>(s_prod_raw, chunk, prod, lean);
-        else st_lds4(&s_prod_raw[swz_prod(4 * chunk)], prod);
-    }
-    __syncthreads();
-}
-
-// true when every vector load of the interior path stays inside full chunks of the arrays
-template <int IPT>
-__device__ __forceinline__ bool tile_is_interior(const Coord c0, const Coord c1, int tile, int num_tiles,
-                                                 int last_full_nz, int last_full_ro)
-{
-    const int first = c0.x + 1;
-    const int i0 = first & ~3;
-    const int ro_chunks = ((c1.x - c0.x) + (first - i0) + IPT + 3) / 4;
-    return tile != num_tiles - 1 && c1.y <= last_full_nz + 4 && i0 + 4 * ro_chunks <= last_full_ro + 4;
-}
-
-template <typename V, int BLOCK, int IPT, bool NT, bool FL, bool BAND = false, typename AG = NoAfterGather, typename MV = V>
-__device__ __forceinline__ void stage_tile(const Params<V, MV> &p, const Coord c0, const Coord c1, int tile, int num_tiles,
-                                           const TileRegs<V, BLOCK, IPT, MV> &regs, typename EndType<FL>::type *s_end_raw,
-                                           V *s_prod_raw, int last_full_nz, int last_full_ro, unsigned *s_flag, const V *s_x = nullptr, int tid_in = -1,
-                                           bool lean = false, AG after_gather = AG())
-{
-    const bool interior = tile_is_interior<IPT>(c0, c1, tile, num_tiles, last_full_nz, last_full_ro);      // block-uniform
-    if constexpr (BAND) {              // (a banded pass is for an x beyond L2: never the LDS copy)
-        if (interior) stage_tile_interior<V, BLOCK, IPT, NT, FL, false, true>(p, c0, c1, regs, s_end_raw, s_prod_raw, s_flag, nullptr, tid_in);
-        else stage_tile_careful<V, BLOCK, IPT, NT, FL, false, true>(p, c0, c1, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, nullptr, tid_in);
-    } else if (MSPMV_LIKELY((layout_hints<V, IPT>()), s_x == nullptr)) {
-        // (the likelihoods order the code of the SMALL tile shapes: x in memory, interior tile, usable hints, lean reduction first and in
-        //  one piece -- a block that runs alone, i.e. a small problem, waits for every stretch of instructions it jumps to:
-        //  instruction-cache misses per 28-tile launch 169 -> 87, wave-cycles -21 %, profiles/r04_small_call_counters.txt; a full
-        //  device has them all in its caches, and the large fp32 shape sits at its register limit: the hints cost it spills)
-        if (MSPMV_LIKELY((layout_hints<V, IPT>()), interior)) stage_tile_interior<V, BLOCK, IPT, NT, FL, false, false, AG>(p, c0, c1, regs, s_end_raw, s_prod_raw, s_flag, nullptr, -1, lean, after_gather);
-        else stage_tile_careful<V, BLOCK, IPT, NT, FL, false, false, AG>(p, c0, c1, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, nullptr, -1, lean, after_gather);
-    } else {                                  // block-uniform: x lives in LDS (tiny x only)
-        if (MSPMV_LIKELY((layout_hints<V, IPT>()), interior)) stage_tile_interior<V, BLOCK, IPT, NT, FL, true, false, AG>(p, c0, c1, regs, s_end_raw, s_prod_raw, s_flag, s_x, -1, lean, after_gather);
-        else stage_tile_careful<V, BLOCK, IPT, NT, FL, true, false, AG>(p, c0, c1, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, s_x, -1, lean, after_gather);
-    }
-}
-
-// x -> LDS (dynamic shared memory, p.x_lds entries) at block start; nullptr when the call does not use it.
-// The copy is visible after the block's first barrier.
-template <typename V, typename MV = V>
-__device__ __forceinline__ const V *stage_x_in_lds(const Params<V, MV> &p, unsigned char *s_dyn, int block)
-{
-    if (p.x_lds <= 0) return nullptr;
-    V *s_x = reinterpret_cast<V *>(s_dyn);
-    for (int i = threadIdx.x; i < p.x_lds; i += block) s_x[i] = p.x[i];
-    return s_x;
-}
-
-// The same copy in two steps (tile_kernel_snap, scalar-hint shapes): the loads are REQUESTED at the very head of the block --
-// before the hints are waited for, before the tile's streams -- and WRITTEN to LDS after the streams have been requested
-// (vector loads return in order: waiting for the oldest does not wait for the streams).  In one step the block sat through
-// hint latency + x latency with nothing else in flight: 0.5 us of a 5.7 us block life on the reference's --dense inputs.
-template <typename V, int BLOCK> struct XRegs { static constexpr int N = X_LDS_MAX_BYTES / (int) sizeof(V) / BLOCK; V v[N]; };
-template <typename V, int BLOCK, typename MV = V>
-__device__ __forceinline__ void request_x_for_lds(const Params<V, MV> &p, XRegs<V, BLOCK> &xr)
-{
-    static_assert(XRegs<V, BLOCK>::N >= 1, "x_lds entries per thread");
-#pragma unroll
-    for (int j = 0; j < XRegs<V, BLOCK>::N; ++j) {
-        const int i = (int) threadIdx.x + j * BLOCK;
-        xr.v[j] = i < p.x_lds ? p.x[i] : (V) 0;
-    }
-}
-template <typename V, int BLOCK, typename MV = V>
-__device__ __forceinline__ void commit_x_to_lds(const Params<V, MV> &p, const XRegs<V, BLOCK> &xr, unsigned char *s_dyn)
-{
-    V *s_x = reinterpret_cast<V *>(s_dyn);
-#pragma unroll
-    for (int j = 0; j < XRegs<V, BLOCK>::N; ++j) {
-        const int i = (int) threadIdx.x + j * BLOCK;
-        if (i < p.x_lds) s_x[i] = xr.v[j];
-    }
-}
-
-// Block -> tile mapping of the one-tile-per-block launches.  Blocks are dealt round-robin to the 8
-// XCDs (block b runs on XCD b % 8: observed; only speed depends on it).  Inside every group of 8*G
-// blocks, XCD k takes G CONSECUTIVE tiles: neighbouring tiles gather neighbouring x (which then stays in
-// that XCD's private L2) and each XCD reads longer contiguous pieces of the CSR arrays, while the XCDs
-// still advance through the matrix together.  Bijective for any num_tiles; log2 G = 0 turns it off.
-constexpr int TILE_MAP_CONTIGUOUS = 30;       // chunk_log2 value selecting one contiguous tile range per XCD
-__device__ __forceinline__ int xcd_chunked_tile(int b, int num_tiles, int chunk_log2)
-{
-    if (chunk_log2 == TILE_MAP_CONTIGUOUS) {
-        // XCD k takes tiles [k*T/8, (k+1)*T/8): what the band-major prepared plan wants (each XCD's L2
-        // then only ever sees the x slice of the band(s) its range covers); bijective for any T
-        const int q = num_tiles / 8, r = num_tiles % 8;
-        const int xcd = b & 7, idx = b >> 3;
-        return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
-    if (chunk_log2 > 0) {
-        // groups of span = 8 * 2^chunk_log2 blocks; shifts, not divisions (the compiler does not see that span is a power of
-        // two, and this sits at the very head of every block, before its first load can be requested); b, num_tiles >= 0
-        const int sh = chunk_log2 + 3;
-        if (b < ((num_tiles >> sh) << sh)) {
-            const int q = b >> sh, r = b & ((1 << sh) - 1);
-            return (((q << 3) | (r & 7)) << chunk_log2) + (r >> 3);
-        }
-    }
-    return b;
-}
-
-// the same map without a branch (the head of tile_kernel_snap: scalar selects, nothing between the wave's start and its hint request)
-__device__ __forceinline__ int xcd_chunked_tile_flat(int b, int num_tiles, int chunk_log2)
-{
-    const int q8 = num_tiles >> 3, r8 = num_tiles & 7, xcd = b & 7;
-    const int contiguous = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (b >> 3);
-    const int sh = (chunk_log2 & 15) + 3, cl = chunk_log2 & 15;                     // (& 15: the shifts stay defined when chunk_log2 is the contiguous code)
-    const int q = b >> sh, r = b & ((1 << sh) - 1);
-    const int chunked = b < ((num_tiles >> sh) << sh) ? (((q << 3) | (r & 7)) << cl) + (r >> 3) : b;
-    return chunk_log2 == TILE_MAP_CONTIGUOUS ? contiguous : chunk_log2 > 0 ? chunked : b;
-}
-
-// The compact launches (small problems: up to 2304 tiles): ONE CONTIGUOUS TILE RANGE PER XCD (map != 0), the same range in every call.
-// Blocks are dealt round-robin to the XCDs (block b -> XCD b % 8), so with tile = block index neighbouring tiles sit on eight different
-// XCDs and each fetches the x window of its rows for itself (a 5-point grid of 500^2: 10.9 KB of x beside the 17 KB of the tile's own
-// streams); with one range per XCD the window is fetched once per XCD, the lines that straddle tile boundaries once instead of twice
-// -- and a matrix of up to ~4 MB per XCD appears to be still in that XCD's L2 at the next call of a solver's loop (where the advantage
-// ends: 2300-2800 tiles, 4-6 MB per XCD; mspmv_api.hip: compact_max_tiles).  Measured (tools/ab_driver, interleaved with the block-index map, fp64 / fp32 5-point grids):
-// 697 tiles 4.35 -> 4.13 / 3.29 -> 3.27 us per call, 1003 tiles 5.31 -> 4.69 / 3.75 -> 3.53, 1366 tiles 7.05 -> 6.09 / 4.64 -> 4.07.
-// Forward progress is not a matter of order here either: a tile that needs another workgroup's record (a long row ending in it) polls a
-// bounded number of times and then computes the sum itself; inside a range a lower-numbered tile sits on an earlier block, only the
-// first tiles of a range (and group leaders at a range's edge) look at blocks dispatched after them.
-__device__ __forceinline__ int compact_tile(int b, int num_tiles, int map)
-{
-    const int q8 = num_tiles >> 3, r8 = num_tiles & 7, xcd = b & 7;
-    const int contiguous = xcd * q8 + (xcd < r8 ? xcd : r8) + (b >> 3);
-    return map ? contiguous : b;                  // (scalar arithmetic and a select: nothing between the wave's start and its hint request)
-}
-
-// Clock-scheduled column bands (mspmv_tdm.hpp): the one-pass form of the same organisation.  band_shift == 0: the passes.
-struct TdmArgs {
-    int band_shift;        // band = column >> band_shift
-    int bands;             // ceil(cols / 2^band_shift) <= TDM_MAX_BANDS
-    float inv_slot;        // 1 / (ticks of the 100 MHz clock a band stays on air)
-    int lookahead;         // bands after the one on air that may be taken too
-};
-template <typename V, int BLOCK, int IPT, bool NT>
-__device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c0, const Coord c1, const TileRegs<V, BLOCK, IPT> &regs,
-                                               end16_t *s_end_raw, V *s_prod_raw, int last_full_nz, int last_full_ro, unsigned *s_flag,
-                                               int *s_start, int *s_wave_sum, const TdmArgs &ta, int tid);
-constexpr int TDM_MAX_BANDS = 32;
-
-// What the tile kernel needs to know about them (BAND variants of tile_kernel_vec; verdict == nullptr otherwise)
+// What the tile kernel needs to know about the column bands (the Bands and Clocked variants of tile_kernel_vec; verdict == nullptr otherwise)
 struct BandArgs {
     const int *verdict;        // BAND_WINDOWS verdicts of band_detect_block
     int *counters;             // 8 claim counters, BAND_COUNTER_STRIDE ints apart, zeroed by band_detect_block
@@ -2121,11 +134,12 @@ __device__ __forceinline__ void run_band_passes(Params<V> p, const Coord *__rest
             const Coord c0 = coords[tile];
             const Coord c1 = coords[tile + 1];
             TileRegs<V, BLOCK, IPT> regs;
-            issue_nonzero_loads<V, BLOCK, IPT, NT, !band_lazy_values<V, true>()>(p, c0, c1, regs, t);     // (fp64: columns now, values by band in the staging)
-            stage_tile<V, BLOCK, IPT, NT, true, true>(p, c0, c1, tile, num_tiles, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, nullptr, t);
+            constexpr bool FL = true, BAND = true, AXPBY = true;      // (16-bit row ends and flags; this band's columns only; every pass with alpha and beta)
+            issue_nonzero_loads<V, BLOCK, IPT, NT, !band_lazy_values<V, BAND>()>(p, c0, c1, regs, t);     // (fp64: columns now, values by band in the staging)
+            stage_tile<V, BLOCK, IPT, NT, FL, BAND>(p, c0, c1, tile, num_tiles, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, nullptr, t);
             const int pshift = c0.y - (c0.y & ~3);
             const int eshift = (c0.x + 1) - ((c0.x + 1) & ~3);
-            consume_tile_flags<V, BLOCK, IPT, true>(p, c0, c1.x - c0.x, c1.y - c0.y, s_end_raw + eshift, s_prod_raw, s_flag,
+            consume_tile_flags<V, BLOCK, IPT, AXPBY>(p, c0, c1.x - c0.x, c1.y - c0.y, s_end_raw + eshift, s_prod_raw, s_flag,
                                                     s_wave_key, s_wave_val, carries + tile, pshift, nullptr, nullptr, 0, false, 0, t);
             if (tid == 0) {
                 s_next = following;
@@ -2141,11 +155,13 @@ __device__ __forceinline__ void run_band_passes(Params<V> p, const Coord *__rest
 __device__ unsigned long long *g_mspmv_trace = nullptr;
 #endif
 
-template <typename V, int BLOCK, int IPT, bool AXPBY, bool XCD_REMAP, bool NT, int ABLATE = 0, bool PERSIST = false, bool BAND = false, bool TDM = false, typename MV = V>
-__global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !PERSIST, ABLATE == 7>())) void tile_kernel_vec(Params<V, MV> p, const Coord *__restrict__ coords,
+template <typename V, int BLOCK, int IPT, typename BODY, typename OUT, typename STREAMS, typename MV = V>
+__global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !BODY::PERSIST, BODY::ABLATE == 7>())) void tile_kernel_vec(Params<V, MV> p, const Coord *__restrict__ coords,
                                                                 Carry<V> *__restrict__ carries, int num_tiles, int xcd_chunk_log2,
                                                                 BandArgs ba)
 {
+    constexpr bool AXPBY = OUT::AXPBY, NT = STREAMS::NT, BAND = BODY::BAND, TDM = BODY::TDM, PERSIST = BODY::PERSIST, XCD_REMAP = BODY::XCD_REMAP;
+    constexpr int ABLATE = BODY::ABLATE;
     constexpr int NW = BLOCK / WAVE;
     constexpr int CPT = IPT / 4 + 1;
     constexpr int SLOTS = CPT * BLOCK * 4;         // >= TILE + 8
@@ -2212,7 +228,8 @@ __global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !PERSIST
                 // (values by plain 16-byte loads, also where the ordinary body fetches them line by line: the two bodies then share no
                 //  loads, the ordinary one compiles as it does in the kernel of the passes, and this one needs no lane swaps)
                 asm volatile("" : "+s"(p.nnz));       // (nothing of this body is merged with the ordinary one's)
-                issue_nonzero_loads<V, BLOCK, IPT, NT, true, false>(p, c0, c1, tregs);
+                constexpr bool VALS = true, LINEWISE_OK = false;
+                issue_nonzero_loads<V, BLOCK, IPT, NT, VALS, LINEWISE_OK>(p, c0, c1, tregs);
                 stage_tile_tdm<V, BLOCK, IPT, NT>(p, c0, c1, tregs, s_end_raw, s_prod_raw, (p.nnz & ~3) - 4, ((p.rows + 1) & ~3) - 4, s_flag,
                                                   s_tdm_start, s_wave_key, ba.tdm, (int) threadIdx.x);
                 consume_tile_flags<V, BLOCK, IPT, AXPBY>(p, c0, c1.x - c0.x, c1.y - c0.y, s_end_raw + ((c0.x + 1) - ((c0.x + 1) & ~3)), s_prod_raw, s_flag,
@@ -2818,11 +835,12 @@ longer_rows:
     goto store_row;
 }
 
-template <typename V, int BLOCK, int IPT, bool AXPBY, bool NT, bool COMPACT = false, typename MV = V>
-__global__ __launch_bounds__(BLOCK, (COMPACT ? 4 : tile_waves_per_simd<V, BLOCK, IPT, true>())) void tile_kernel_snap(Coord *__restrict__ coords, int *__restrict__ rstart,
+template <typename V, int BLOCK, int IPT, typename BODY, typename OUT, typename STREAMS, typename MV = V>
+__global__ __launch_bounds__(BLOCK, (BODY::COMPACT ? 4 : tile_waves_per_simd<V, BLOCK, IPT, true>())) void tile_kernel_snap(Coord *__restrict__ coords, int *__restrict__ rstart,
                                                            int num_tiles, int xcd_chunk_log2,
                                                            Params<V, MV> p, Carry<V> *__restrict__ carries, LookBack lb, int lean_avg)
 {
+    constexpr bool AXPBY = OUT::AXPBY, NT = STREAMS::NT, COMPACT = BODY::COMPACT;
     constexpr int TILE = BLOCK * IPT;
     constexpr int NW = BLOCK / WAVE;
     constexpr int CPT = IPT / 4 + 1;
@@ -2962,7 +980,8 @@ __global__ __launch_bounds__(BLOCK, (COMPACT ? 4 : tile_waves_per_simd<V, BLOCK,
             const bool ok1 = (x1 > 0 ? before1 == rs1 : rs1 == 0) & (x1 < p.rows ? y1 <= at1 : d1 == total);
             verdict = single | (ok0 & ok1);
         };
-        stage_tile<V, BLOCK, IPT, NT, true, false, decltype(check_hints)>(p, c0, c1, tile, num_tiles, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, s_x, -1, lean, check_hints);
+        constexpr bool FL = true, BAND = false;         // (16-bit row ends and row-start bits; every column)
+        stage_tile<V, BLOCK, IPT, NT, FL, BAND, decltype(check_hints)>(p, c0, c1, tile, num_tiles, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, s_x, -1, lean, check_hints);
         MSPMV_SNAP_TR(3);
         good = verdict;
     }
@@ -2988,7 +1007,8 @@ __global__ __launch_bounds__(BLOCK, (COMPACT ? 4 : tile_waves_per_simd<V, BLOCK,
         lean = snap0 && snap1 && (unsigned) (c1.y - c0.y) <= (unsigned) lean_avg * (unsigned) (c1.x - c0.x);
         TileRegs<V, BLOCK, IPT, MV> regs;
         issue_nonzero_loads<V, BLOCK, IPT, NT>(p, c0, c1, regs);
-        stage_tile<V, BLOCK, IPT, NT, true>(p, c0, c1, tile, num_tiles, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, s_x, -1, lean);
+        constexpr bool FL = true;
+        stage_tile<V, BLOCK, IPT, NT, FL>(p, c0, c1, tile, num_tiles, regs, s_end_raw, s_prod_raw, last_full_nz, last_full_ro, s_flag, s_x, -1, lean);
     }
     store_hints(!good);
     // the tiles that hold published pieces of this tile's first row (only when the row ends here and began > HEAD_MAX
@@ -3091,5 +1111,3 @@ __global__ void mg_apply_kernel(V *__restrict__ y_local, const V *__restrict__ c
 }
 
 }  // namespace mspmv
-
-#include "mspmv_tdm.hpp"

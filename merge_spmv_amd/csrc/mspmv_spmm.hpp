@@ -43,7 +43,7 @@ struct Pack {
 };
 
 // cross-lane moves of a pack: element by element (found by argument-dependent lookup from the
-// scan templates of mspmv_kernels.hpp)
+// scan templates of mspmv_wave.hpp)
 template <int CTRL, int ROW_MASK, typename T, int K>
 __device__ __forceinline__ Pack<T, K> dpp_move(Pack<T, K> old, Pack<T, K> src)
 {
@@ -156,12 +156,13 @@ __device__ __forceinline__ void lds_store_pack(int4v *s_units, int e, const P &v
 }
 
 // One tile per block.  BLOCK x IPT path items; the staging is the predicated ("careful") form of
-// mspmv_kernels.hpp for every tile (nothing outside the tile or the arrays is used).
-template <typename T, int K, int BLOCK, int IPT, bool AXPBY, bool NT>
+// mspmv_stage.hpp for every tile (nothing outside the tile or the arrays is used).
+template <typename T, int K, int BLOCK, int IPT, typename OUT, typename STREAMS>
 __global__ __launch_bounds__(BLOCK) void spmm_tile_kernel(MMParams<T> p, const Coord *__restrict__ coords,
                                                           CarryMM<T, K> *__restrict__ carries, int num_tiles, int groups,
                                                           int xcd_chunk_log2)
 {
+    constexpr bool AXPBY = OUT::AXPBY, NT = STREAMS::NT;
     typedef Pack<T, K> P;
     static_assert(sizeof(P) == 4 || sizeof(P) == 8 || sizeof(P) % 16 == 0, "a pack is 4 or 8 bytes or whole 16-byte units");
     constexpr int NW = BLOCK / WAVE;
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(BLOCK) void spmm_tile_kernel(MMParams<T> p, const C
     const end16_t *s_end = s_end_raw + eshift;
     const int base = tid * NPT;
     const bool nz_tail = c1.y > last_full_nz + 4;
-    // (fp64 values read non-temporally arrive laid out line by line over the wave, mspmv_kernels.hpp: ld_stream4_linewise)
+    // (fp64 values read non-temporally arrive laid out line by line over the wave, mspmv_wave.hpp: ld_stream4_linewise)
     if constexpr (vals_linewise<T, NT, false>()) {
 #pragma unroll
         for (int k = 0; k < CPT; ++k) regs.val[k] = linewise_own(regs.val[k]);
@@ -349,11 +350,12 @@ __global__ __launch_bounds__(BLOCK) void spmm_tile_kernel(MMParams<T> p, const C
 // of NS = BLOCK / LS partial rows, added in slot order (deterministic).  The tile's open row leaves as the same CarryMM the pack
 // kernel writes: one fix-up serves both.  Tiles are merge-path tiles (rows + nonzeros bounded), the nonzero shares inside a tile
 // are equal whatever the row lengths.
-template <typename T, int SW, int VEC, int BLOCK, int IPT, bool AXPBY, bool NT>
+template <typename T, int SW, int VEC, int BLOCK, int IPT, typename OUT, typename STREAMS>
 __global__ __launch_bounds__(BLOCK) void spmm_lane_kernel(MMParams<T> p, const Coord *__restrict__ coords,
                                                           CarryMM<T, SW> *__restrict__ carries, int num_tiles, int groups,
                                                           int xcd_chunk_log2)
 {
+    constexpr bool AXPBY = OUT::AXPBY, NT = STREAMS::NT;
     static_assert(SW == 8 || SW == 16, "group width");
     static_assert(VEC * sizeof(T) <= 16 && SW % VEC == 0, "right-hand sides per lane: at most 16 bytes");
     constexpr int LS = SW / VEC;                        // lanes per slot

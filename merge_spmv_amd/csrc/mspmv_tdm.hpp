@@ -16,15 +16,24 @@
 // The clock is a cache-affinity schedule, not a protocol: a block may gather any band at any time and the result is the
 // same -- bit for bit the one-sweep tile_kernel_vec's, since products and reduction are the same (unlike the passes,
 // which add band partials).  Nothing waits for another workgroup; a wave with nothing on air sleeps and looks again.
-// Carrier: tile_kernel_vec<..., BAND, TDM> (mspmv_kernels.hpp) -- one tile per block, the verdict of the 64 sampled windows chooses
+// Carrier: tile_kernel_vec<..., Clocked, ...> (mspmv_kernels.hpp) -- one tile per block, the verdict of the 64 sampled windows chooses
 // between this staging and the ordinary one; the slot length comes from the dispatcher (mspmv_api.hip).
 // Measured: C2 fp32 0.64 ms against the passes' 0.83, fp64 0.98-1.00 against 1.30 (profiles/r06_c2_f32, r06_c2_f64); the prototype
 // (tools/tdm_spmv.hip), a persistent kernel of its own and the staging inside the one-launch kernel, all measured and dropped, are
 // in docs/history/round6.md.
 #pragma once
-#include "mspmv_kernels.hpp"
+#include "mspmv_stage.hpp"
 
 namespace mspmv {
+
+// What the dispatcher hands the kernel about them (inside BandArgs, mspmv_kernels.hpp).  band_shift == 0: the passes.
+struct TdmArgs {
+    int band_shift;        // band = column >> band_shift
+    int bands;             // ceil(cols / 2^band_shift) <= TDM_MAX_BANDS
+    float inv_slot;        // 1 / (ticks of the 100 MHz clock a band stays on air)
+    int lookahead;         // bands after the one on air that may be taken too
+};
+constexpr int TDM_MAX_BANDS = 32;
 
 constexpr int TDM_COPIES = 8;              // counters per (band, wave): lanes 8 apart share one
 constexpr int TDM_SLOT_SHIFT = 20;         // sorted word = slot in the tile's raw product array (12 bits) << 20 | column inside its band

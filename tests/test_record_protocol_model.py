@@ -1,4 +1,4 @@
-"""Exhaustive check of the tagged-record protocol of tile_kernel_snap (csrc/mspmv_kernels.hpp: rec_announce / rec_store / rec_take) on a
+"""Exhaustive check of the tagged-record protocol of tile_kernel_snap (csrc/mspmv_types.hpp: rec_announce / rec_store / rec_take) on a
 model: every interleaving of the atomic operations of one publisher and one consumer on a two-word slot -- and of the two-level chain
 publisher -> group leader -> consumer -- under RELAXED ordering (operations of one thread on DIFFERENT words may take effect in either
 order unless one depends on the other's value; operations on the same word keep program order; the exchanges are atomic), for every
@@ -24,7 +24,7 @@ W0, W1 = 0, 1
 
 
 def _source_functions():
-    text = open(os.path.join(ROOT, "merge_spmv_amd", "csrc", "mspmv_kernels.hpp")).read()
+    text = open(os.path.join(ROOT, "merge_spmv_amd", "csrc", "mspmv_types.hpp")).read()
     out = []
     for name in ("rec_announce", "rec_store", "rec_take"):
         m = re.search(r"__device__ __forceinline__ [a-z ]+ " + name + r"\(.*?\n}\n", text, flags=re.S)

@@ -1,7 +1,7 @@
 // tools/band_ceiling.hip -- what ANY column-band scheme over the unchanged CSR arrays can reach on C2 (development aid,
 // not part of the product).  The kernels below do the memory work of a banded CsrMV tile -- 16-byte streams of (col, val),
 // the gather of x for the nonzeros of one column band -- and nothing else (no LDS staging, no row reduction, no y), so their
-// times are ceilings for the product's tile_kernel_vec<.., BAND> under each organisation:
+// times are ceilings for the product's tile_kernel_vec<.., Bands, ..> under each organisation:
 //   passes   chip-wide phases, one band per phase (what run_band_passes does), with / without a register prefetch of the
 //            next tile and with / without fetching the values only for chunks that hold a nonzero of the band
 //   xcd      every XCD (pair) owns one band for the whole call and streams the whole matrix itself: no phases

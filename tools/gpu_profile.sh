@@ -59,7 +59,7 @@ dtype = os.environ.get("PROFILE_DTYPE") or ("f64" if "f64" in extra else "f32")
 workload = os.environ.get("PROFILE_LABEL") or ("dense32" if "dense32" in extra else "c2" if dtype == "f64" else "c2_f32")      # (bench.py's replay labels)
 d = {"workload": workload, "dtype": dtype, "command": os.environ.get("PROFILE_CMD", "bench.py " + extra),
      "collected": "separate rocprofv3 --kernel-trace --pmc passes (tools/gpu_profile.sh), averaged per dispatch of the tile kernel",
-     "kernel": "tile kernel of the call (tile_kernel_vec<..,BAND> for column-band candidates, tile_kernel_snap otherwise)",
+     "kernel": "tile kernel of the call (tile_kernel_vec<.., Clocked, ..> for column-band candidates, tile_kernel_snap otherwise)",
      "FETCH_SIZE_KB_per_launch": fetch_kb, "WRITE_SIZE_KB_per_launch": write_kb,
      "correction": "MI355X_MICROARCH.md HBM section: on gfx950 FETCH_SIZE tallies 128-byte requests at 64 bytes -> doubled; KB -> bytes x1024",
      "tile_kernel_hbm_bytes_per_launch": None if fetch_kb is None or write_kb is None else int((2 * fetch_kb + write_kb) * 1024),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/record_soak.py [seconds] [seed] -- a soak of the tagged-record protocol of the one-launch kernel (mspmv_kernels.hpp: "EVERY
+"""tools/record_soak.py [seconds] [seed] -- a soak of the tagged-record protocol of the one-launch kernel (mspmv_types.hpp: "EVERY
 RECORD SLOT IS CLEAN": announce / record / take, cancel by atomic exchange) under the conditions it exists for: random matrices of
 long rows (rows over a few to hundreds of tiles, back to back, between runs of short rows), random poll budgets (the default, one
 look, a handful, never), streams restricted to a random fraction of the CUs (the residency the dispatcher assumes is then several
