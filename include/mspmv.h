@@ -822,6 +822,106 @@ int mspmv_csric0_f64(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t 
                      double *d_values_l, const int32_t *d_row_offsets, const int32_t *d_column_indices, int32_t mirror,
                      int32_t *d_pivot, mspmv_stream_t stream, int debug_sync);
 
+/* ---- extension: MULTICOLOUR ORDERING, part 1: a deterministic graph colouring on the device (csrc/mspmv_color.hip; what
+ * rocsparse_csrcolor is in rocSPARSE).  The level-scheduled family above (mspmv_csrsv_*, mspmv_csrsm_*, mspmv_csrilu0_*,
+ * mspmv_csric0_*) pays one launch per level; after a symmetric permutation by colour a row depends only on rows of smaller colours, so
+ * the LOWER plan of P A P^T has at most as many levels as there are colours, and none of that family's code changes.
+ * GRAPH: the vertices are the rows of a rows x rows CSR pattern; u and v are neighbours when u != v and A[u,v] OR A[v,u] is stored.  The
+ * pattern need not be structurally symmetric (the analysis builds A^T's pattern with mspmv_csr_transpose_*).  Diagonal entries are
+ * ignored, repeated columns are harmless, rows need not be sorted, empty rows may sit anywhere.
+ * DEFINITION, the pattern and the priorities alone:
+ *     key(v)   = (uint64) prio(v) << 32 | v
+ *     prio(v)  = d_priority[v] when priorities are given, else fmix32(v), the 32-bit finaliser
+ *                h = v;  h ^= h >> 16;  h *= 0x85ebca6b;  h ^= h >> 13;  h *= 0xc2b2ae35;  h ^= h >> 16
+ *     color[v] = the smallest non-negative integer that is not the colour of any neighbour u with key(u) > key(v)
+ * that is, sequential greedy colouring in descending key order: a total function of its input, not of any schedule, round structure,
+ * alignment or kernel.  Equal priorities fall to the vertex index (the larger index first).  Derived from the colours:
+ *     order[]   = the vertices sorted stably by colour (ascending vertex inside a colour)
+ *     inverse[] : inverse[order[i]] = i
+ *     offsets[] : colours + 1 entries; colour c holds order[offsets[c] .. offsets[c + 1])
+ * info.edges is the number of stored off-diagonal entries, duplicates counted; info.max_color_rows the largest colour class.
+ * SCHEME: Jones-Plassmann in rounds.  A vertex is coloured once every neighbour of larger key holds a colour; its colour goes from -1
+ * to its final value in one 32-bit store.  A reader in another workgroup of the same launch sees -1 (and waits one more round) or
+ * the final value, so the result is the definition whatever the timing; nothing but the kernel boundary and, inside one workgroup,
+ * the barrier orders two rounds: no flags, no spinning, no workgroup that waits on another.  While more than 4096 vertices remain a
+ * round is one launch over the compacted list, after which the host reads the remaining count back; at or below 4096 ONE workgroup
+ * finishes all remaining rounds.  A vertex of 64 or more neighbour slots is scanned by its whole wave.  info.rounds is the number of
+ * those host steps (informational: it may depend on timing, the colours do not).
+ * THE HANDLE is opaque and OWNS ITS STORAGE, exactly as mspmv_csrsv_plan_t and for the same reason: the host must learn a
+ * pattern-dependent count.  mspmv_csr_color_create ALLOCATES (hipMalloc: scratch, freed before it returns; the four arrays, kept
+ * until mspmv_csr_color_destroy), is SYNCHRONOUS and reads a few bytes back per step.  debug_sync prints one line per launch.
+ * LIMITS, refused before anything is launched or allocated: rows, nnz >= 0; rows + nnz <= 2^31 - 65537; nnz > 0 with rows == 0; NULL
+ * pattern arrays with nnz > 0; a NULL `coloring`.  rows == 0 gives a valid handle with 0 colours (no device is touched; the getters
+ * return NULL).  nnz == 0 gives colour 0 everywhere (the pattern arrays may be NULL).  A NULL handle makes the getters return NULL
+ * and info and destroy return 1.  Column indices lie in [0, rows), not checked, as everywhere.
+ * USE: mspmv_csr_permute_* with row_perm = order and col_map = inverse gives P A P^T; b' = b[order] and x = x'[inverse] are
+ * mspmv_coo_to_csr_values_*(b, order, b', rows) and (x', inverse, x, rows).  THE PRICE is a weaker incomplete factor: IC(0)-
+ * preconditioned CG on a 5-point grid of 24 x 24 takes 48 iterations in multicolour order against 32 in natural order (88 without).
+ * Measured on MI355X (profiles/color_bench.txt; DESIGN.md 4 "Multicolour ordering"), colouring against rocsparse_csrcolor on the same
+ * pattern: a 5-point grid of 2000 x 2000 6.2 ms, 5 colours, 11 rounds against 1.3 ms and 16 colours; a 7-point grid of 128^3 5.2 ms, 7
+ * colours, 14 rounds against 1.4 ms and 22 colours; A + A^T + I of an R-MAT graph of scale 16 173 ms, 112 colours, 406 rounds against
+ * 321 ms and 526 colours: rocSPARSE is 4 - 5 times faster on the grids and uses 3 - 5 times the colours everywhere.  What the order
+ * buys, fp64, natural -> multicolour: on the 2000 x 2000 grid the LOWER solve 3999 levels, 29.4 ms -> 5 levels, 0.15 ms, the UPPER
+ * solve 25.1 -> 0.34 ms, mspmv_csric0 25.7 -> 0.68 ms, mspmv_csrilu0 26.7 -> 0.75 ms; on the 128^3 grid 382 -> 7 levels, the solves
+ * 2.55 / 2.42 -> 0.15 / 0.30 ms, the factorisations 3.15 / 3.17 -> 0.68 / 0.61 ms; on the R-MAT graph 427 -> 112 levels, the solves
+ * 91 / 117 -> 60 / 42 ms (one lane per row of thousands of entries either way; not factorised).  IC(0)-preconditioned CG on the
+ * 2000 x 2000 grid (the 5-point Laplacian + 0.01 I, to 1e-8 |b|): 74 iterations x 52.3 ms = 3872 ms in natural order, 114
+ * iterations x 0.69 ms = 78 ms in multicolour order: 1.5 times the iterations, 50 times sooner. ---- */
+typedef struct mspmv_csr_color mspmv_csr_color_t;
+typedef struct mspmv_csr_color_info {
+    int32_t rows, nnz;
+    int32_t colors;            /* number of colours (0 for rows == 0)                                 */
+    int32_t max_color_rows;    /* the largest colour class                                            */
+    int32_t rounds;            /* host steps of the colouring (informational)                         */
+    int64_t edges;             /* stored off-diagonal entries, duplicates counted                     */
+    uint64_t device_bytes;     /* what the handle holds on the device                                 */
+} mspmv_csr_color_info_t;
+int mspmv_csr_color_create(mspmv_csr_color_t **coloring, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                           int32_t rows, int32_t nnz, const uint32_t *d_priority /* rows entries, or NULL */,
+                           mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_color_info(const mspmv_csr_color_t *coloring, mspmv_csr_color_info_t *info);
+const int32_t *mspmv_csr_color_colors(const mspmv_csr_color_t *coloring);   /* device, rows entries       */
+const int32_t *mspmv_csr_color_order(const mspmv_csr_color_t *coloring);    /* device, rows entries       */
+const int32_t *mspmv_csr_color_inverse(const mspmv_csr_color_t *coloring);  /* device, rows entries       */
+const int32_t *mspmv_csr_color_offsets(const mspmv_csr_color_t *coloring);  /* device, colors + 1 entries */
+int mspmv_csr_color_destroy(mspmv_csr_color_t *coloring);
+
+/* ---- extension: MULTICOLOUR ORDERING, part 2: B = A[row_perm, :] with the columns renumbered, canonical (csrc/mspmv_permute.hip).
+ * DEFINITION: row i of B holds the entries of A's row row_perm[i]; each column c is replaced by col_map[c]; the entries of a row are
+ * sorted STABLY by the new column, so entries that map to one column keep their stored order.  B entry j is A entry permutation[j];
+ * values are moved, never recomputed.  Equivalently: bit for bit what mspmv_coo_to_csr_* gives on the triples (inverse_row(r),
+ * col_map[c], v) listed in A's stored order -- which is how it is computed: one lane per row inverts row_perm, the entries are expanded
+ * to (new row, new column) in equal tiles whatever the row lengths (one row of 2^20 entries is no single lane's loop), then the COO
+ * build's radix passes sort them.  With row_perm = order and col_map = inverse of a colouring this is P A P^T; a canonical A (sorted
+ * rows, no duplicates) stays canonical, which is what mspmv_csrilu0_* and mspmv_csric0_* require.
+ * row_perm is a permutation of [0, rows) and col_map maps into [0, cols): neither is checked, as indices are not checked elsewhere.
+ * d_row_perm == NULL and d_col_map == NULL mean the identity (both NULL: a stable sort of every row by column).
+ * The call allocates nothing, reads nothing back, launches the same kernels whatever the data and can be captured in a graph.  Inputs
+ * are not modified and must not alias the outputs.  d_values == NULL and d_values_b == NULL: structure (+ permutation) only.
+ * nnz == 0 gives all-zero offsets; rows == 0 or cols == 0 with nnz > 0 is refused; rows + nnz <= 2^31 - 65537.  Same two-phase temp
+ * storage, 16-byte alignment, stream, debug_sync and error conventions as mspmv_coo_to_csr_*; temp storage: that call's plus
+ * 4 x rows + 8 x nnz bytes.
+ * NEW VALUES on the same pattern and the vectors need no entry point of their own: mspmv_coo_to_csr_values_*(values, permutation, out,
+ * nnz) is out[j] = values[permutation[j]]; the same call with `order` gives b' = b[order], with `inverse` x = x'[inverse].
+ * COST next to mspmv_coo_to_csr_* on the same entries, measured on MI355X (tools/color_bench.py; profiles/color_bench.txt):
+ * the two extra launches add 5 - 14 %: P A P^T of a 5-point grid of 2000 x 2000 (20.0 M entries, fp64, 3 + 3 passes) 2.71 ms against
+ * 2.44 ms; of a 7-point grid of 128^3 (14.6 M entries) 1.84 against 1.75 ms; of A + A^T + I of an R-MAT graph of scale 16 (1.9 M
+ * entries) 0.24 against 0.21 ms. ---- */
+int mspmv_csr_permute_f32(void *d_temp, size_t *temp_bytes,
+                          const float *d_values /* or NULL */, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                          int32_t rows, int32_t cols, int32_t nnz,
+                          const int32_t *d_row_perm /* rows entries or NULL = identity */,
+                          const int32_t *d_col_map  /* cols entries or NULL = identity */,
+                          float *d_values_b, int32_t *d_row_offsets_b, int32_t *d_column_indices_b,
+                          int32_t *d_permutation /* nnz entries, may be NULL */, mspmv_stream_t stream, int debug_sync);
+int mspmv_csr_permute_f64(void *d_temp, size_t *temp_bytes,
+                          const double *d_values /* or NULL */, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                          int32_t rows, int32_t cols, int32_t nnz,
+                          const int32_t *d_row_perm /* rows entries or NULL = identity */,
+                          const int32_t *d_col_map  /* cols entries or NULL = identity */,
+                          double *d_values_b, int32_t *d_row_offsets_b, int32_t *d_column_indices_b,
+                          int32_t *d_permutation /* nnz entries, may be NULL */, mspmv_stream_t stream, int debug_sync);
+
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */
 typedef struct mspmv_launch_info {

@@ -19,6 +19,7 @@ from typing import Optional, Tuple
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
            "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv", "csrsm", "csrilu0", "Ilu0", "csric0", "Ic0",
+           "CsrColoring", "csr_color", "csr_permute", "multicolor_reorder",
            "plan_bench_record", "library_path", "load_library", "launch_info",
            "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles", "profile_begin", "profile_end", "MspmvError",
            "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
@@ -66,6 +67,11 @@ class _CsrSvInfo(ctypes.Structure):
                 ("levels", ctypes.c_int32), ("launches", ctypes.c_int32), ("narrow_rows", ctypes.c_int32),
                 ("max_level_rows", ctypes.c_int32), ("bad_diagonal_row", ctypes.c_int32), ("used_entries", ctypes.c_int64),
                 ("device_bytes", ctypes.c_uint64)]
+
+
+class _CsrColorInfo(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int32), ("nnz", ctypes.c_int32), ("colors", ctypes.c_int32), ("max_color_rows", ctypes.c_int32),
+                ("rounds", ctypes.c_int32), ("edges", ctypes.c_int64), ("device_bytes", ctypes.c_uint64)]
 
 
 class _CsrSmInfo(ctypes.Structure):
@@ -236,6 +242,18 @@ def load_library() -> ctypes.CDLL:
     for name in ("mspmv_csric0_f32", "mspmv_csric0_f64"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [vp, vp, sz_p, vp, vp, vp, vp, i32, vp, vp, ctypes.c_int]
+    lib.mspmv_csr_color_create.restype = ctypes.c_int
+    lib.mspmv_csr_color_create.argtypes = [ctypes.POINTER(vp), vp, vp, i32, i32, vp, vp, ctypes.c_int]
+    lib.mspmv_csr_color_info.restype = ctypes.c_int
+    lib.mspmv_csr_color_info.argtypes = [vp, ctypes.POINTER(_CsrColorInfo)]
+    for name in ("mspmv_csr_color_colors", "mspmv_csr_color_order", "mspmv_csr_color_inverse", "mspmv_csr_color_offsets"):
+        getattr(lib, name).restype = vp
+        getattr(lib, name).argtypes = [vp]
+    lib.mspmv_csr_color_destroy.restype = ctypes.c_int
+    lib.mspmv_csr_color_destroy.argtypes = [vp]
+    for name in ("mspmv_csr_permute_f32", "mspmv_csr_permute_f64"):
+        getattr(lib, name).restype = ctypes.c_int
+        getattr(lib, name).argtypes = [vp, sz_p, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int]
     lib.mspmv_csr_gemm_products.restype = ctypes.c_int
     lib.mspmv_csr_gemm_products.argtypes = [vp, sz_p, vp, vp, i32, i32, i32, vp, i32, vp, vp, ctypes.c_int]
     lib.mspmv_csrmv_hotcols_skew.restype = ctypes.c_int
@@ -1527,6 +1545,157 @@ class Ic0(_Factor0):
     @staticmethod
     def _call(plan, temp, values, l, row_offsets, column_indices, pivot, stream, debug_synchronous):
         _ic0_call(plan, temp, values, l, row_offsets, column_indices, True, pivot, stream, debug_synchronous)
+
+
+def _pattern_check(what, row_offsets, column_indices):
+    """the checks the C ABI cannot make for a CSR pattern; returns (device, rows, nnz)"""
+    import torch
+    for t, name in ((row_offsets, "row_offsets"), (column_indices, "column_indices")):
+        if not isinstance(t, torch.Tensor):
+            raise MspmvError(f"{what}: {name} must be a tensor")
+    if not (row_offsets.is_cuda and column_indices.is_cuda):
+        raise MspmvError(f"{what} needs CUDA (HIP) tensors: the kernels only run on the GPU")
+    if row_offsets.dtype != torch.int32 or column_indices.dtype != torch.int32:
+        raise MspmvError(f"{what}: row_offsets / column_indices must be int32")
+    if row_offsets.dim() != 1 or row_offsets.numel() < 1 or not row_offsets.is_contiguous() or column_indices.dim() != 1 \
+            or not column_indices.is_contiguous() or column_indices.device != row_offsets.device:
+        raise MspmvError(f"{what}: row_offsets (rows + 1 entries) and column_indices must be contiguous 1-D tensors on one device")
+    return row_offsets.device, row_offsets.numel() - 1, column_indices.numel()
+
+
+def _index_check(what, t, name, need, dev, dtypes=None):
+    import torch
+    dtypes = dtypes or (torch.int32,)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dtypes or t.device != dev or t.dim() != 1 \
+            or not t.is_contiguous() or t.numel() != need:
+        raise MspmvError(f"{what}: {name} must be a contiguous 1-D {' / '.join(str(d) for d in dtypes)} tensor of {need} entries on {dev}")
+
+
+class CsrColoring:
+    """The deterministic multicolouring of a square CSR pattern (mspmv_csr_color_*; include/mspmv.h states the definition): u and v are
+    neighbours when A[u,v] or A[v,u] is stored, and color[v] is the smallest colour that no neighbour of larger key holds, key(v) =
+    priorities[v] << 32 | v (priorities: rows entries, int32 or uint32, their 32 bits read as unsigned; None: a hash of the index).  The
+    constructor analyses the PATTERN (synchronous; the handle owns what it allocates).
+    .colors, .order (the vertices sorted stably by colour), .inverse (inverse[order[i]] = i), .offsets (num_colors + 1 entries): int32
+    tensors on the pattern's device (copies); .num_colors; .info: the handle's figures (colors, max_color_rows, rounds, edges, ...).
+    `permute_vector(v)` is v[order], `permute_vector(v, back=True)` v[inverse]; csr_permute(..., row_perm=.order, col_map=.inverse) is
+    P A P^T, whose LOWER CsrSv plan has at most num_colors levels."""
+
+    def __init__(self, row_offsets, column_indices, priorities=None, stream=None, debug_synchronous: bool = False):
+        import torch
+        self._handle = None
+        self.device, self.rows, self.nnz = _pattern_check("CsrColoring", row_offsets, column_indices)
+        if priorities is not None:
+            _index_check("CsrColoring", priorities, "priorities", self.rows, self.device,
+                         (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ()))
+        self._lib = load_library()
+        handle = ctypes.c_void_p(0)
+        with torch.cuda.device(self.device):
+            _check(self._lib.mspmv_csr_color_create(ctypes.byref(handle), _ptr(row_offsets), _ptr(column_indices), self.rows, self.nnz,
+                                                    _ptr(priorities), _stream_handle(stream), int(bool(debug_synchronous))),
+                   "mspmv_csr_color_create")
+        self._handle = handle
+        raw = _CsrColorInfo()
+        _check(self._lib.mspmv_csr_color_info(self._handle, ctypes.byref(raw)), "mspmv_csr_color_info")
+        self.info = {name: int(getattr(raw, name)) for name, _ in _CsrColorInfo._fields_}
+        self.num_colors = self.info["colors"]
+        self._kept = {}
+
+    def _array(self, name, count):
+        import torch
+        if name not in self._kept:
+            if self._handle is None:
+                raise MspmvError("CsrColoring: the handle is closed")
+            ptr = getattr(self._lib, "mspmv_csr_color_" + name)(self._handle)
+            if not ptr or count == 0:
+                self._kept[name] = torch.zeros(count, dtype=torch.int32, device=self.device)
+            else:
+                self._kept[name] = torch.as_tensor(_PlanArray(ptr, count), device=self.device).clone()
+        return self._kept[name]
+
+    colors = property(lambda self: self._array("colors", self.rows))
+    order = property(lambda self: self._array("order", self.rows))
+    inverse = property(lambda self: self._array("inverse", self.rows))
+    offsets = property(lambda self: self._array("offsets", self.num_colors + 1))
+
+    def permute_vector(self, v, back: bool = False, out=None, stream=None):
+        """v[order] (the vector in the multicolour numbering), or with back=True v[inverse] (back in the original numbering), through
+        mspmv_coo_to_csr_values_*.  Asynchronous on `stream`."""
+        import torch
+        if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype not in (torch.float32, torch.float64) or v.device != self.device \
+                or v.dim() != 1 or not v.is_contiguous() or v.numel() != self.rows:
+            raise MspmvError(f"CsrColoring.permute_vector: v must be a contiguous 1-D float32 / float64 tensor of {self.rows} entries on {self.device}")
+        if out is None:
+            out = torch.empty_like(v)
+        if not isinstance(out, torch.Tensor) or out.dtype != v.dtype or out.device != v.device or out.dim() != 1 or not out.is_contiguous() \
+                or out.numel() != self.rows or out.data_ptr() == v.data_ptr() and self.rows > 0:
+            raise MspmvError("CsrColoring.permute_vector: out must be another contiguous tensor of v's dtype, length and device")
+        index = self.inverse if back else self.order
+        fn = self._lib.mspmv_coo_to_csr_values_f32 if v.dtype == torch.float32 else self._lib.mspmv_coo_to_csr_values_f64
+        _check(fn(_ptr(v), _ptr(index), _ptr(out), self.rows, _stream_handle(stream), 0), "mspmv_coo_to_csr_values")
+        return out
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None:
+            handle, self._handle = self._handle, None
+            self._lib.mspmv_csr_color_destroy(handle)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def csr_color(row_offsets, column_indices, priorities=None):
+    """One-shot colouring: (colors, num_colors) of the pattern (CsrColoring keeps the order, its inverse and the offsets too)."""
+    coloring = CsrColoring(row_offsets, column_indices, priorities)
+    try:
+        return coloring.colors, coloring.num_colors
+    finally:
+        coloring.close()
+
+
+def csr_permute(values, row_offsets, column_indices, num_cols: int, row_perm=None, col_map=None, return_permutation: bool = False,
+                stream=None):
+    """B = A[row_perm, :] with every column c renamed col_map[c] and every row sorted stably by its new column (mspmv_csr_permute_*): a
+    generators.DeviceCsr (values=None: structure only, .values is None).  row_perm: a permutation of the rows, col_map: num_cols entries
+    into [0, num_cols) (None: the identity; neither is checked).  With return_permutation=True returns (csr, permutation): B entry j is
+    A entry permutation[j].  With a CsrColoring's (order, inverse) this is P A P^T.  Asynchronous on `stream`; nothing is read back."""
+    import torch
+    from .generators import DeviceCsr
+    dev, rows, nnz = _pattern_check("csr_permute", row_offsets, column_indices)
+    cols = int(num_cols)
+    if cols < 0:
+        raise MspmvError("csr_permute: negative num_cols")
+    if values is not None and (not isinstance(values, torch.Tensor) or values.dtype not in (torch.float32, torch.float64) or values.device != dev
+                               or values.dim() != 1 or not values.is_contiguous() or values.numel() != nnz):
+        raise MspmvError(f"csr_permute: values must be a contiguous 1-D float32 / float64 tensor of {nnz} entries on {dev}")
+    if row_perm is not None:
+        _index_check("csr_permute", row_perm, "row_perm", rows, dev)
+    if col_map is not None:
+        _index_check("csr_permute", col_map, "col_map", cols, dev)
+    dtype = torch.float32 if values is None else values.dtype
+    lib = load_library()
+    fn = lib.mspmv_csr_permute_f32 if dtype == torch.float32 else lib.mspmv_csr_permute_f64
+    row_offsets_b = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    cols_b = torch.empty(nnz, dtype=torch.int32, device=dev)
+    values_b = None if values is None else torch.empty(nnz, dtype=dtype, device=dev)
+    permutation = torch.empty(nnz, dtype=torch.int32, device=dev) if return_permutation else None
+    args = (_ptr(values), _ptr(row_offsets), _ptr(column_indices), rows, cols, nnz, _ptr(row_perm), _ptr(col_map), _ptr(values_b),
+            ctypes.c_void_p(row_offsets_b.data_ptr()), _ptr(cols_b), _ptr(permutation))
+    with torch.cuda.device(dev):
+        _two_phase(fn, "mspmv_csr_permute", dev, stream, args)
+    csr = DeviceCsr(rows, cols, row_offsets_b, cols_b, values_b)
+    return (csr, permutation) if return_permutation else csr
+
+
+def multicolor_reorder(values, row_offsets, column_indices, priorities=None, stream=None):
+    """(coloring, csr): the CsrColoring of a square pattern and P A P^T = csr_permute(values, ..., row_perm=coloring.order,
+    col_map=coloring.inverse).  Solve P A P^T x' = coloring.permute_vector(b); x = coloring.permute_vector(x', back=True)."""
+    coloring = CsrColoring(row_offsets, column_indices, priorities, stream=stream)
+    return coloring, csr_permute(values, row_offsets, column_indices, coloring.rows, row_perm=coloring.order, col_map=coloring.inverse,
+                                 stream=stream)
 
 
 class CsrMVPlan:
