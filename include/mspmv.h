@@ -711,8 +711,8 @@ int mspmv_csrsm_solve_f64(mspmv_csrsv_plan_t *plan, const double *d_values, cons
 
 /* ---- extension: ILU(0), the incomplete LU factorisation without fill-in, level-scheduled (csrc/mspmv_csrilu0.hip; what
  * rocsparse_csrilu0 is in rocSPARSE): A ~ L U on A's own pattern, the preconditioner whose two sweeps mspmv_csrsv_* solves.  With it
- * a preconditioned Krylov iteration stays inside this library: mspmv_csrmv_* for A p, mspmv_csrilu0_* once per matrix, two
- * mspmv_csrsv_solve_* per iteration.
+ * the sparse parts of a preconditioned Krylov iteration stay inside this library: mspmv_csrmv_* for A p, mspmv_csrilu0_* once per
+ * matrix, two mspmv_csrsv_solve_* per iteration (the loop itself is built for conjugate gradients only: mspmv_pcg_* below).
  * THE PLAN: lower_plan is any plan made by mspmv_csrsv_plan_create with MSPMV_CSRSV_LOWER (either diag) for this pattern: row i of
  * the row-wise elimination needs the finished rows whose column its strict lower part stores, which is the dependency graph of
  * L x = b, so the plan's levels, order and segments are the factorisation's too.  rows and nnz are taken from it; the same plan then
@@ -762,7 +762,8 @@ int mspmv_csrilu0_f64(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t
 /* ---- extension: IC(0), the incomplete Cholesky factorisation without fill-in, level-scheduled (csrc/mspmv_csric0.hip; what
  * rocsparse_csric0 is in rocSPARSE): A ~ L L^T on the pattern of A's lower triangle, the SYMMETRIC preconditioner that conjugate
  * gradients needs and ILU(0) cannot give, at half of ILU(0)'s work and half of its factor.  With it a preconditioned CG stays
- * inside this library: mspmv_csrmv_* for A p, mspmv_csric0_* once per matrix, two mspmv_csrsv_solve_* per iteration.
+ * inside this library: mspmv_csrmv_* for A p, mspmv_csric0_* once per matrix, two mspmv_csrsv_solve_* per iteration, and the loop
+ * itself with its dots and updates: mspmv_pcg_* below.
  * THE PLAN: lower_plan is any plan made by mspmv_csrsv_plan_create with MSPMV_CSRSV_LOWER (either diag) for this pattern: row i of
  * the row-wise Cholesky needs the finished rows whose column its strict lower part stores, which is the dependency graph of
  * L x = b, so the plan's levels, order and segments are the factorisation's too, exactly as for mspmv_csrilu0_*.  rows and nnz are
@@ -921,6 +922,129 @@ int mspmv_csr_permute_f64(void *d_temp, size_t *temp_bytes,
                           const int32_t *d_col_map  /* cols entries or NULL = identity */,
                           double *d_values_b, int32_t *d_row_offsets_b, int32_t *d_column_indices_b,
                           int32_t *d_permutation /* nnz entries, may be NULL */, mspmv_stream_t stream, int debug_sync);
+
+/* ---- extension: THE DETERMINISTIC REDUCTION and the dot product built on it (csrc/mspmv_vec.hpp, mspmv_vec.hip).  The one piece of a
+ * Krylov iteration whose bits a BLAS leaves open, defined here like everything else: *d_result = R(a o b), ONE value ON THE DEVICE.
+ * Nothing is read back, nothing allocated, no atomics; two launches ordered by the kernel boundary; the call can be captured in a graph.
+ * d_a == d_b gives the squared norm.  Inputs are not modified and may have any alignment of their type.
+ * DEFINITION, in the value type T.  The summands are the products s[i] = fl(a[i] * b[i]), i in [0, n), each rounded on its own (no
+ * fused multiply-add).  R(s) is a fixed tree, a function of n and T alone -- not of the grid, the alignment, the device or the kernel:
+ *     chunk(c[0 .. 1024))  =  q[t] = ((c[4t] + c[4t+1]) + c[4t+2]) + c[4t+3]  for t in [0, 256);  then eight times  q <- q[0::2] + q[1::2]
+ *                             (neighbours first: q[0] + q[1], q[2] + q[3], ...);  the one value left
+ *     level(v)             =  v cut into consecutive chunks of 1024, the last one filled up with +0.0;  [chunk(each)]
+ *                             (at least one chunk: an empty v gives one chunk of zeros)
+ *     R(s)                 =  p = level(s);   if p has more than 1024 entries:  p = level(p);   R = chunk(p filled up with +0.0 to 1024)
+ * The fill is +0.0 and the last step is ALWAYS made, which fixes the sign of a zero: products that are all -0.0 sum to -0.0 inside
+ * a chunk, and the result is -0.0 only if no step of the tree met a fill (n = 2^20 or n = 2^30: every level full);
+ * n == 0 gives +0.0.  Nothing is flushed to zero; Inf and NaN propagate (a NaN result is a NaN; its sign and payload are not defined).
+ * In numpy:  def chunk(c): q = c.reshape(-1, 256, 4); q = ((q[..., 0] + q[..., 1]) + q[..., 2]) + q[..., 3]
+ *                         while q.shape[1] > 1: q = q[:, 0::2] + q[:, 1::2]
+ *                         return q[:, 0]                                          (c: the padded level, a multiple of 1024 long)
+ * tests/pcg_model.py is this restatement.
+ * TEMP STORAGE, two-phase: d_temp == NULL writes the size to *temp_bytes, does no work and needs no device.  d_temp is 16-byte aligned
+ * and holds the level-1 partials: max(1, ceil(n / 1024)) values, rounded up to 16 bytes.  Whatever it held before does not matter.
+ * Asynchronous on `stream`; debug_sync prints one line per launch (vec_dot_kernel, vec_fold_kernel) and waits for it; returns 0 or a
+ * hipError_t.  LIMITS, refused before anything is launched: a NULL temp_bytes; n < 0; n > 2^30 (the fold has two levels); *temp_bytes
+ * too small; a misaligned d_temp; a NULL d_result; NULL d_a or d_b with n > 0.
+ * Measured on MI355X against torch.dot (rocBLAS) at n = 4 * 10^6 (tools/pcg_bench.py; profiles/pcg_bench.txt; DESIGN.md 4
+ * "Preconditioned conjugate gradients"), fp64 / fp32: 20 calls in a replayed graph, per call, 14.3 / 7.2 us against 16.5 / 9.0 us
+ * (4.5 TB/s); one call from Python between events, the host's enqueue of two launches included, 23.6 / 17.4 us against 19.1 /
+ * 13.0 us: torch.dot is 1.2 - 1.3 times faster there. ---- */
+int mspmv_vec_dot_f32(void *d_temp, size_t *temp_bytes, const float *d_a, const float *d_b, int64_t n, float *d_result,
+                      mspmv_stream_t stream, int debug_sync);
+int mspmv_vec_dot_f64(void *d_temp, size_t *temp_bytes, const double *d_a, const double *d_b, int64_t n, double *d_result,
+                      mspmv_stream_t stream, int debug_sync);
+
+/* ---- extension: PRECONDITIONED CONJUGATE GRADIENTS on the device (csrc/mspmv_pcg.hip): A x = b for a symmetric positive definite A in
+ * CSR, the loop that mspmv_csrmv_*, mspmv_csric0_* and mspmv_csrsv_* were built for, as one call.  The scalars of the iteration live
+ * on the device, the dots are the reduction R above, and the host reads nothing inside the loop unless asked to.
+ * THE HANDLE is opaque and OWNS ITS STORAGE, as mspmv_csrsv_plan_t does.  mspmv_pcg_create ALLOCATES (one hipMalloc: the vectors q, p,
+ * r, z, mid, the partials, the state block, the diagonal for JACOBI, and the temp storage of mspmv_csrmv_prepared_* in the size its
+ * query states), runs mspmv_csrmv_prepare on d_row_offsets, for JACOBI finds every row's diagonal entry (one lane per row) and reads
+ * state.bad_diagonal_row back; it is SYNCHRONOUS.  It depends on the pattern alone: new values need no new handle.
+ * PRECONDITIONER M, chosen at creation:
+ *     MSPMV_PCG_NONE     z = r
+ *     MSPMV_PCG_JACOBI   z[i] = r[i] / d[i], d[i] the stored diagonal entry of row i of d_values, taken once per solve.  A pattern with a
+ *                        row of no or of more than one diagonal entry (state.bad_diagonal_row >= 0) is refused by the solve.
+ *     MSPMV_PCG_FACTOR   z = second^-1 (first^-1 r): mspmv_csrsv_solve_* with first_plan on r into mid, then with second_plan on mid into
+ *                        z, alpha = 1, both on d_factor_values with ITS pattern arrays (mspmv_pcg_set_factor; none of them is copied or
+ *                        owned: they live as long as solves use them).  IC(0) with the mirror: first = LOWER + NON_UNIT, second = UPPER +
+ *                        NON_UNIT on the factor; ILU(0): LOWER + UNIT, UPPER + NON_UNIT; symmetric Gauss-Seidel: the same on A itself.
+ * ARITHMETIC, all in the value type T, every operation rounded on its own (no fused multiply-add), nothing flushed to zero:
+ *     x = +0.0, r = b            (use_x_as_guess: q = A x by mspmv_csrmv_prepared_*, r[i] = b[i] - q[i])
+ *     bb = R(b o b);  rt = (T) rtol, at = (T) atol;  s = fl(fl(rt * rt) * bb), a2 = fl(at * at);  stop2 = s > a2 ? s : a2
+ *     rr = R(r o r);  history[0] = rr;  iterations = 0;      rr <= stop2  ->  CONVERGED
+ *     z = M^-1 r;  rz = R(r o z);  p = z
+ *     iteration k = 1, 2, ...:
+ *         q = A p                                     (mspmv_csrmv_prepared_*, alpha = 1, beta = 0)
+ *         pq = R(p o q);                              not (pq > 0)  ->  BREAKDOWN: nothing else of this iteration is written,
+ *                                                                       iterations stays k - 1
+ *         alpha = rz / pq
+ *         x[i] = x[i] + fl(alpha * p[i]);   r[i] = r[i] - fl(alpha * q[i])
+ *         rr = R(r o r);  history[k] = rr;  iterations = k;      rr <= stop2  ->  CONVERGED;   rr is NaN  ->  BREAKDOWN
+ *         z = M^-1 r;  rz' = R(r o z);                not (rz' > 0)  ->  BREAKDOWN
+ *         beta = rz' / rz;  rz = rz';  p[i] = z[i] + fl(beta * p[i])
+ * (stop2 with a NaN s is a2.)  x, iterations, the status and the history are functions of the inputs alone -- not of check_every, the
+ * grid or the alignment of b and x.
+ * LAUNCHES: beside the product and the sweeps, an iteration launches state.launches_per_iteration kernels of the solver's own, a
+ * function of the preconditioner alone: 5 for NONE and JACOBI (the chunk sums of p o q; a one-workgroup step that folds them and
+ * makes alpha; the x and r updates fused with the chunk sums of r o r and, for JACOBI, with z and those of r o z; the step that folds
+ * them, tests and makes beta; the p update), 7 for FACTOR (the chunk sums of r o z and their step are launches of their own behind
+ * the sweeps).  No workgroup waits on another; there are no floating-point atomics.
+ * THE FREEZE: once the status is not RUNNING, every later kernel of the solver's own reads the status and returns: x, the state and
+ * the history entries beyond `iterations` stay as they are (the product and the sweeps still run, on scratch).  Hence
+ *     check_every = c > 0   iterations are enqueued c at a time; after each group the state block is read back (one small copy, one
+ *                           synchronisation) and the call returns at a status other than RUNNING or at max_iterations;
+ *     check_every = 0       max_iterations iterations are enqueued and nothing is read back: the call is asynchronous, allocates
+ *                           nothing and can be captured in a graph (one stream, no parallel branches);
+ * with the same x, iterations, status and history either way.  A solve that ends at max_iterations leaves the status RUNNING.
+ * d_history: max_iterations + 1 values of T on the device, or NULL.  d_x and d_b may have any alignment of T; they must not overlap.
+ * The matrix arrays passed to a solve hold the pattern the handle was made from.  mspmv_pcg_state reads the state block back on
+ * `stream` and waits for it (rows == 0: host only).  debug_sync prints one line per launch (pcg_*_kernel, and the lines of the
+ * product and the sweeps) and waits for each.
+ * LIMITS, refused before anything is launched or allocated: create -- a NULL `pcg`; rows, nnz < 0; rows + nnz > 2^31 - 65537; rows >
+ * 2^30; nnz > 0 with rows == 0; value_bytes not 4 or 8; an unknown kind; NULL d_row_offsets with rows > 0, NULL d_column_indices with
+ * nnz > 0.  set_factor -- a NULL handle or plan; a handle of another kind; a plan whose rows differ from the handle's or whose
+ * bad_diagonal_row >= 0; NULL factor arrays with nnz > 0.  solve -- a NULL handle or one of the other value type; rtol or atol
+ * negative or NaN; max_iterations < 0; check_every < 0; FACTOR without set_factor; JACOBI on a bad diagonal; NULL d_b, d_x or matrix
+ * arrays with rows > 0.  rows == 0 touches no device: create gives a valid handle, a solve returns CONVERGED at 0 iterations.
+ * Measured on MI355X (tools/pcg_bench.py; profiles/pcg_bench.txt; DESIGN.md 4 "Preconditioned conjugate gradients"), fp64, multicolour
+ * order, IC(0), against the torch loop it replaces (two torch.dot, four elementwise passes, one norm read back per iteration): the
+ * 5-point Laplacian + 0.01 I on 2000 x 2000, 114 iterations either way, 70.0 ms with check_every = 0 (72.9 ms with 1, 73.7 ms with 8,
+ * 70.0 ms replayed from a graph) against 77.6 ms; a 7-point grid of 128^3, 14 iterations, 7.94 ms (8.28 / 8.98 / 7.97 ms) against
+ * 8.58 ms: check_every = 8 enqueues 16 iterations there and LOSES 5 %.  Of 0.614 ms per iteration the product is 0.077, the two sweeps
+ * 0.464 and the solver's own launches 0.074 ms (the loop's glue: 0.14 ms), which is 416 MB of vector passes at 5.6 TB/s. ---- */
+#define MSPMV_PCG_NONE 0
+#define MSPMV_PCG_JACOBI 1
+#define MSPMV_PCG_FACTOR 2
+#define MSPMV_PCG_RUNNING 0
+#define MSPMV_PCG_CONVERGED 1
+#define MSPMV_PCG_BREAKDOWN 2
+typedef struct mspmv_pcg mspmv_pcg_t;
+typedef struct mspmv_pcg_state {
+    int32_t status;                  /* MSPMV_PCG_RUNNING (also: ended at max_iterations), _CONVERGED, _BREAKDOWN */
+    int32_t iterations;              /* updates of x made                                                         */
+    int32_t launches_per_iteration;  /* the solver's own, beside the product and the sweeps: the kind alone       */
+    int32_t precond_kind;
+    int32_t bad_diagonal_row;        /* JACOBI: smallest row with no or more than one stored diagonal; -1         */
+    int32_t reserved;
+    double rr, bb, stop2, rz;        /* the values of T, widened                                                  */
+    uint64_t device_bytes;           /* what the handle holds on the device                                       */
+} mspmv_pcg_state_t;
+int mspmv_pcg_create(mspmv_pcg_t **pcg, const int32_t *d_row_offsets, const int32_t *d_column_indices, int32_t rows, int32_t nnz,
+                     int32_t value_bytes, int32_t precond_kind, mspmv_stream_t stream, int debug_sync);
+int mspmv_pcg_set_factor(mspmv_pcg_t *pcg, mspmv_csrsv_plan_t *first_plan, mspmv_csrsv_plan_t *second_plan, const void *d_factor_values,
+                         const int32_t *d_row_offsets, const int32_t *d_column_indices);
+int mspmv_pcg_solve_f32(mspmv_pcg_t *pcg, const float *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                        const float *d_b, float *d_x, int32_t use_x_as_guess, double rtol, double atol, int32_t max_iterations,
+                        int32_t check_every, float *d_history /* max_iterations + 1 entries, or NULL */, mspmv_stream_t stream,
+                        int debug_sync);
+int mspmv_pcg_solve_f64(mspmv_pcg_t *pcg, const double *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
+                        const double *d_b, double *d_x, int32_t use_x_as_guess, double rtol, double atol, int32_t max_iterations,
+                        int32_t check_every, double *d_history /* max_iterations + 1 entries, or NULL */, mspmv_stream_t stream,
+                        int debug_sync);
+int mspmv_pcg_state(mspmv_pcg_t *pcg, mspmv_pcg_state_t *state, mspmv_stream_t stream);
+int mspmv_pcg_destroy(mspmv_pcg_t *pcg);
 
 /* ---- introspection (the counterpart of the reference's debug_synchronous
  * launch log, dispatch_spmv_orig.cuh:685-739, as data) ---- */
