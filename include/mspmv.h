@@ -973,7 +973,7 @@ int mspmv_vec_dot_f64(void *d_temp, size_t *temp_bytes, const double *d_a, const
  * ARITHMETIC, all in the value type T, every operation rounded on its own (no fused multiply-add), nothing flushed to zero:
  *     x = +0.0, r = b            (use_x_as_guess: q = A x by mspmv_csrmv_prepared_*, r[i] = b[i] - q[i])
  *     bb = R(b o b);  rt = (T) rtol, at = (T) atol;  s = fl(fl(rt * rt) * bb), a2 = fl(at * at);  stop2 = s > a2 ? s : a2
- *     rr = R(r o r);  history[0] = rr;  iterations = 0;      rr <= stop2  ->  CONVERGED
+ *     rr = R(r o r);  history[0] = rr;  iterations = 0;      rr <= stop2 and rr < +Inf  ->  CONVERGED
  *     z = M^-1 r;  rz = R(r o z);  p = z
  *     iteration k = 1, 2, ...:
  *         q = A p                                     (mspmv_csrmv_prepared_*, alpha = 1, beta = 0)
@@ -981,11 +981,15 @@ int mspmv_vec_dot_f64(void *d_temp, size_t *temp_bytes, const double *d_a, const
  *                                                                       iterations stays k - 1
  *         alpha = rz / pq
  *         x[i] = x[i] + fl(alpha * p[i]);   r[i] = r[i] - fl(alpha * q[i])
- *         rr = R(r o r);  history[k] = rr;  iterations = k;      rr <= stop2  ->  CONVERGED;   rr is NaN  ->  BREAKDOWN
+ *         rr = R(r o r);  history[k] = rr;  iterations = k;      rr <= stop2 and rr < +Inf  ->  CONVERGED;   rr is NaN  ->  BREAKDOWN
  *         z = M^-1 r;  rz' = R(r o z);                not (rz' > 0)  ->  BREAKDOWN
  *         beta = rz' / rz;  rz = rz';  p[i] = z[i] + fl(beta * p[i])
- * (stop2 with a NaN s is a2.)  x, iterations, the status and the history are functions of the inputs alone -- not of check_every, the
- * grid or the alignment of b and x.
+ * (stop2 with a NaN s is a2.  An infinite rr never converges, whatever stop2 is.  With +-Inf in b, bb and rr are +Inf (and stop2 with
+ * rtol > 0): the start stays RUNNING, and the solve ends BREAKDOWN by the rules above, which way depends on the signs.  q = A p holds
+ * infinities; if the products p[i] * q[i] hold a -Inf or a NaN beside the +Inf, pq is NaN and the solve ends at 0 iterations with x
+ * untouched; if every infinite product is +Inf, pq = +Inf passes, alpha = Inf / Inf is NaN, the update fills x and r with NaN and the
+ * solve ends at 1 iteration by the NaN rr.)  x, iterations, the status and the history are functions of the inputs alone -- not of
+ * check_every, the grid or the alignment of b and x.
  * LAUNCHES: beside the product and the sweeps, an iteration launches state.launches_per_iteration kernels of the solver's own, a
  * function of the preconditioner alone: 5 for NONE and JACOBI (the chunk sums of p o q; a one-workgroup step that folds them and
  * makes alpha; the x and r updates fused with the chunk sums of r o r and, for JACOBI, with z and those of r o z; the step that folds

@@ -1822,9 +1822,10 @@ class Pcg:
 
     def solve(self, values, b, x=None, rtol: float = 1e-8, atol: float = 0.0, max_iterations: int = 1000, check_every: int = 8,
               history=False, stream=None, debug_synchronous: bool = False):
-        """Solves A x = b to rr <= max(rtol^2 bb, atol^2) or max_iterations.  x: None (a new tensor, the start is +0) or a tensor that
-        holds the guess and receives the solution.  check_every = 0: nothing is read back and the call is asynchronous (and
-        capturable).  history: False, True (a new tensor of max_iterations + 1 entries, kept as .history) or such a tensor."""
+        """Solves A x = b to rr <= max(rtol^2 bb, atol^2) or max_iterations; an infinite rr never counts as converged (an Inf in b ends
+        BREAKDOWN: at 0 iterations, or at 1 with x all NaN).  x: None (a new tensor, the start is +0) or a tensor that holds the guess and receives the solution.
+        check_every = 0: nothing is read back and the call is asynchronous (and capturable).  history: False, True (a new tensor of
+        max_iterations + 1 entries, kept as .history) or such a tensor."""
         import torch
         if self._handle is None:
             raise MspmvError("Pcg: closed")

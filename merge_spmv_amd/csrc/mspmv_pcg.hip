@@ -203,7 +203,7 @@ __global__ __launch_bounds__(VEC_FOLD_BLOCK) void pcg_step_kernel(PcgDev<T> *st,
             st->alpha = 0; st->beta = 0; st->pq = 0; st->spare = 0;
             st->bb = bb; st->rr = rr; st->rz = rz; st->stop2 = stop2;
             st->iterations = 0;
-            st->status = rr <= stop2 ? MSPMV_PCG_CONVERGED : MSPMV_PCG_RUNNING;
+            st->status = rr <= stop2 && rr < (T) INFINITY ? MSPMV_PCG_CONVERGED : MSPMV_PCG_RUNNING;       // (never on an infinite residual)
             if (history) history[0] = rr;
         }
         return;
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(VEC_FOLD_BLOCK) void pcg_step_kernel(PcgDev<T> *st,
         st->rr = rr;
         st->iterations = k;
         if (history) history[k] = rr;
-        if (rr <= st->stop2) { st->status = MSPMV_PCG_CONVERGED; next = false; }
+        if (rr <= st->stop2 && rr < (T) INFINITY) { st->status = MSPMV_PCG_CONVERGED; next = false; }
         else if (rr != rr) { st->status = MSPMV_PCG_BREAKDOWN; next = false; }
     }
     if (!next) return;

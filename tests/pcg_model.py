@@ -65,9 +65,12 @@ def reduce_loop(v):
         return level(p)[0]
 
 
-def pcg(apply_A, apply_M, b, x0, rtol, atol, max_iterations):
+def pcg(apply_A, apply_M, b, x0, rtol, atol, max_iterations, info=None):
     """(x, status, iterations, history): history[0 .. iterations] as an array of b's dtype.  apply_A(p) -> A p, apply_M(r) -> M^-1 r, both
-    on arrays of b's dtype; x0 None: x = +0, r = b."""
+    on arrays of b's dtype; x0 None: x = +0, r = b.  info: a dict that receives the scalars as the solve leaves them (bb, stop2, rr, rz
+    and the last pq, of b's dtype; rz None if the solve ended before z was made, pq None before the first iteration) and
+    `exit`, the test that ended it: "start" or "rr" (CONVERGED),
+    "pq", "rr-nan" or "rz" (BREAKDOWN), None (max_iterations)."""
     t = b.dtype.type
     with np.errstate(all="ignore"):
         if x0 is None:
@@ -81,17 +84,18 @@ def pcg(apply_A, apply_M, b, x0, rtol, atol, max_iterations):
         stop2 = s if s > a2 else a2
         rr = dot(r, r)
         history = [rr]
-        if rr <= stop2:
-            return x, CONVERGED, 0, np.array(history, dtype=b.dtype)
-        z = apply_M(r)
-        rz = dot(r, z)
-        p = z.copy()
-        status, iterations = RUNNING, 0
-        for k in range(1, max_iterations + 1):
+        status, iterations, rz, pq, left = RUNNING, 0, None, None, None
+        if rr <= stop2 and rr < np.inf:                              # (an infinite residual never counts as converged)
+            status, left = CONVERGED, "start"
+        else:
+            z = apply_M(r)
+            rz = dot(r, z)
+            p = z.copy()
+        for k in range(1, max_iterations + 1 if status == RUNNING else 0):
             q = apply_A(p)
             pq = dot(p, q)
             if not pq > 0:
-                status = BREAKDOWN
+                status, left = BREAKDOWN, "pq"
                 break
             alpha = rz / pq
             x = x + alpha * p
@@ -99,18 +103,20 @@ def pcg(apply_A, apply_M, b, x0, rtol, atol, max_iterations):
             rr = dot(r, r)
             history.append(rr)
             iterations = k
-            if rr <= stop2:
-                status = CONVERGED
+            if rr <= stop2 and rr < np.inf:
+                status, left = CONVERGED, "rr"
                 break
             if rr != rr:
-                status = BREAKDOWN
+                status, left = BREAKDOWN, "rr-nan"
                 break
             z = apply_M(r)
             rz2 = dot(r, z)
             if not rz2 > 0:
-                status = BREAKDOWN
+                status, left = BREAKDOWN, "rz"
                 break
             beta = rz2 / rz
             rz = rz2
             p = z + beta * p
+        if info is not None:
+            info.update(bb=bb, stop2=stop2, rr=rr, rz=rz, pq=pq, exit=left)
         return x, status, iterations, np.array(history, dtype=b.dtype)

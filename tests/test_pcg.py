@@ -14,25 +14,15 @@ import pytest
 import merge_spmv_amd as M
 from conftest import ROOT
 import pcg_model as model
+from pcg_common import LIMIT, NP, PRECS, RESIDUAL, RTOL, TORCH, _bits, _host_product, _true_residual
 
 torch = pytest.importorskip("torch")
 gpu = pytest.mark.gpu
 
 NEW = ["mspmv_pcg_create", "mspmv_pcg_set_factor", "mspmv_pcg_solve_f32", "mspmv_pcg_solve_f64", "mspmv_pcg_state", "mspmv_pcg_destroy"]
-NP = {"f32": np.float32, "f64": np.float64}
-TORCH = {"f32": torch.float32, "f64": torch.float64}
-PRECS = ["f32", "f64"]
-RTOL = {"f32": 1e-5, "f64": 1e-10}
-RESIDUAL = {"f32": 1e-4, "f64": 1e-8}          # the true residual |b - A x| <= this |b|
 GRIDS = [(24, 24), (40, 25)]
 PRECONDS = ["none", "jacobi", "ic0", "ic0-multicolour"]
-LIMIT = 400
 NONE, JACOBI, FACTOR = 0, 1, 2
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int32 if a.dtype == np.float32 else np.int64)
 
 
 def _laplacian(w, h, dtype, diagonal=True):
@@ -47,14 +37,6 @@ def _laplacian(w, h, dtype, diagonal=True):
     col = np.asarray([c for r in rows for c in r], np.int32)
     r_of = np.repeat(np.arange(len(rows)), np.diff(off))
     return off, col, np.where(col == r_of, 4.0, -1.0).astype(dtype)
-
-
-def _true_residual(off, col, val, x, b):
-    """|b - A x| / |b| in fp64 on the host"""
-    r_of = np.repeat(np.arange(len(off) - 1), np.diff(off))
-    ax = np.zeros(len(off) - 1)
-    np.add.at(ax, r_of, val.astype(np.float64) * x.astype(np.float64)[col])
-    return float(np.linalg.norm(b.astype(np.float64) - ax)) / float(np.linalg.norm(b.astype(np.float64)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
@@ -133,17 +115,6 @@ def _dense(off, col, val):
     a = np.zeros((n, n), val.dtype)
     a[np.repeat(np.arange(n), np.diff(off)), col] = val
     return a
-
-
-def _host_product(off, col, val):
-    """A p on the host, every product and every add rounded in the value type"""
-    r_of = np.repeat(np.arange(len(off) - 1), np.diff(off))
-
-    def apply(p):
-        y = np.zeros(len(off) - 1, val.dtype)
-        np.add.at(y, r_of, val * p[col])
-        return y
-    return apply
 
 
 def test_the_model_solves_a_small_grid():
