@@ -17,7 +17,9 @@ from typing import Optional
 
 import numpy as np
 
-from . import load_library, _check, CsrMVWorkspace, DeviceSpmv, csrmv, _stream_handle, _value_bytes, MspmvError
+from ._lib import MspmvError, _MgInfo, _check, load_library
+from ._args import _Handle, _PlanArray, _stream_handle, _value_bytes
+from .csrmv import CsrMVWorkspace, csrmv
 
 EXCHANGE_AUTO, EXCHANGE_RCCL, EXCHANGE_PEER, EXCHANGE_IPC = 0, 1, 2, 3
 
@@ -46,21 +48,6 @@ def local_offsets(row_offsets_i64: np.ndarray, row_begin: int, row_end: int, nz_
     return out
 
 
-class _MgInfo(ctypes.Structure):
-    _fields_ = [("parts", ctypes.c_int32), ("local_parts", ctypes.c_int32), ("exchange", ctypes.c_int32),
-                ("value_bytes", ctypes.c_int32), ("replicas", ctypes.c_int32), ("hot_parts", ctypes.c_int32),
-                ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("carry_bytes_per_step", ctypes.c_uint64),
-                ("allgather_bytes_per_step", ctypes.c_uint64), ("steps", ctypes.c_uint64)]
-
-
-class _DeviceArray:
-    """plan-owned device memory seen by torch (torch.as_tensor reads __cuda_array_interface__: no copy)"""
-
-    def __init__(self, ptr: int, count: int, typestr: str):
-        self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False),
-                                         "version": 2, "strides": None}
-
-
 def unique_id() -> bytes:
     """128-byte token (an ncclUniqueId) ONE process makes and every process of a multi-process plan passes."""
     buf = ctypes.create_string_buffer(128)
@@ -68,13 +55,15 @@ def unique_id() -> bytes:
     return buf.raw
 
 
-class MgPlan:
+class MgPlan(_Handle):
     """Thin caller of the C multi-GPU operator (include/mspmv.h: mspmv_mg_plan_*): all the per-step work --
     the parts' CsrMV launches, the one carry exchange (peer reads or one RCCL all-gather) and the owners'
     adds -- happens below the C ABI in ONE call, `csrmv()`.
 
     part_ids / device_ids: the parts THIS process drives (all of them, or one per process under
     torch.distributed.run; then `id128` = unique_id() of one rank, shipped to the others)."""
+
+    _destroy = "mspmv_mg_plan_destroy"
 
     def __init__(self, row_split, nz_split, num_cols: int, dtype, part_ids, device_ids, exchange: int = EXCHANGE_AUTO,
                  id128: Optional[bytes] = None):
@@ -89,13 +78,15 @@ class MgPlan:
         self.device_ids = [int(d) for d in device_ids]
         self.num_cols = int(num_cols)
         ids = np.asarray(self.part_ids, dtype=np.int32); devs = np.asarray(self.device_ids, dtype=np.int32)
-        self._handle = ctypes.c_void_p()
+        self._lib = load_library()
+        handle = ctypes.c_void_p()
         idbuf = ctypes.create_string_buffer(id128, 128) if id128 is not None else None
-        _check(load_library().mspmv_mg_plan_create(ctypes.byref(self._handle), self.parts, len(self.part_ids),
-                                                   ids.ctypes.data_as(ctypes.c_void_p), devs.ctypes.data_as(ctypes.c_void_p),
-                                                   self.row_split.ctypes.data_as(ctypes.c_void_p),
-                                                   self.nz_split.ctypes.data_as(ctypes.c_void_p), self.num_cols, self.vb,
-                                                   int(exchange), idbuf), "mspmv_mg_plan_create")
+        _check(self._lib.mspmv_mg_plan_create(ctypes.byref(handle), self.parts, len(self.part_ids),
+                                              ids.ctypes.data_as(ctypes.c_void_p), devs.ctypes.data_as(ctypes.c_void_p),
+                                              self.row_split.ctypes.data_as(ctypes.c_void_p),
+                                              self.nz_split.ctypes.data_as(ctypes.c_void_p), self.num_cols, self.vb,
+                                              int(exchange), idbuf), "mspmv_mg_plan_create")
+        self._handle = handle
         self._keep = {}
 
     def local_rows(self, i: int) -> int:
@@ -122,48 +113,47 @@ class MgPlan:
                       not column_indices.is_contiguous() or column_indices.numel() != n):
             raise MspmvError("set_part: values / column_indices must be contiguous tensors of the part's nonzero count on its device")
         self._keep[i] = (values, local_row_offsets, column_indices)
-        _check(load_library().mspmv_mg_plan_set_part(self._handle, i, ctypes.c_void_p(values.data_ptr() if n else 0),
-                                                     ctypes.c_void_p(local_row_offsets.data_ptr()),
-                                                     ctypes.c_void_p(column_indices.data_ptr() if n else 0)),
+        _check(self._lib.mspmv_mg_plan_set_part(self._live(), i, ctypes.c_void_p(values.data_ptr() if n else 0),
+                                                ctypes.c_void_p(local_row_offsets.data_ptr()),
+                                                ctypes.c_void_p(column_indices.data_ptr() if n else 0)),
                "mspmv_mg_plan_set_part")
 
     def _view(self, ptr, count, i):
         torch = self.torch
         if count == 0:
             return torch.empty(0, dtype=self.dtype, device=torch.device("cuda", self.device_ids[i]))
-        t = torch.as_tensor(_DeviceArray(ptr, count, "<f4" if self.vb == 4 else "<f8"), device=torch.device("cuda", self.device_ids[i]))
-        return t
+        return torch.as_tensor(_PlanArray(ptr, count, "<f4" if self.vb == 4 else "<f8"), device=torch.device("cuda", self.device_ids[i]))
 
     def x(self, i: int):
         """the replica of x on local part i's device (num_cols entries), as a tensor aliasing plan memory"""
-        return self._view(load_library().mspmv_mg_plan_x(self._handle, i), self.num_cols, i)
+        return self._view(self._lib.mspmv_mg_plan_x(self._live(), i), self.num_cols, i)
 
     def y(self, i: int, with_open_row: bool = False):
         """local part i's owned rows of y (aliasing plan memory)"""
         n = self.local_rows(i) if with_open_row else self.owned_rows(i)
-        return self._view(load_library().mspmv_mg_plan_y(self._handle, i), n, i)
+        return self._view(self._lib.mspmv_mg_plan_y(self._live(), i), n, i)
 
     def stream(self, i: int) -> int:
-        return int(load_library().mspmv_mg_plan_stream(self._handle, i) or 0)
+        return int(self._lib.mspmv_mg_plan_stream(self._live(), i) or 0)
 
     def info(self) -> dict:
         info = _MgInfo()
-        _check(load_library().mspmv_mg_plan_info(self._handle, ctypes.byref(info)), "mspmv_mg_plan_info")
+        _check(self._lib.mspmv_mg_plan_info(self._live(), ctypes.byref(info)), "mspmv_mg_plan_info")
         return {name: getattr(info, name) for name, _ in _MgInfo._fields_}
 
     def ipc_export(self) -> bytes:
         """this process's hipIpc handles (x replicas, mailbox blocks) as one blob (mspmv_mg_plan_ipc_export)"""
         size = ctypes.c_size_t(0)
-        _check(load_library().mspmv_mg_plan_ipc_export(self._handle, None, ctypes.byref(size)), "mspmv_mg_plan_ipc_export")
+        _check(self._lib.mspmv_mg_plan_ipc_export(self._live(), None, ctypes.byref(size)), "mspmv_mg_plan_ipc_export")
         buf = ctypes.create_string_buffer(size.value)
-        _check(load_library().mspmv_mg_plan_ipc_export(self._handle, buf, ctypes.byref(size)), "mspmv_mg_plan_ipc_export")
+        _check(self._lib.mspmv_mg_plan_ipc_export(self._live(), buf, ctypes.byref(size)), "mspmv_mg_plan_ipc_export")
         return buf.raw[: size.value]
 
     def ipc_import(self, blobs):
         """every process's blob (its own included, any order): opens the peers' memory (mspmv_mg_plan_ipc_import)"""
         stride = max(len(b) for b in blobs)
         flat = b"".join(b + b"\0" * (stride - len(b)) for b in blobs)
-        _check(load_library().mspmv_mg_plan_ipc_import(self._handle, flat, len(blobs), stride), "mspmv_mg_plan_ipc_import")
+        _check(self._lib.mspmv_mg_plan_ipc_import(self._live(), flat, len(blobs), stride), "mspmv_mg_plan_ipc_import")
 
     def ipc_connect(self, group=None):
         """export, all-gather the blobs over torch.distributed (any backend), import: one call per rank"""
@@ -176,38 +166,27 @@ class MgPlan:
     def hot_columns(self, enable=True):
         """the parts' hot-column plans (mspmv_mg_plan_hot_columns): True / 1 always, False / 0 never, -1 automatic (the default of a new
         plan: decided per part when its matrix is attached)"""
-        _check(load_library().mspmv_mg_plan_hot_columns(self._handle, -1 if (enable is not True and enable is not False and int(enable) < 0) else int(bool(enable))),
+        _check(self._lib.mspmv_mg_plan_hot_columns(self._live(), -1 if (enable is not True and enable is not False and int(enable) < 0) else int(bool(enable))),
                "mspmv_mg_plan_hot_columns")
 
     def exchange_ms(self, local_index: int = 0) -> float:
         """milliseconds the exchange of the last step took on a local part (mspmv_mg_plan_exchange_ms; synchronises)"""
         ms = ctypes.c_float(0)
-        lib = load_library()
-        lib.mspmv_mg_plan_exchange_ms.restype = ctypes.c_int
-        lib.mspmv_mg_plan_exchange_ms.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-        _check(lib.mspmv_mg_plan_exchange_ms(self._handle, int(local_index), ctypes.byref(ms)), "mspmv_mg_plan_exchange_ms")
+        _check(self._lib.mspmv_mg_plan_exchange_ms(self._live(), int(local_index), ctypes.byref(ms)), "mspmv_mg_plan_exchange_ms")
         return float(ms.value)
 
     def csrmv(self):
-        _check(load_library().mspmv_mg_csrmv(self._handle), "mspmv_mg_csrmv")
+        _check(self._lib.mspmv_mg_csrmv(self._live()), "mspmv_mg_csrmv")
 
     def allgather_rows(self):
-        _check(load_library().mspmv_mg_allgather_rows(self._handle), "mspmv_mg_allgather_rows")
+        _check(self._lib.mspmv_mg_allgather_rows(self._live()), "mspmv_mg_allgather_rows")
 
     def synchronize(self):
-        _check(load_library().mspmv_mg_synchronize(self._handle), "mspmv_mg_synchronize")
+        _check(self._lib.mspmv_mg_synchronize(self._live()), "mspmv_mg_synchronize")
 
     def close(self):
-        if self._handle:
-            load_library().mspmv_mg_plan_destroy(self._handle)
-            self._handle = ctypes.c_void_p()
-            self._keep = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self._keep = {}
 
 
 @dataclass

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import ROOT
 import merge_spmv_amd as M
+from merge_spmv_amd import _lib as L                     # (the loader: its state is what test_missing_library_fails_loudly replaces)
 from oracle import oracle as O
 
 
@@ -69,8 +70,8 @@ def test_setters_switch_to_the_development_library_and_defaults_do_not():
 
 
 def test_missing_library_fails_loudly(monkeypatch):
-    monkeypatch.setattr(M, "_libs", {})
-    monkeypatch.setattr(M, "_LIB_NAMES", {"product": "libmspmv_does_not_exist.so", "dev": "libmspmv_dev.so"})
+    monkeypatch.setattr(L, "_libs", {})
+    monkeypatch.setattr(L, "_LIB_NAMES", {"product": "libmspmv_does_not_exist.so", "dev": "libmspmv_dev.so"})
     monkeypatch.delenv("MSPMV_LIB", raising=False)
     with pytest.raises(M.MspmvError):
         M.load_library()
@@ -230,3 +231,27 @@ def test_headers_are_plain_c(tmp_path):
     r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-c", str(src), "-o", str(tmp_path / "hdr.o"), "-I", ROOT],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+# merge_spmv_amd.__all__ as it stood when the package was one module: the split by operation must not change the surface
+ALL = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr",
+       "csr_sum_duplicates", "coomv", "csr_add", "CsrAdd", "csr_symmetrize", "csr_gemm", "CsrGemm", "csr_gemm_products", "sddmm", "CsrSv", "csrsv",
+       "csrsm", "csrilu0", "Ilu0", "csric0", "Ic0", "CsrColoring", "csr_color", "csr_permute", "multicolor_reorder", "vec_dot", "Pcg", "pcg",
+       "plan_bench_record", "library_path", "load_library", "launch_info", "set_tuning", "set_tdm", "clocked_bands", "debug_read_tiles",
+       "profile_begin", "profile_end", "MspmvError", "TUNE_ATOMIC_FIX", "TUNE_NO_VEC"]
+# the private names tests, tools and bench.py reach through the package
+PRIVATE = ["_libs", "_ptr", "_stream_handle", "_CsrSvInfo", "_CsrSmInfo", "_CsrColorInfo", "_PcgState", "_ilu0_temp_bytes", "_ilu0_call",
+           "_ic0_temp_bytes", "_ic0_call", "_many_layout"]
+
+
+def test_the_package_surface_survives_the_split_by_operation():
+    assert M.__all__ == ALL
+    for name in ALL + PRIVATE:
+        assert getattr(M, name, None) is not None, name
+    assert M._libs is L._libs                        # conftest.py reads M._libs: the loader's dict itself, never a copy
+    assert M.use_library("dev") == "product"
+    M.load_library()
+    assert M._libs is L._libs and "dev" in M._libs
+    assert M.use_library("product") == "dev"
+    M.load_library()
+    assert M._libs is L._libs and set(M._libs) == {"product", "dev"}
