@@ -81,7 +81,8 @@ int mspmv_set_record_polls(int32_t polls);
  * problems (dispatch_spmv_orig.cuh:674-679, agent_spmv_orig.cuh:867-891). */
 int mspmv_set_compact_tiles(int32_t max_tiles);
 #ifdef MSPMV_DEV
-/* -DMSPMV_DEV only: device buffer (16 x 8 uint64 per block) receiving the clock64() stamps; NULL turns it off */
+/* -DMSPMV_DEV only: device buffer (16 x 8 uint64 per block) receiving the clock64() stamps; NULL turns it off.  While it is set the
+ * clocked kernel stamps too, EVERY block of its launch: 8 uint64 per tile, wall clock (tools/trace_tiles.py clocked) */
 int mspmv_dev_set_trace(void *d_buf);
 #endif
 #ifdef __cplusplus

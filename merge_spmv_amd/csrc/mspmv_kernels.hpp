@@ -229,11 +229,19 @@ __global__ __launch_bounds__(BLOCK, (tile_waves_per_simd<V, BLOCK, IPT, !BODY::P
                 //  loads, the ordinary one compiles as it does in the kernel of the passes, and this one needs no lane swaps)
                 asm volatile("" : "+s"(p.nnz));       // (nothing of this body is merged with the ordinary one's)
                 constexpr bool VALS = true, LINEWISE_OK = false;
+#ifdef MSPMV_DEV
+                // development: eight wall-clock stamps per block (the buffer of mspmv_dev_set_trace: 8 words per tile; tools/trace_tiles.py clocked)
+                unsigned long long *const tdm_tr = g_mspmv_trace ? g_mspmv_trace + (size_t) blockIdx.x * 8 : nullptr;
+                if (tdm_tr && threadIdx.x == 0) tdm_tr[0] = wall_clock64();
+#else
+                unsigned long long *const tdm_tr = nullptr;
+#endif
                 issue_nonzero_loads<V, BLOCK, IPT, NT, VALS, LINEWISE_OK>(p, c0, c1, tregs);
                 stage_tile_tdm<V, BLOCK, IPT, NT>(p, c0, c1, tregs, s_end_raw, s_prod_raw, (p.nnz & ~3) - 4, ((p.rows + 1) & ~3) - 4, s_flag,
-                                                  s_tdm_start, s_wave_key, ba.tdm, (int) threadIdx.x);
+                                                  s_tdm_start, s_wave_key, ba.tdm, (int) threadIdx.x, tdm_tr);
                 consume_tile_flags<V, BLOCK, IPT, AXPBY>(p, c0, c1.x - c0.x, c1.y - c0.y, s_end_raw + ((c0.x + 1) - ((c0.x + 1) & ~3)), s_prod_raw, s_flag,
                                                          s_wave_key, s_wave_val, carries + tile, c0.y - (c0.y & ~3));
+                if (tdm_tr && threadIdx.x == 0) tdm_tr[7] = wall_clock64();
                 return;
             } else {
                 // the passes instead: run by the first ba.grid blocks of this launch, the others return

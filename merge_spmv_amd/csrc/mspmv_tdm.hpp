@@ -2,17 +2,24 @@
 //
 // The column-band passes (run_band_passes, mspmv_kernels.hpp) read the whole CSR stream once per band so that at any moment
 // every XCD gathers from one slice of x, which its 4 MiB L2 keeps.  Here the stream is read ONCE.  A block
-//   1. loads its merge-path tile's (column, value) chunks as every tile kernel does,
+//   1. loads its merge-path tile's (column, value) chunks as every tile kernel does -- and, right behind them, every thread's first
+//      chunk of the tile's row ends, which then arrive with the stream,
 //   2. sorts the tile's nonzeros by column band THROUGH LDS (replicated counters filled by LDS atomics, one exclusive scan, a second
 //      round of atomics that hands out positions; the sorted (slot | column-in-band) words pass through the product array and come
 //      back into registers, striped over the block: no LDS beyond what the tile kernel has anyway),
-//   3. gathers band by band -- and WHEN it may gather from a band is read off the chip-wide 100 MHz clock (s_memrealtime):
+//   3. stages the row ends it has (tile-relative ends, row-start bits: the counters' space is free once the sort is through),
+//   4. gathers band by band -- and WHEN it may gather from a band is read off the chip-wide 100 MHz clock (s_memrealtime):
 //      band (t / slot) % B is "on air".  Blocks never talk to each other: whatever tile a block holds and whenever it got
 //      it, its gathers of band b happen while the other blocks of its XCD gather from band b (or the ones just after), so the
 //      XCD's L2 holds a band or two of x and the gathers hit.  The x values land in the product array at the nonzeros'
 //      own slots,
-//   4. multiplies (every thread its own chunks again), stages the row ends, and hands over to the ordinary reduction
-//      (consume_tile_flags): y is written once, with the caller's alpha and beta, one carry per tile, ordinary fix-up.
+//   5. multiplies (every thread its own chunks again), takes the remaining row ends (only a tile of more than 4 * BLOCK - eshift
+//      rows has any), patches the ragged array tails, and hands over to the ordinary reduction (consume_tile_flags): y is written
+//      once, with the caller's alpha and beta, one carry per tile, ordinary fix-up.
+// (Until the tile life was measured phase by phase -- tools/trace_tiles.py clocked, profiles/clocked_tile_life_*.txt,
+//  docs/history/clocked_tile_life.md -- all row ends were requested behind the last gather and awaited there, and the poll loop
+//  reloaded eleven spilled lane masks each time it looked at the clock and walked the band starts lane by lane.  Forming the product
+//  at the gather -- values parked in the product array, no multiply pass -- was built and measured too: 0.2 % SLOWER, not kept.)
 // The clock is a cache-affinity schedule, not a protocol: a block may gather any band at any time and the result is the
 // same -- bit for bit the one-sweep tile_kernel_vec's, since products and reduction are the same (unlike the passes,
 // which add band partials).  Nothing waits for another workgroup; a wave with nothing on air sleeps and looks again.
@@ -42,8 +49,10 @@ constexpr int TDM_SLOT_SHIFT = 20;         // sorted word = slot in the tile's r
 template <typename V, int BLOCK, int IPT, bool NT>
 __device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c0, const Coord c1, const TileRegs<V, BLOCK, IPT> &regs,
                                                end16_t *s_end_raw, V *s_prod_raw, int last_full_nz, int last_full_ro, unsigned *s_flag,
-                                               int *s_start, int *s_wave_sum, const TdmArgs &ta, int tid)
+                                               int *s_start, int *s_wave_sum, const TdmArgs &ta, int tid, unsigned long long *tr = nullptr)
 {
+    // (tr: -DMSPMV_DEV only, eight wall-clock stamps of this block's life, thread 0: tools/trace_tiles.py clocked; nullptr in the product)
+#define MSPMV_TDM_TR(i) do { if (tr && tid == 0) tr[i] = wall_clock64(); } while (0)
     constexpr int CPT = IPT / 4 + 1;
     constexpr int NW = BLOCK / WAVE;
     constexpr int SLOTS = CPT * BLOCK * 4;
@@ -58,11 +67,40 @@ __device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c
     const int first = c0.x + 1;
     const int i0 = first & ~3;
     const int eshift = first - i0;
-    int *const s_cnt = reinterpret_cast<int *>(s_end_raw);           // [band][wave][copy]; the row ends are staged after the gathers
+    int *const s_cnt = reinterpret_cast<int *>(s_end_raw);           // [band][wave][copy]; the row ends are staged once the sort is through
     unsigned *const s_exch = reinterpret_cast<unsigned *>(s_prod_raw);
     const unsigned col_mask = (1u << ta.band_shift) - 1u;
     const int ncnt = ta.bands * (NW * TDM_COPIES);
+    // row ends of the tile: every thread's first chunk is requested now, behind the nonzeros (the caller has just asked for them), and
+    // arrives with them -- tiles of up to 4 * BLOCK - eshift rows, i.e. all but those of very short rows, which take the other chunks
+    // behind the gathers.  Clamped as everywhere: nothing outside [0, rows] is read.
+    const int ro_chunks = (tile_rows + eshift + 3) / 4;
+    const int ro_safe = i0 < last_full_ro ? i0 : last_full_ro;
+    auto ro_load = [&](int q) {
+        int i = i0 + 4 * q;
+        i = (q < ro_chunks && i <= last_full_ro) ? i : ro_safe;
+        return ld_stream4<NT>(row_offsets + i);
+    };
+    // tile-relative row ends of chunk q and the row-start bits they set (the sentinel outside the tile and where step 7 patches)
+    auto ro_stage = [&](const Vec4<int> &ro, int q) {
+        const int i = i0 + 4 * q;
+        int v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = 4 * q - eshift + j;
+            const bool in = r >= 0 && r < tile_rows && i <= last_full_ro;
+            v[j] = in ? ro.get(j) - c0.y : 0x3fffffff;
+            if ((unsigned) v[j] < (unsigned) tile_nnz) {
+                const int b = (c0.y - a0) + v[j];
+                atomicOr(&s_flag[b >> 5], 1u << (b & 31));
+            }
+        }
+        st_lds4(&s_end_raw[4 * q], v);
+    };
+    const Vec4<int> ro_first = ro_load(tid);
 
+    if (tr) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    MSPMV_TDM_TR(1);
     // ---- 1. how many nonzeros of the tile fall into every (band, wave, copy) bucket
     for (int j = tid; j < ncnt; j += BLOCK) s_cnt[j] = 0;
     __syncthreads();
@@ -135,17 +173,25 @@ __device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c
         if (__popcll(__ballot(lane < ta.bands && st > lo)) <= 2) lookahead = ta.bands;
     }
     __syncthreads();                          // every sorted word is in registers: the product array may take the x values
+    MSPMV_TDM_TR(2);
+    // ---- the row ends that came with the stream, and their row-start bits (the counters' space has been free since the barrier after
+    //      step 3): their four registers are free before the rotation begins
+    ro_stage(ro_first, tid);
+    if (tid == 0) atomicOr(&s_flag[0], 1u << (c0.y - a0));
     // ---- 4. band by band, as the clock says; every wave on its own
     {
-        const int sorted = s_start[ta.bands];
+        // (what the loop below decides on is the wave's, and said to be: in scalar registers, with scalar branches)
+        const int sorted = __builtin_amdgcn_readfirstlane(s_start[ta.bands]);
+        const int wave_first = __builtin_amdgcn_readfirstlane(wave * WAVE);
         unsigned done = 0u;
 #pragma unroll
-        for (int k = 0; k < IPT; ++k) if (k * BLOCK + wave * WAVE >= sorted) done |= 1u << k;
+        for (int k = 0; k < IPT; ++k) if (k * BLOCK + wave_first >= sorted) done |= 1u << k;
         const unsigned all = (1u << IPT) - 1u;
         // (a safety valve, not a schedule: a wave that has found nothing on air 4096 times in a row -- ~0.6 ms, twenty rotations and
         //  more -- stops asking the clock and takes what is left; it never fires under a clock that runs, and no launch can hang on one
         //  that does not)
         int idle = 0;
+        bool first_stamped = false;
         while (done != all) {
             // (24 bits of the clock: exact in a float; the wrap every 0.17 s costs one odd slot)
             const unsigned slot = (unsigned) ((float) ((unsigned) wall_clock64() & 0xFFFFFFu) * ta.inv_slot);
@@ -153,6 +199,10 @@ __device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c
             //  at once, was tried: 0.651 -> 0.647 ms fp32, 0.990 -> 0.982 fp64, within noise; not kept)
             const int on_air = (int) (slot % (unsigned) ta.bands);
             bool any = false;
+            // (the count of sorted words goes through an empty asm once per look at the clock: `idx < sorted` is then worked out where a
+            //  window is taken -- hoisted out of the loop, the eleven lane masks were 22 scalar registers kept, spilled and reloaded in it)
+            int sorted_now = sorted;
+            asm volatile("" : "+s"(sorted_now));
 #pragma unroll
             for (int k = 0; k < IPT; ++k) {
                 if ((done >> k) & 1u) continue;
@@ -161,29 +211,29 @@ __device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c
                 // (a window that also reaches BACK from the band on air is the same thing with the clock shifted: measured, only its width matters)
                 if (d > lookahead && idle <= 4096) continue;
                 const int idx = k * BLOCK + tid;
-                if (idx < sorted) {
-                    int q = wq;
-                    while (q + 1 < ta.bands && idx >= s_start[q + 1]) ++q;         // (a window seldom spans more than two bands)
+                if (idx < sorted_now) {
+                    // the band of every lane's entry: the window's first band and how many of the next two band starts lie at or before the
+                    // entry -- two reads at wave-uniform addresses, issued together (clamped to the end mark, s_start[bands] = sorted >
+                    // idx); a window that spans more than three bands, which is rare, walks on as all of them used to, a round trip per step
+                    const int b1 = s_start[wq + 1 < ta.bands ? wq + 1 : ta.bands];
+                    const int b2 = s_start[wq + 2 < ta.bands ? wq + 2 : ta.bands];
+                    int q = wq + (idx >= b1 ? 1 : 0) + (idx >= b2 ? 1 : 0);
+                    if (idx >= b2)
+                        while (q + 1 < ta.bands && idx >= s_start[q + 1]) ++q;
                     const unsigned e = ent[k];
-                    s_prod_raw[prod_slot<V, CPT>((int) (e >> TDM_SLOT_SHIFT))] = p.x[((unsigned) q << ta.band_shift) | (e & col_mask)];
+                    const V xv = p.x[((unsigned) q << ta.band_shift) | (e & col_mask)];
+                    if (tr && !first_stamped) { MSPMV_TDM_TR(3); first_stamped = true; }
+                    s_prod_raw[prod_slot<V, CPT>((int) (e >> TDM_SLOT_SHIFT))] = xv;
                 }
                 done |= 1u << k; any = true;
             }
             if (!any) { ++idle; __builtin_amdgcn_s_sleep(4); } else idle = 0;
         }
     }
-    // row ends of the tile: requested behind the gathers (12 registers the gather phase does without), staged below
-    Vec4<int> ro[CPT];
-    const int ro_chunks = (tile_rows + eshift + 3) / 4;
-    const int ro_safe = i0 < last_full_ro ? i0 : last_full_ro;
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int q = tid + k * BLOCK;
-        int i = i0 + 4 * q;
-        i = (q < ro_chunks && i <= last_full_ro) ? i : ro_safe;
-        ro[k] = ld_stream4<NT>(row_offsets + i);
-    }
+    if (tr) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    MSPMV_TDM_TR(4);
     __syncthreads();
+    MSPMV_TDM_TR(5);
     // ---- 5. products: every thread its own chunks again (x value in place -> product in place)
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
@@ -197,25 +247,15 @@ __device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c
         for (int i = 0; i < 4; ++i) prod[i] = ((in_mask >> (4 * k + i)) & 1u) ? own_val.get(i) * xv[i] : (V) 0;
         st_prod_chunk<CPT>(s_prod_raw, chunk, prod, false);
     }
-    // ---- 6. row ends and row-start bits (the counters' space is free again)
+    // ---- 6. a tile of more than 4 * BLOCK - eshift rows (block-uniform; rows of fewer than two nonzeros on average): the rest of its
+    //         row ends, requested behind the gathers as all of them used to be (registers the gather phase does without)
+    if (ro_chunks > BLOCK) {
+        Vec4<int> ro[CPT - 1];
 #pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int q = tid + k * BLOCK;
-        const int i = i0 + 4 * q;
-        int v[4];
+        for (int k = 1; k < CPT; ++k) ro[k - 1] = ro_load(tid + k * BLOCK);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = 4 * q - eshift + j;
-            const bool in = r >= 0 && r < tile_rows && i <= last_full_ro;
-            v[j] = in ? ro[k].get(j) - c0.y : 0x3fffffff;
-            if ((unsigned) v[j] < (unsigned) tile_nnz) {
-                const int b = (c0.y - a0) + v[j];
-                atomicOr(&s_flag[b >> 5], 1u << (b & 31));
-            }
-        }
-        st_lds4(&s_end_raw[4 * q], v);
+        for (int k = 1; k < CPT; ++k) ro_stage(ro[k - 1], tid + k * BLOCK);
     }
-    if (tid == 0) atomicOr(&s_flag[0], 1u << (c0.y - a0));
     // ---- 7. ragged array tails (only the tile that reaches the end of an array), as stage_tile_careful patches them
     const bool nz_tail = c1.y > last_full_nz + 4;
     const bool ro_tail = first + tile_rows > last_full_ro + 4;
@@ -235,6 +275,8 @@ __device__ __forceinline__ void stage_tile_tdm(const Params<V> &p, const Coord c
         }
     }
     __syncthreads();
+    MSPMV_TDM_TR(6);
+#undef MSPMV_TDM_TR
 }
 
 }  // namespace mspmv
