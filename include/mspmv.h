@@ -712,7 +712,8 @@ int mspmv_csrsm_solve_f64(mspmv_csrsv_plan_t *plan, const double *d_values, cons
 /* ---- extension: ILU(0), the incomplete LU factorisation without fill-in, level-scheduled (csrc/mspmv_csrilu0.hip; what
  * rocsparse_csrilu0 is in rocSPARSE): A ~ L U on A's own pattern, the preconditioner whose two sweeps mspmv_csrsv_* solves.  With it
  * the sparse parts of a preconditioned Krylov iteration stay inside this library: mspmv_csrmv_* for A p, mspmv_csrilu0_* once per
- * matrix, two mspmv_csrsv_solve_* per iteration (the loop itself is built for conjugate gradients only: mspmv_pcg_* below).
+ * matrix, two mspmv_csrsv_solve_* per iteration (the loop itself is built for conjugate gradients: mspmv_pcg_* below, and for
+ * BiCGStab, the nonsymmetric case this factor is for: mspmv_bicgstab_* of include/mspmv_krylov.h; GMRES is not).
  * THE PLAN: lower_plan is any plan made by mspmv_csrsv_plan_create with MSPMV_CSRSV_LOWER (either diag) for this pattern: row i of
  * the row-wise elimination needs the finished rows whose column its strict lower part stores, which is the dependency graph of
  * L x = b, so the plan's levels, order and segments are the factorisation's too.  rows and nnz are taken from it; the same plan then
@@ -763,7 +764,7 @@ int mspmv_csrilu0_f64(const mspmv_csrsv_plan_t *lower_plan, void *d_temp, size_t
  * rocsparse_csric0 is in rocSPARSE): A ~ L L^T on the pattern of A's lower triangle, the SYMMETRIC preconditioner that conjugate
  * gradients needs and ILU(0) cannot give, at half of ILU(0)'s work and half of its factor.  With it a preconditioned CG stays
  * inside this library: mspmv_csrmv_* for A p, mspmv_csric0_* once per matrix, two mspmv_csrsv_solve_* per iteration, and the loop
- * itself with its dots and updates: mspmv_pcg_* below.
+ * itself with its dots and updates: mspmv_pcg_* below (for nonsymmetric matrices: mspmv_bicgstab_* of include/mspmv_krylov.h).
  * THE PLAN: lower_plan is any plan made by mspmv_csrsv_plan_create with MSPMV_CSRSV_LOWER (either diag) for this pattern: row i of
  * the row-wise Cholesky needs the finished rows whose column its strict lower part stores, which is the dependency graph of
  * L x = b, so the plan's levels, order and segments are the factorisation's too, exactly as for mspmv_csrilu0_*.  rows and nnz are
