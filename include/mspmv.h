@@ -713,7 +713,7 @@ int mspmv_csrsm_solve_f64(mspmv_csrsv_plan_t *plan, const double *d_values, cons
  * rocsparse_csrilu0 is in rocSPARSE): A ~ L U on A's own pattern, the preconditioner whose two sweeps mspmv_csrsv_* solves.  With it
  * the sparse parts of a preconditioned Krylov iteration stay inside this library: mspmv_csrmv_* for A p, mspmv_csrilu0_* once per
  * matrix, two mspmv_csrsv_solve_* per iteration (the loop itself is built for conjugate gradients: mspmv_pcg_* below, and for
- * BiCGStab, the nonsymmetric case this factor is for: mspmv_bicgstab_* of include/mspmv_krylov.h; GMRES is not).
+ * BiCGStab, the nonsymmetric case this factor is for: mspmv_bicgstab_* of include/mspmv_krylov.h, and GMRES(m): mspmv_gmres_* of include/mspmv_gmres.h).
  * THE PLAN: lower_plan is any plan made by mspmv_csrsv_plan_create with MSPMV_CSRSV_LOWER (either diag) for this pattern: row i of
  * the row-wise elimination needs the finished rows whose column its strict lower part stores, which is the dependency graph of
  * L x = b, so the plan's levels, order and segments are the factorisation's too.  rows and nnz are taken from it; the same plan then

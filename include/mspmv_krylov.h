@@ -3,7 +3,7 @@
  * The layer calls only what libmspmv.so exports -- mspmv_csrmv_prepare, mspmv_csrmv_prepared_*, mspmv_csrsv_solve_*,
  * mspmv_csrsv_plan_info -- and is linked against the libmspmv.so next to it.  mspmv.h itself holds conjugate gradients
  * (mspmv_pcg_*), which need a symmetric positive definite matrix; what is here serves the NONSYMMETRIC case, for which
- * mspmv_csrilu0_* makes the factor.  GMRES is not here.
+ * mspmv_csrilu0_* makes the factor.  GMRES(m) is mspmv_gmres.h.
  *
  * ---- RIGHT-PRECONDITIONED BiCGStab on the device (csrc/mspmv_bicgstab.hip): A x = b for a square A in CSR, as one call.  The
  * scalars of the iteration live in a state block on the device, every dot is the deterministic reduction R of mspmv.h

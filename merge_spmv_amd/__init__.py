@@ -21,6 +21,8 @@ This file only gathers the names; the code lives, one operation family per modul
   krylov      vec_dot, Pcg, pcg
   bicgstab    Bicgstab, bicgstab, BICGSTAB_EXIT: the Krylov layer on top of the C ABI (include/mspmv_krylov.h, libmspmv_krylov.so, which
               always runs on the product libmspmv.so next to it); attributes of the package, not in __all__
+  gmres       Gmres, gmres, GMRES_EXIT: restarted GMRES(m), the same kind of layer (include/mspmv_gmres.h, libmspmv_gmres.so);
+              attributes of the package, not in __all__
   plans       CsrMVPlan, CsrMVHotColumns and bench.py's records of them
   introspect  launch_info, the setters of the development library, profiling, debug readers, sampled_check
 (multi_gpu and generators are imported by name, as before).  Imports run down this list only.
@@ -40,6 +42,7 @@ from .solve import (CsrSv, Ic0, Ilu0, _ic0_call, _ic0_temp_bytes, _ilu0_call, _i
 from .reorder import CsrColoring, csr_color, multicolor_reorder
 from .krylov import PCG_STATUS, Pcg, pcg, vec_dot
 from .bicgstab import BICGSTAB_EXIT, Bicgstab, bicgstab
+from .gmres import GMRES_EXIT, Gmres, gmres
 from .plans import CsrMVHotColumns, CsrMVPlan, hotcols_bench_record, plan_bench_record
 
 __all__ = ["DeviceSpmv", "csrmv", "csrmv_mixed", "csrmm", "CsrMVWorkspace", "CsrMVPlan", "csr_transpose", "CsrTranspose", "coo_to_csr", "CooToCsr", "csr_sum_duplicates", "coomv",
