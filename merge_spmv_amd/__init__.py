@@ -16,7 +16,9 @@ This file only gathers the names; the code lives, one operation family per modul
   _args       pointers, streams, argument checks, the two-phase temp call, the handle base class
   csrmv       DeviceSpmv, csrmv, csrmv_mixed, csrmm, CsrMVWorkspace
   convert     transpose, COO, duplicate summing, coomv, add, gemm, permute, sddmm
-  solve       CsrSv (csrsv, csrsm), ILU(0), IC(0)
+  fill        CsrFill, csr_fill: level-of-fill patterns, the symbolic phase of ILU(k) / IC(k) (include/mspmv_fill.h, libmspmv_fill.so, a
+              library of its own); attributes of the package, not in __all__
+  solve       CsrSv (csrsv, csrsm), ILU(0), IC(0); Iluk, Ick: the same on a filled pattern (attributes of the package, not in __all__)
   reorder     CsrColoring, csr_color, multicolor_reorder
   krylov      vec_dot, Pcg, pcg
   bicgstab    Bicgstab, bicgstab, BICGSTAB_EXIT: the Krylov layer on top of the C ABI (include/mspmv_krylov.h, libmspmv_krylov.so, which
@@ -37,7 +39,8 @@ from .introspect import (band_passes, cache_stream_rate, clocked_bands, debug_ba
 from .csrmv import CsrMVWorkspace, DeviceSpmv, csrmm, csrmv, csrmv_mixed
 from .convert import (CooToCsr, CsrAdd, CsrGemm, CsrTranspose, coo_to_csr, coomv, csr_add, csr_gemm, csr_gemm_products, csr_permute,
                       csr_sum_duplicates, csr_symmetrize, csr_transpose, sddmm)
-from .solve import (CsrSv, Ic0, Ilu0, _ic0_call, _ic0_temp_bytes, _ilu0_call, _ilu0_temp_bytes, csric0, csric0_group, csrilu0,
+from .fill import CsrFill, csr_fill
+from .solve import (CsrSv, Ic0, Ick, Ilu0, Iluk, _ic0_call, _ic0_temp_bytes, _ilu0_call, _ilu0_temp_bytes, csric0, csric0_group, csrilu0,
                     csrilu0_group, csrsm, csrsv)
 from .reorder import CsrColoring, csr_color, multicolor_reorder
 from .krylov import PCG_STATUS, Pcg, pcg, vec_dot

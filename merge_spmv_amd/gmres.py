@@ -10,7 +10,7 @@ import os
 
 from ._lib import _F, _HERE, MspmvError, _check, _prototype, load_library, use_library
 from ._args import _Handle, _index_check, _pattern_check, _ptr, _stream_handle, _typed
-from .solve import CsrSv, Ilu0, _Factor0
+from .solve import CsrSv, Ilu0, Iluk, _Factor0
 from .reorder import multicolor_reorder
 from .krylov import PCG_STATUS
 
@@ -187,14 +187,19 @@ class Gmres(_Handle):
 
 
 def gmres(values, row_offsets, column_indices, b, preconditioner="ilu0", reorder: bool = True, restart: int = 30, x=None,
-          rtol: float = 1e-8, atol: float = 0.0, max_iterations: int = 1000, check_every: int = 8, stream=None, return_state: bool = False):
+          rtol: float = 1e-8, atol: float = 0.0, max_iterations: int = 1000, check_every: int = 8, stream=None, return_state: bool = False,
+          fill_level: int = 0):
     """One-shot A x = b for a square CSR matrix (sorted rows, no duplicates; "ilu0" and "jacobi" need every diagonal entry stored).
     preconditioner: "ilu0" | "jacobi" | None.  With reorder (and "ilu0") the matrix is permuted to multicolour order
     (multicolor_reorder), ILU(0) is made of P A P^T, the system is solved in that numbering and x is mapped back
-    (CsrColoring.permute_vector(back=True)): b, x, and a guess given as x, are in the caller's numbering.  Returns x, or (x, state)
-    with return_state.  A loop over right-hand sides or values keeps a Gmres (and the Ilu0 and CsrColoring) instead."""
+    (CsrColoring.permute_vector(back=True)): b, x, and a guess given as x, are in the caller's numbering.  fill_level > 0 (with
+    "ilu0" only): ILU(fill_level) instead, an Iluk on the filled pattern of the matrix that is factorised (P A P^T with reorder).
+    Returns x, or (x, state) with return_state.  A loop over right-hand sides or values keeps a Gmres (and the Ilu0 and CsrColoring)
+    instead."""
     if preconditioner not in ("ilu0", "jacobi", None):
         raise MspmvError(f"gmres: unknown preconditioner {preconditioner!r}")
+    if int(fill_level) < 0:
+        raise MspmvError(f"gmres: fill_level must not be negative, got {fill_level}")
     coloring = ilu = None
     val, off, col, rhs, x0 = values, row_offsets, column_indices, b, x
     try:
@@ -205,7 +210,7 @@ def gmres(values, row_offsets, column_indices, b, preconditioner="ilu0", reorder
             x0 = None if x is None else coloring.permute_vector(x, stream=stream)
         m = None
         if preconditioner == "ilu0":
-            ilu = Ilu0(off, col, stream=stream)
+            ilu = Iluk(off, col, int(fill_level), stream=stream) if int(fill_level) > 0 else Ilu0(off, col, stream=stream)
             ilu.factor(val, stream=stream)
             m = ilu
         solver = Gmres(off, col, b.dtype, preconditioner="jacobi" if preconditioner == "jacobi" else m, restart=restart, stream=stream)

@@ -5,7 +5,7 @@ import ctypes
 
 from ._lib import MspmvError, _PcgState, _check, load_library
 from ._args import _Handle, _index_check, _pattern_check, _ptr, _stream_handle, _two_phase, _typed
-from .solve import CsrSv, Ic0, _Factor0
+from .solve import CsrSv, Ic0, Ick, _Factor0
 from .reorder import multicolor_reorder
 
 
@@ -144,14 +144,17 @@ class Pcg(_Handle):
 
 
 def pcg(values, row_offsets, column_indices, b, preconditioner="ic0", reorder: bool = True, x=None, rtol: float = 1e-8, atol: float = 0.0,
-        max_iterations: int = 1000, check_every: int = 8, stream=None, return_state: bool = False):
+        max_iterations: int = 1000, check_every: int = 8, stream=None, return_state: bool = False, fill_level: int = 0):
     """One-shot A x = b for a symmetric positive definite CSR matrix (sorted rows, no duplicates, structurally symmetric for "ic0").
     preconditioner: "ic0" | "jacobi" | None.  With reorder (and "ic0") the matrix is permuted to multicolour order
     (multicolor_reorder), IC(0) is made of P A P^T, the system is solved in that numbering and x is mapped back
-    (CsrColoring.permute_vector(back=True)): x, and a guess given as x, are in the caller's numbering.  Returns x, or (x, state) with
-    return_state.  A loop over right-hand sides or values keeps a Pcg (and the Ic0 and CsrColoring) instead."""
+    (CsrColoring.permute_vector(back=True)): x, and a guess given as x, are in the caller's numbering.  fill_level > 0 (with "ic0"
+    only): IC(fill_level) instead, an Ick on the filled pattern of the matrix that is factorised (P A P^T with reorder).  Returns x,
+    or (x, state) with return_state.  A loop over right-hand sides or values keeps a Pcg (and the Ic0 and CsrColoring) instead."""
     if preconditioner not in ("ic0", "jacobi", None):
         raise MspmvError(f"pcg: unknown preconditioner {preconditioner!r}")
+    if int(fill_level) < 0:
+        raise MspmvError(f"pcg: fill_level must not be negative, got {fill_level}")
     coloring = ic = None
     val, off, col, rhs, x0 = values, row_offsets, column_indices, b, x
     try:
@@ -162,7 +165,7 @@ def pcg(values, row_offsets, column_indices, b, preconditioner="ic0", reorder: b
             x0 = None if x is None else coloring.permute_vector(x, stream=stream)
         m = None
         if preconditioner == "ic0":
-            ic = Ic0(off, col, stream=stream)
+            ic = Ick(off, col, int(fill_level), stream=stream) if int(fill_level) > 0 else Ic0(off, col, stream=stream)
             ic.factor(val, stream=stream)
             m = ic
         solver = Pcg(off, col, b.dtype, preconditioner="jacobi" if preconditioner == "jacobi" else m, stream=stream)

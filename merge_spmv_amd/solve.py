@@ -1,11 +1,12 @@
 """The level-scheduled triangular solves (CsrSv: csrsv for one right-hand side, csrsm for k) and the two factorisations that run along
-the same levels, ILU(0) and IC(0)."""
+the same levels, ILU(0) and IC(0), and ILU(k) / IC(k): the same two on a level-of-fill pattern (fill.py)."""
 from __future__ import annotations
 
 import ctypes
 
 from ._lib import MspmvError, _CsrSmInfo, _CsrSvInfo, _check, load_library
 from ._args import _Handle, _many_layout, _pattern_check, _ptr, _stream_handle, _typed
+from .fill import CsrFill
 
 
 class CsrSv(_Handle):
@@ -346,3 +347,49 @@ class Ic0(_Factor0):
     @staticmethod
     def _call(plan, temp, values, l, row_offsets, column_indices, pivot, stream, debug_synchronous):
         _ic0_call(plan, temp, values, l, row_offsets, column_indices, True, pivot, stream, debug_synchronous)
+
+
+class _FactorK:
+    """What Iluk and Ick add to Ilu0 / Ic0: the CsrFill of the given pattern, on whose filled pattern the plans are made, and the kept
+    filled values that `factor` scatters A's values into before it factorises them."""
+
+    fill = None
+
+    def __init__(self, row_offsets, column_indices, level: int, stream=None):
+        self.fill = CsrFill(row_offsets, column_indices, level, stream=stream)
+        self.level, self.source_nnz = self.fill.level, self.fill.nnz
+        self._filled = None
+        try:
+            super().__init__(self.fill.row_offsets, self.fill.column_indices, stream=stream)
+        except Exception:
+            self.close()
+            raise
+
+    def factor(self, values, stream=None, debug_synchronous: bool = False):
+        """Factorises A's `values` (the entries of the pattern GIVEN to the constructor) on the filled pattern: they are scattered into a
+        kept filled array (+0.0 at fill entries, one launch), which is then factorised as Ilu0 / Ic0 factorise theirs."""
+        self._ready()
+        if self._filled is not None and getattr(values, "dtype", None) != self._filled.dtype:
+            self._filled = None
+        self._filled = self.fill.values(values, out=self._filled, stream=stream)
+        return super().factor(self._filled, stream=stream, debug_synchronous=debug_synchronous)
+
+    def close(self):
+        super().close()
+        if self.fill is not None:
+            self.fill.close()
+        self._filled = None
+
+
+class Iluk(_FactorK, Ilu0):
+    """The ILU(k) preconditioner of one pattern: an Ilu0 made on the level-`level` filled pattern (CsrFill; synchronous).
+    `factor(values)` takes the values of the pattern given here; .row_offsets / .column_indices are the FILLED pattern's, .lu_values the
+    factor on it, .fill the CsrFill (levels, source).  solve, solve_many, .lower, .upper and the use as a preconditioner of Pcg,
+    Bicgstab and Gmres are Ilu0's.  level = 0 is Ilu0 bit for bit."""
+
+
+class Ick(_FactorK, Ic0):
+    """The IC(k) preconditioner of one structurally symmetric pattern: an Ic0 made on the level-`level` filled pattern (CsrFill, which
+    is symmetric when the pattern is; synchronous).  `factor(values)` takes the values of the pattern given here; .row_offsets /
+    .column_indices are the FILLED pattern's, .l_values the factor on it, .fill the CsrFill.  Everything else is Ic0's.  level = 0 is
+    Ic0 bit for bit."""
