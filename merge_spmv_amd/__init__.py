@@ -20,6 +20,7 @@ This file only gathers the names; the code lives, one operation family per modul
               library of its own); attributes of the package, not in __all__
   solve       CsrSv (csrsv, csrsm), ILU(0), IC(0); Iluk, Ick: the same on a filled pattern (attributes of the package, not in __all__)
   reorder     CsrColoring, csr_color, multicolor_reorder
+  _solver     what Pcg, Bicgstab and Gmres share: the loader of a layer library, the solver base class, the one-shot body
   krylov      vec_dot, Pcg, pcg
   bicgstab    Bicgstab, bicgstab, BICGSTAB_EXIT: the Krylov layer on top of the C ABI (include/mspmv_krylov.h, libmspmv_krylov.so, which
               always runs on the product libmspmv.so next to it); attributes of the package, not in __all__

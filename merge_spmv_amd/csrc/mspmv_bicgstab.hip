@@ -1,7 +1,8 @@
 // mspmv_bicgstab.hip -- right-preconditioned BiCGStab on the device (mspmv_bicgstab_* of include/mspmv_krylov.h, which states the
 // arithmetic).  This file is libmspmv_krylov.so: a layer ON TOP of the C ABI.  The products and the sweeps are calls of what
 // libmspmv.so exports (mspmv_csrmv_prepare, mspmv_csrmv_prepared_*, mspmv_csrsv_solve_*, mspmv_csrsv_plan_info); from the source tree
-// it takes only header-only pieces: the deterministic vector layer (mspmv_vec.hpp) and lv_launched (mspmv_levels.hpp).
+// it takes only header-only pieces: the deterministic vector layer (mspmv_vec.hpp), lv_launched (mspmv_levels.hpp) and what the three
+// Krylov solvers know about A and M^-1 (mspmv_krylov_op.hpp: those calls, the refusals, the operator's part of the carve).
 //
 // What one iteration launches, on one stream, ordered by the kernel boundary alone:
 //     FACTOR: two mspmv_csrsv_solve_*     ph = second^-1 first^-1 p      (NONE: ph is p;  JACOBI: ph = p / d was made with p)
@@ -25,11 +26,8 @@
 // one-workgroup step.
 #include <hip/hip_runtime.h>
 
-#include <new>
-
 #include "../../include/mspmv_krylov.h"
-#include "mspmv_levels.hpp"     // lv_launched
-#include "mspmv_vec.hpp"
+#include "mspmv_krylov_op.hpp"
 
 #pragma clang fp contract(off)
 
@@ -40,16 +38,9 @@ struct BicgDev {                                                    // the state
 };
 
 struct mspmv_bicgstab {
-    int32_t rows = 0, nnz = 0, value_bytes = 0, kind = 0, bad_diagonal_row = -1;
-    long long m = 0;                                                // level-1 partials of a dot
-    char *base = nullptr;                                           // the one allocation the arrays below are carved from
-    void *p = nullptr, *v = nullptr, *r = nullptr, *rh = nullptr, *t = nullptr, *hat = nullptr, *mid = nullptr, *diag = nullptr, *part[2] = {},
-         *state = nullptr, *mv_temp = nullptr;
-    int *dpos = nullptr;
-    size_t mv_bytes = 0;
-    mspmv_csrsv_plan_t *first = nullptr, *second = nullptr;         // FACTOR: the two sweeps (not owned)
-    const void *f_vals = nullptr;
-    const int32_t *f_off = nullptr, *f_cols = nullptr;
+    mspmv::KrylovOp op;                                             // A and M^-1
+    char *base = nullptr;                                           // the one allocation the arrays below (and op's) are carved from
+    void *p = nullptr, *v = nullptr, *r = nullptr, *rh = nullptr, *t = nullptr, *hat = nullptr, *part[2] = {}, *state = nullptr;
     mspmv_bicgstab_state_t h_state{};                               // rows == 0: what a solve leaves (no device)
 };
 
@@ -57,22 +48,11 @@ namespace {
 
 using namespace mspmv;
 
+static_assert(MSPMV_BICGSTAB_NONE == KRYLOV_NONE && MSPMV_BICGSTAB_JACOBI == KRYLOV_JACOBI && MSPMV_BICGSTAB_FACTOR == KRYLOV_FACTOR,
+              "the kinds of mspmv_krylov_op.hpp");
+
 enum { BICG_START = 0, BICG_RV = 1, BICG_SS = 2, BICG_TT = 3, BICG_RR = 4 };
 constexpr int BICG_LAUNCHES = 9;
-
-// one lane per row: where the row's diagonal entry is; the smallest row with none or more than one goes to *bad (all ones: none)
-__global__ __launch_bounds__(256) void bicgstab_diag_kernel(const int *__restrict__ off, const int *__restrict__ cols, int rows, int *__restrict__ dpos,
-                                                            unsigned *__restrict__ bad)
-{
-    const long long t = (long long) blockIdx.x * 256 + threadIdx.x;
-    if (t >= rows) return;
-    const int r = (int) t;
-    int at = 0, count = 0;
-    for (int e = off[r]; e < off[r + 1]; ++e)
-        if (cols[e] == r) { at = e; ++count; }
-    dpos[r] = at;
-    if (count != 1) atomicMin(bad, (unsigned) r);
-}
 
 // the start of a solve: r = b - q (q = A x for a guess; NULL: x = +0, r = b), rh = r, p = r, the chunk sums of b.b and r.r;
 // JACOBI: d, ph = p / d
@@ -333,32 +313,15 @@ struct BicgRun {
 
     T *arr(void *a) const { return static_cast<T *>(a); }
     BicgDev<T> *st() const { return static_cast<BicgDev<T> *>(h->state); }
-    T *ph() const { return arr(h->kind == MSPMV_BICGSTAB_NONE ? h->p : h->hat); }
-    T *sh() const { return arr(h->kind == MSPMV_BICGSTAB_NONE ? h->r : h->hat); }
+    T *ph() const { return arr(h->op.kind == MSPMV_BICGSTAB_NONE ? h->p : h->hat); }
+    T *sh() const { return arr(h->op.kind == MSPMV_BICGSTAB_NONE ? h->r : h->hat); }
 
-    int product(const T *in, T *out) const
-    {
-        size_t bytes = h->mv_bytes;
-        const mspmv_stream_t s = reinterpret_cast<mspmv_stream_t>(stream);
-        if constexpr (sizeof(T) == 4) return mspmv_csrmv_prepared_f32(h->mv_temp, &bytes, vals, off, cols, in, out, h->rows, h->rows, h->nnz, 1.0f, 0.0f, s, dbg);
-        else return mspmv_csrmv_prepared_f64(h->mv_temp, &bytes, vals, off, cols, in, out, h->rows, h->rows, h->nnz, 1.0, 0.0, s, dbg);
-    }
-    int sweeps(const T *in) const                                    // hat = second^-1 (first^-1 in)
-    {
-        const mspmv_stream_t s = reinterpret_cast<mspmv_stream_t>(stream);
-        const T *fv = static_cast<const T *>(h->f_vals);
-        if constexpr (sizeof(T) == 4) {
-            if (int e = mspmv_csrsv_solve_f32(h->first, fv, h->f_off, h->f_cols, 1.0f, in, arr(h->mid), s, dbg)) return e;
-            return mspmv_csrsv_solve_f32(h->second, fv, h->f_off, h->f_cols, 1.0f, arr(h->mid), arr(h->hat), s, dbg);
-        } else {
-            if (int e = mspmv_csrsv_solve_f64(h->first, fv, h->f_off, h->f_cols, 1.0, in, arr(h->mid), s, dbg)) return e;
-            return mspmv_csrsv_solve_f64(h->second, fv, h->f_off, h->f_cols, 1.0, arr(h->mid), arr(h->hat), s, dbg);
-        }
-    }
+    int product(const T *in, T *out) const { return krylov_product(h->op, vals, off, cols, in, out, stream, dbg); }
+    int sweeps(const T *in) const { return krylov_sweeps<T>(h->op, in, arr(h->hat), stream, dbg); }  // hat = second^-1 (first^-1 in)
     int step(int mode) const
     {
         hipLaunchKernelGGL(bicgstab_step_kernel<T>, dim3(1), dim3(VEC_FOLD_BLOCK), 0, stream, st(), (const T *) arr(h->part[0]), (const T *) arr(h->part[1]),
-                           h->m, mode, rtol2, atol2, history);
+                           h->op.m, mode, rtol2, atol2, history);
         return lv_launched(stream, dbg, "bicgstab_step_kernel", 1, VEC_FOLD_BLOCK);
     }
     int dot(const T *a, const T *b) const
@@ -376,14 +339,14 @@ struct BicgRun {
     int init(const T *b, const T *q) const
     {
         hipLaunchKernelGGL((bicgstab_init_kernel<T, KIND>), dim3(grid), dim3(VEC_BLOCK), 0, stream, b, q, x, arr(h->r), arr(h->rh), arr(h->p), arr(h->hat),
-                           arr(h->diag), vals, (const int *) h->dpos, n, arr(h->part[0]), arr(h->part[1]));
+                           arr(h->op.diag), vals, (const int *) h->op.dpos, n, arr(h->part[0]), arr(h->part[1]));
         return lv_launched(stream, dbg, "bicgstab_init_kernel", grid, VEC_BLOCK);
     }
     template <int KIND>
     int s_update() const
     {
         hipLaunchKernelGGL((bicgstab_s_kernel<T, KIND>), dim3(grid), dim3(VEC_BLOCK), 0, stream, (const BicgDev<T> *) st(), (const T *) ph(),
-                           (const T *) arr(h->v), x, arr(h->r), arr(h->hat), (const T *) arr(h->diag), n, arr(h->part[0]));
+                           (const T *) arr(h->v), x, arr(h->r), arr(h->hat), (const T *) arr(h->op.diag), n, arr(h->part[0]));
         return lv_launched(stream, dbg, "bicgstab_s_kernel", grid, VEC_BLOCK);
     }
     int update() const
@@ -396,7 +359,7 @@ struct BicgRun {
     int new_p() const
     {
         hipLaunchKernelGGL((bicgstab_p_kernel<T, KIND>), dim3(grid), dim3(VEC_BLOCK), 0, stream, (const BicgDev<T> *) st(), (const T *) arr(h->r),
-                           (const T *) arr(h->v), arr(h->p), arr(h->hat), (const T *) arr(h->diag), n);
+                           (const T *) arr(h->v), arr(h->p), arr(h->hat), (const T *) arr(h->op.diag), n);
         return lv_launched(stream, dbg, "bicgstab_p_kernel", grid, VEC_BLOCK);
     }
 
@@ -407,12 +370,12 @@ struct BicgRun {
             if (int e = product(x, arr(h->v))) return e;
             q = arr(h->v);
         }
-        if (int e = h->kind == MSPMV_BICGSTAB_JACOBI ? init<MSPMV_BICGSTAB_JACOBI>(b, q) : init<MSPMV_BICGSTAB_NONE>(b, q)) return e;
+        if (int e = h->op.kind == MSPMV_BICGSTAB_JACOBI ? init<MSPMV_BICGSTAB_JACOBI>(b, q) : init<MSPMV_BICGSTAB_NONE>(b, q)) return e;
         return step(BICG_START);
     }
     int iteration() const
     {
-        const bool jacobi = h->kind == MSPMV_BICGSTAB_JACOBI, factor = h->kind == MSPMV_BICGSTAB_FACTOR;
+        const bool jacobi = h->op.kind == MSPMV_BICGSTAB_JACOBI, factor = h->op.kind == MSPMV_BICGSTAB_FACTOR;
         if (factor)
             if (int e = sweeps(arr(h->p))) return e;
         if (int e = product(ph(), arr(h->v))) return e;
@@ -435,9 +398,7 @@ template <typename T>
 int bicg_read(const mspmv_bicgstab *h, mspmv_bicgstab_state_t *out, hipStream_t stream)
 {
     BicgDev<T> d;
-    hipError_t e = hipMemcpyAsync(&d, h->state, sizeof(d), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return (int) e;
+    if (int e = krylov_read(h->state, d, stream)) return e;
     out->status = d.status; out->iterations = d.iterations; out->exit_test = d.exit_test;
     out->rr = (double) d.rr; out->bb = (double) d.bb; out->stop2 = (double) d.stop2;
     out->rho = (double) d.rho; out->alpha = (double) d.alpha; out->omega = (double) d.omega;
@@ -448,66 +409,35 @@ template <typename T>
 int bicg_solve(mspmv_bicgstab *h, const T *vals, const int32_t *off, const int32_t *cols, const T *b, T *x, int guess, double rtol, double atol,
                int32_t max_iterations, int32_t check_every, T *history, hipStream_t stream, int dbg)
 {
-    if (!h || h->value_bytes != (int32_t) sizeof(T)) return hipErrorInvalidValue;
-    if (!(rtol >= 0) || !(atol >= 0) || max_iterations < 0 || check_every < 0) return hipErrorInvalidValue;       // (a NaN fails both)
-    if (h->kind == MSPMV_BICGSTAB_FACTOR && !h->first) return hipErrorInvalidValue;
-    if (h->kind == MSPMV_BICGSTAB_JACOBI && h->bad_diagonal_row >= 0) return hipErrorInvalidValue;
-    if (h->rows > 0 && (!b || !x || !off || (h->nnz > 0 && (!vals || !cols)))) return hipErrorInvalidValue;
-    const T rt = (T) rtol, at = (T) atol;
-    const T rtol2 = rt * rt, atol2 = at * at;
-    if (h->rows == 0) {
+    T rtol2, atol2;
+    if (int e = krylov_refuse_solve(h ? &h->op : nullptr, vals, off, cols, b, x, rtol, atol, max_iterations, check_every, rtol2, atol2)) return e;
+    if (h->op.rows == 0) {
         h->h_state.status = MSPMV_PCG_CONVERGED; h->h_state.iterations = 0; h->h_state.exit_test = MSPMV_BICGSTAB_EXIT_START;
         h->h_state.rr = 0; h->h_state.bb = 0; h->h_state.rho = 0; h->h_state.alpha = 0; h->h_state.omega = 0; h->h_state.stop2 = (double) atol2;
         return hipSuccess;
     }
-    const BicgRun<T> run{h, stream, dbg, vals, off, cols, x, rtol2, atol2, history, (long long) h->rows, (unsigned) h->m};
+    const BicgRun<T> run{h, stream, dbg, vals, off, cols, x, rtol2, atol2, history, (long long) h->op.rows, (unsigned) h->op.m};
     if (int e = run.start(b, guess)) return e;
-    for (int done = 0; done < max_iterations;) {
-        const int group = check_every > 0 ? std::min(check_every, max_iterations - done) : max_iterations - done;
-        for (int i = 0; i < group; ++i)
-            if (int e = run.iteration()) return e;
-        done += group;
-        if (check_every > 0) {
-            mspmv_bicgstab_state_t now{};
-            if (int e = bicg_read<T>(h, &now, stream)) return e;
-            if (now.status != MSPMV_PCG_RUNNING) break;
-        }
-    }
-    return hipSuccess;
+    return krylov_groups<BicgDev<T>>(run, max_iterations, check_every);
 }
 
 static int bicg_build(mspmv_bicgstab &h, const int32_t *off, const int32_t *cols, hipStream_t stream, int dbg)
 {
-    const uint64_t vb = (uint64_t) h.value_bytes, vec = align256((uint64_t) h.rows * vb), part = align256((uint64_t) h.m * vb);
-    size_t mv = 0;
-    if (int e = mspmv_csrmv_prepare(nullptr, &mv, nullptr, h.rows, h.nnz, h.value_bytes, nullptr, 0)) return e;
-    h.mv_bytes = mv;
-    const bool jacobi = h.kind == MSPMV_BICGSTAB_JACOBI, factor = h.kind == MSPMV_BICGSTAB_FACTOR;
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) { const uint64_t at = o; o += bytes; return at; };
-    const uint64_t state_o = take(256), p_o = take(vec), v_o = take(vec), r_o = take(vec), rh_o = take(vec), t_o = take(vec),
-                   hat_o = take(jacobi || factor ? vec : 0), mid_o = take(factor ? vec : 0), diag_o = take(jacobi ? vec : 0),
-                   dpos_o = take(jacobi ? align256((uint64_t) h.rows * 4) : 0), p0_o = take(part), p1_o = take(part), mv_o = take(align256(mv));
-    if (hipMalloc(reinterpret_cast<void **>(&h.base), o) != hipSuccess) return hipErrorOutOfMemory;
-    h.h_state.device_bytes = o;
+    if (int e = krylov_query(h.op)) return e;
+    const uint64_t vb = (uint64_t) h.op.value_bytes, vec = align256((uint64_t) h.op.rows * vb), part = align256((uint64_t) h.op.m * vb);
+    const bool own_hat = h.op.kind != MSPMV_BICGSTAB_NONE;          // NONE: ph is p and sh is s, which lives in r
+    KrylovCarve c;
+    const uint64_t state_o = c.take(256), p_o = c.take(vec), v_o = c.take(vec), r_o = c.take(vec), rh_o = c.take(vec), t_o = c.take(vec),
+                   hat_o = c.take(own_hat ? vec : 0);
+    c.precond(h.op, vec);
+    const uint64_t p0_o = c.take(part), p1_o = c.take(part);
+    c.product(h.op);
+    if (int e = krylov_build(h.op, h.base, c, off, cols, stream, dbg)) return e;
+    h.h_state.device_bytes = c.size;
     h.state = h.base + state_o; h.p = h.base + p_o; h.v = h.base + v_o; h.r = h.base + r_o; h.rh = h.base + rh_o; h.t = h.base + t_o;
-    h.hat = jacobi || factor ? h.base + hat_o : nullptr;            // NONE: ph is p and sh is s, which lives in r
-    h.mid = factor ? h.base + mid_o : nullptr;
-    h.diag = jacobi ? h.base + diag_o : nullptr;
-    h.dpos = jacobi ? reinterpret_cast<int *>(h.base + dpos_o) : nullptr;
-    h.part[0] = h.base + p0_o; h.part[1] = h.base + p1_o; h.mv_temp = h.base + mv_o;
-    if (hipMemsetAsync(h.state, 0, 256, stream) != hipSuccess) return hipErrorInvalidValue;
-    size_t bytes = mv;
-    if (int e = mspmv_csrmv_prepare(h.mv_temp, &bytes, off, h.rows, h.nnz, h.value_bytes, reinterpret_cast<mspmv_stream_t>(stream), dbg)) return e;
-    if (jacobi) {
-        unsigned *bad = reinterpret_cast<unsigned *>(h.base + state_o + 128);
-        if (hipMemsetAsync(bad, 0xff, 4, stream) != hipSuccess) return hipErrorInvalidValue;
-        const unsigned grid = grid_for(h.rows, 256);
-        hipLaunchKernelGGL(bicgstab_diag_kernel, dim3(grid), dim3(256), 0, stream, off, cols, (int) h.rows, h.dpos, bad);
-        if (int e = lv_launched(stream, dbg, "bicgstab_diag_kernel", grid, 256)) return e;
-        if (hipMemcpyAsync(&h.bad_diagonal_row, bad, 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return hipErrorInvalidValue;
-    }
-    return (int) hipStreamSynchronize(stream);
+    h.hat = own_hat ? h.base + hat_o : nullptr;
+    h.part[0] = h.base + p0_o; h.part[1] = h.base + p1_o;
+    return hipSuccess;
 }
 
 }  // namespace
@@ -519,42 +449,17 @@ int mspmv_bicgstab_create(mspmv_bicgstab_t **solver, const int32_t *d_row_offset
 {
     if (!solver) return hipErrorInvalidValue;
     *solver = nullptr;
-    if (rows < 0 || nnz < 0 || (long long) rows + nnz > MAX_ITEMS || rows > VEC_MAX_N) return hipErrorInvalidValue;
-    if ((value_bytes != 4 && value_bytes != 8) || precond_kind < MSPMV_BICGSTAB_NONE || precond_kind > MSPMV_BICGSTAB_FACTOR) return hipErrorInvalidValue;
-    if (nnz > 0 && rows == 0) return hipErrorInvalidValue;
-    if (rows > 0 && (!d_row_offsets || (nnz > 0 && !d_column_indices))) return hipErrorInvalidValue;
-    mspmv_bicgstab *h = new (std::nothrow) mspmv_bicgstab;
-    if (!h) return hipErrorOutOfMemory;
-    h->rows = rows; h->nnz = nnz; h->value_bytes = value_bytes; h->kind = precond_kind;
-    h->m = vec_partials(rows);
-    h->h_state.launches_per_iteration = BICG_LAUNCHES;
-    h->h_state.precond_kind = precond_kind;
-    h->h_state.bad_diagonal_row = -1;
-    if (rows > 0) {
-        if (int e = bicg_build(*h, d_row_offsets, d_column_indices, reinterpret_cast<hipStream_t>(stream), debug_sync)) {
-            (void) hipGetLastError();
-            (void) mspmv_bicgstab_destroy(h);
-            return e;
-        }
-        h->h_state.bad_diagonal_row = h->bad_diagonal_row;
-    }
-    *solver = h;
-    return hipSuccess;
+    if (int e = krylov_refuse_create(d_row_offsets, d_column_indices, rows, nnz, value_bytes, precond_kind)) return e;
+    return krylov_create(solver, rows, nnz, value_bytes, precond_kind, [&](mspmv_bicgstab &h) {
+        h.h_state.launches_per_iteration = BICG_LAUNCHES;
+        return rows > 0 ? bicg_build(h, d_row_offsets, d_column_indices, reinterpret_cast<hipStream_t>(stream), debug_sync) : (int) hipSuccess;
+    });
 }
 
 int mspmv_bicgstab_set_factor(mspmv_bicgstab_t *solver, mspmv_csrsv_plan_t *first_plan, mspmv_csrsv_plan_t *second_plan, const void *d_factor_values,
                               const int32_t *d_row_offsets, const int32_t *d_column_indices)
 {
-    if (!solver || solver->kind != MSPMV_BICGSTAB_FACTOR || !first_plan || !second_plan) return hipErrorInvalidValue;
-    for (const mspmv_csrsv_plan_t *plan : {first_plan, second_plan}) {
-        mspmv_csrsv_info_t info;
-        if (int e = mspmv_csrsv_plan_info(plan, &info)) return e;
-        if (info.rows != solver->rows || info.bad_diagonal_row >= 0) return hipErrorInvalidValue;
-        if (info.nnz > 0 && (!d_factor_values || !d_row_offsets || !d_column_indices)) return hipErrorInvalidValue;
-    }
-    solver->first = first_plan; solver->second = second_plan;
-    solver->f_vals = d_factor_values; solver->f_off = d_row_offsets; solver->f_cols = d_column_indices;
-    return hipSuccess;
+    return krylov_set_factor(solver ? &solver->op : nullptr, first_plan, second_plan, d_factor_values, d_row_offsets, d_column_indices);
 }
 
 int mspmv_bicgstab_solve_f32(mspmv_bicgstab_t *solver, const float *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
@@ -577,17 +482,11 @@ int mspmv_bicgstab_state(mspmv_bicgstab_t *solver, mspmv_bicgstab_state_t *state
 {
     if (!solver || !state) return hipErrorInvalidValue;
     *state = solver->h_state;
-    if (solver->rows == 0) return hipSuccess;
+    if (solver->op.rows == 0) return hipSuccess;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return solver->value_bytes == 4 ? bicg_read<float>(solver, state, s) : bicg_read<double>(solver, state, s);
+    return solver->op.value_bytes == 4 ? bicg_read<float>(solver, state, s) : bicg_read<double>(solver, state, s);
 }
 
-int mspmv_bicgstab_destroy(mspmv_bicgstab_t *solver)
-{
-    if (!solver) return hipErrorInvalidValue;
-    if (solver->base) (void) hipFree(solver->base);
-    delete solver;
-    return hipSuccess;
-}
+int mspmv_bicgstab_destroy(mspmv_bicgstab_t *solver) { return krylov_destroy(solver); }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // mspmv_gmres.hip -- right-preconditioned restarted GMRES(m) on the device (mspmv_gmres_* of include/mspmv_gmres.h, which states the
 // arithmetic).  This file is libmspmv_gmres.so: a layer ON TOP of the C ABI, as mspmv_bicgstab.hip is.  The products and the sweeps
 // are calls of what libmspmv.so exports (mspmv_csrmv_prepare, mspmv_csrmv_prepared_*, mspmv_csrsv_solve_*, mspmv_csrsv_plan_info);
-// from the source tree it takes only header-only pieces: the deterministic vector layer (mspmv_vec.hpp) and lv_launched
-// (mspmv_levels.hpp).
+// from the source tree it takes only header-only pieces: the deterministic vector layer (mspmv_vec.hpp), lv_launched
+// (mspmv_levels.hpp) and what the three Krylov solvers know about A and M^-1 (mspmv_krylov_op.hpp: those calls, the refusals, the
+// operator's part of the carve).  The loop over cycles and slots is this file's own.
 //
 // What inner slot j of a cycle launches, on one stream, ordered by the kernel boundary alone:
 //     FACTOR: two mspmv_csrsv_solve_*     z = second^-1 first^-1 v_j     (NONE: z is v_j;  JACOBI: z = v_j / d was made with v_j)
@@ -26,11 +27,8 @@
 // and the closing kernels but END return when the cycle holds no column.  The dots are the defined reduction of mspmv_vec.hpp.
 #include <hip/hip_runtime.h>
 
-#include <new>
-
 #include "../../include/mspmv_gmres.h"
-#include "mspmv_levels.hpp"     // lv_launched
-#include "mspmv_vec.hpp"
+#include "mspmv_krylov_op.hpp"
 
 #pragma clang fp contract(off)
 
@@ -47,16 +45,11 @@ struct GmresSmall {                                                 // the small
 };
 
 struct mspmv_gmres {
-    int32_t rows = 0, nnz = 0, value_bytes = 0, kind = 0, restart = 0, bad_diagonal_row = -1;
-    long long m = 0, pstride = 0, vstride = 0;                      // level-1 partials of a dot; elements between two rows of partials, two basis vectors
-    char *base = nullptr;                                           // the one allocation the arrays below are carved from
-    void *V = nullptr, *w = nullptr, *hat = nullptr, *mid = nullptr, *diag = nullptr, *part = nullptr, *small = nullptr, *state = nullptr,
-         *mv_temp = nullptr;
-    int *dpos = nullptr;
-    size_t mv_bytes = 0;
-    mspmv_csrsv_plan_t *first = nullptr, *second = nullptr;         // FACTOR: the two sweeps (not owned)
-    const void *f_vals = nullptr;
-    const int32_t *f_off = nullptr, *f_cols = nullptr;
+    mspmv::KrylovOp op;                                             // A and M^-1
+    int32_t restart = 0;
+    long long pstride = 0, vstride = 0;                             // elements between two rows of partials, two basis vectors
+    char *base = nullptr;                                           // the one allocation the arrays below (and op's) are carved from
+    void *V = nullptr, *w = nullptr, *hat = nullptr, *part = nullptr, *small = nullptr, *state = nullptr;
     mspmv_gmres_state_t h_state{};                                  // rows == 0: what a solve leaves (no device)
 };
 
@@ -64,22 +57,10 @@ namespace {
 
 using namespace mspmv;
 
+static_assert(MSPMV_GMRES_NONE == KRYLOV_NONE && MSPMV_GMRES_JACOBI == KRYLOV_JACOBI && MSPMV_GMRES_FACTOR == KRYLOV_FACTOR, "the kinds of mspmv_krylov_op.hpp");
+
 enum { GMRES_START = 0, GMRES_H1 = 1, GMRES_H2 = 2, GMRES_NORM = 3, GMRES_SOLVE = 4, GMRES_END = 5 };
 constexpr int GMRES_LAUNCHES = 7, GMRES_CYCLE_LAUNCHES = 5;
-
-// one lane per row: where the row's diagonal entry is; the smallest row with none or more than one goes to *bad (all ones: none)
-__global__ __launch_bounds__(256) void gmres_diag_kernel(const int *__restrict__ off, const int *__restrict__ cols, int rows, int *__restrict__ dpos,
-                                                         unsigned *__restrict__ bad)
-{
-    const long long t = (long long) blockIdx.x * 256 + threadIdx.x;
-    if (t >= rows) return;
-    const int r = (int) t;
-    int at = 0, count = 0;
-    for (int e = off[r]; e < off[r + 1]; ++e)
-        if (cols[e] == r) { at = e; ++count; }
-    dpos[r] = at;
-    if (count != 1) atomicMin(bad, (unsigned) r);
-}
 
 // The chunk sums of v_c o w for c = 0 .. cols - 1, w's chunk in vw: each is vec_chunk_sum's tree (the quad, six butterfly steps,
 // (w0 + w1) + (w2 + w3)), but the waves' sums of all columns wait in s_w for ONE barrier.  Row c of `part` takes column c's.
@@ -422,32 +403,15 @@ struct GmresRun {
     GmresDev<T> *st() const { return static_cast<GmresDev<T> *>(h->state); }
     const GmresDev<T> *cst() const { return st(); }
     T *v(int j) const { return arr(h->V) + (long long) j * h->vstride; }
-    T *z(int j) const { return h->kind == MSPMV_GMRES_NONE ? v(j) : arr(h->hat); }
+    T *z(int j) const { return h->op.kind == MSPMV_GMRES_NONE ? v(j) : arr(h->hat); }
     T *part(int row) const { return arr(h->part) + (long long) row * h->pstride; }
 
-    int product(const T *in, T *out) const
-    {
-        size_t bytes = h->mv_bytes;
-        const mspmv_stream_t s = reinterpret_cast<mspmv_stream_t>(stream);
-        if constexpr (sizeof(T) == 4) return mspmv_csrmv_prepared_f32(h->mv_temp, &bytes, vals, off, cols, in, out, h->rows, h->rows, h->nnz, 1.0f, 0.0f, s, dbg);
-        else return mspmv_csrmv_prepared_f64(h->mv_temp, &bytes, vals, off, cols, in, out, h->rows, h->rows, h->nnz, 1.0, 0.0, s, dbg);
-    }
-    int sweeps(const T *in) const                                    // hat = second^-1 (first^-1 in)
-    {
-        const mspmv_stream_t s = reinterpret_cast<mspmv_stream_t>(stream);
-        const T *fv = static_cast<const T *>(h->f_vals);
-        if constexpr (sizeof(T) == 4) {
-            if (int e = mspmv_csrsv_solve_f32(h->first, fv, h->f_off, h->f_cols, 1.0f, in, arr(h->mid), s, dbg)) return e;
-            return mspmv_csrsv_solve_f32(h->second, fv, h->f_off, h->f_cols, 1.0f, arr(h->mid), arr(h->hat), s, dbg);
-        } else {
-            if (int e = mspmv_csrsv_solve_f64(h->first, fv, h->f_off, h->f_cols, 1.0, in, arr(h->mid), s, dbg)) return e;
-            return mspmv_csrsv_solve_f64(h->second, fv, h->f_off, h->f_cols, 1.0, arr(h->mid), arr(h->hat), s, dbg);
-        }
-    }
+    int product(const T *in, T *out) const { return krylov_product(h->op, vals, off, cols, in, out, stream, dbg); }
+    int sweeps(const T *in) const { return krylov_sweeps<T>(h->op, in, arr(h->hat), stream, dbg); }  // hat = second^-1 (first^-1 in)
     int step(int mode, int j, int arg) const
     {
         const unsigned blocks = mode == GMRES_H1 || mode == GMRES_H2 ? (unsigned) j + 1 : 1;
-        hipLaunchKernelGGL(gmres_step_kernel<T>, dim3(blocks), dim3(VEC_FOLD_BLOCK), 0, stream, st(), (const T *) arr(h->part), h->pstride, h->m, mode, j, arg,
+        hipLaunchKernelGGL(gmres_step_kernel<T>, dim3(blocks), dim3(VEC_FOLD_BLOCK), 0, stream, st(), (const T *) arr(h->part), h->pstride, h->op.m, mode, j, arg,
                            rtol2, atol2, history, small);
         return lv_launched(stream, dbg, "gmres_step_kernel", blocks, VEC_FOLD_BLOCK);
     }
@@ -466,9 +430,9 @@ struct GmresRun {
     }
     int scale(int j) const                                           // v_j = w / scale
     {
-        if (h->kind == MSPMV_GMRES_JACOBI)
+        if (h->op.kind == MSPMV_GMRES_JACOBI)
             hipLaunchKernelGGL((gmres_scale_kernel<T, MSPMV_GMRES_JACOBI>), dim3(grid), dim3(VEC_BLOCK), 0, stream, cst(), (const T *) arr(h->w), v(j),
-                               arr(h->hat), (const T *) arr(h->diag), n);
+                               arr(h->hat), (const T *) arr(h->op.diag), n);
         else
             hipLaunchKernelGGL((gmres_scale_kernel<T, MSPMV_GMRES_NONE>), dim3(grid), dim3(VEC_BLOCK), 0, stream, cst(), (const T *) arr(h->w), v(j),
                                (T *) nullptr, (const T *) nullptr, n);
@@ -478,13 +442,13 @@ struct GmresRun {
     int combine_as() const
     {
         hipLaunchKernelGGL((gmres_combine_kernel<T, KIND>), dim3(grid), dim3(VEC_BLOCK), 0, stream, cst(), (const T *) arr(h->V), h->vstride,
-                           (const T *) small.y, x, arr(h->w), (const T *) arr(h->diag), n);
+                           (const T *) small.y, x, arr(h->w), (const T *) arr(h->op.diag), n);
         return lv_launched(stream, dbg, "gmres_combine_kernel", grid, VEC_BLOCK);
     }
     int combine() const
     {
-        if (h->kind == MSPMV_GMRES_NONE) return combine_as<MSPMV_GMRES_NONE>();
-        if (h->kind == MSPMV_GMRES_JACOBI) return combine_as<MSPMV_GMRES_JACOBI>();
+        if (h->op.kind == MSPMV_GMRES_NONE) return combine_as<MSPMV_GMRES_NONE>();
+        if (h->op.kind == MSPMV_GMRES_JACOBI) return combine_as<MSPMV_GMRES_JACOBI>();
         if (int e = combine_as<MSPMV_GMRES_FACTOR>()) return e;
         if (int e = sweeps(arr(h->w))) return e;
         hipLaunchKernelGGL(gmres_xadd_kernel<T>, dim3(grid), dim3(VEC_BLOCK), 0, stream, cst(), (const T *) arr(h->hat), x, n);
@@ -492,9 +456,9 @@ struct GmresRun {
     }
     int residual(int first, const T *b, const T *q) const
     {
-        if (h->kind == MSPMV_GMRES_JACOBI)
+        if (h->op.kind == MSPMV_GMRES_JACOBI)
             hipLaunchKernelGGL((gmres_residual_kernel<T, MSPMV_GMRES_JACOBI>), dim3(grid), dim3(VEC_BLOCK), 0, stream, cst(), first, b, q, x, arr(h->w),
-                               arr(h->diag), vals, (const int *) h->dpos, n, part(0), part(h->restart));
+                               arr(h->op.diag), vals, (const int *) h->op.dpos, n, part(0), part(h->restart));
         else
             hipLaunchKernelGGL((gmres_residual_kernel<T, MSPMV_GMRES_NONE>), dim3(grid), dim3(VEC_BLOCK), 0, stream, cst(), first, b, q, x, arr(h->w),
                                (T *) nullptr, vals, (const int *) nullptr, n, part(0), part(h->restart));
@@ -513,7 +477,7 @@ struct GmresRun {
     }
     int inner(int j, int width) const
     {
-        if (h->kind == MSPMV_GMRES_FACTOR)
+        if (h->op.kind == MSPMV_GMRES_FACTOR)
             if (int e = sweeps(v(j))) return e;
         if (int e = product(z(j), arr(h->w))) return e;
         if (int e = dots(j)) return e;
@@ -538,9 +502,7 @@ template <typename T>
 int gmres_read(const mspmv_gmres *h, mspmv_gmres_state_t *out, hipStream_t stream, int *closing = nullptr)
 {
     GmresDev<T> d;
-    hipError_t e = hipMemcpyAsync(&d, h->state, sizeof(d), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return (int) e;
+    if (int e = krylov_read(h->state, d, stream)) return e;
     out->status = d.status; out->iterations = d.iterations; out->slots = d.slots; out->cycles = d.cycles; out->exit_test = d.exit_test;
     out->rr = (double) d.rr; out->bb = (double) d.bb; out->stop2 = (double) d.stop2; out->beta = (double) d.beta;
     if (closing) *closing = d.closing;
@@ -551,14 +513,9 @@ template <typename T>
 int gmres_solve(mspmv_gmres *h, const T *vals, const int32_t *off, const int32_t *cols, const T *b, T *x, int guess, double rtol, double atol,
                 int32_t max_iterations, int32_t check_every, T *history, hipStream_t stream, int dbg)
 {
-    if (!h || h->value_bytes != (int32_t) sizeof(T)) return hipErrorInvalidValue;
-    if (!(rtol >= 0) || !(atol >= 0) || max_iterations < 0 || check_every < 0) return hipErrorInvalidValue;       // (a NaN fails both)
-    if (h->kind == MSPMV_GMRES_FACTOR && !h->first) return hipErrorInvalidValue;
-    if (h->kind == MSPMV_GMRES_JACOBI && h->bad_diagonal_row >= 0) return hipErrorInvalidValue;
-    if (h->rows > 0 && (!b || !x || !off || (h->nnz > 0 && (!vals || !cols)))) return hipErrorInvalidValue;
-    const T rt = (T) rtol, at = (T) atol;
-    const T rtol2 = rt * rt, atol2 = at * at;
-    if (h->rows == 0) {
+    T rtol2, atol2;
+    if (int e = krylov_refuse_solve(h ? &h->op : nullptr, vals, off, cols, b, x, rtol, atol, max_iterations, check_every, rtol2, atol2)) return e;
+    if (h->op.rows == 0) {
         h->h_state.status = MSPMV_PCG_CONVERGED; h->h_state.iterations = 0; h->h_state.slots = 0; h->h_state.cycles = 0;
         h->h_state.exit_test = MSPMV_GMRES_EXIT_START;
         h->h_state.rr = 0; h->h_state.bb = 0; h->h_state.beta = 0; h->h_state.stop2 = (double) atol2;
@@ -571,7 +528,7 @@ int gmres_solve(mspmv_gmres *h, const T *vals, const int32_t *off, const int32_t
     small.g = sm + 6 * R;                                            // (restart + 1 entries)
     small.R = sm + 7 * R + 1;
     small.ldr = R;
-    const GmresRun<T> run{h, stream, dbg, vals, off, cols, x, rtol2, atol2, history, (long long) h->rows, (unsigned) h->m, small};
+    const GmresRun<T> run{h, stream, dbg, vals, off, cols, x, rtol2, atol2, history, (long long) h->op.rows, (unsigned) h->op.m, small};
     if (int e = run.start(b, guess, std::min(R, max_iterations))) return e;
     int since = 0;                                                   // inner slots since the host last looked
     for (int done = 0; done < max_iterations;) {
@@ -605,39 +562,22 @@ int gmres_solve(mspmv_gmres *h, const T *vals, const int32_t *off, const int32_t
 
 static int gmres_build(mspmv_gmres &h, const int32_t *off, const int32_t *cols, hipStream_t stream, int dbg)
 {
-    const uint64_t vb = (uint64_t) h.value_bytes, vec = align256((uint64_t) h.rows * vb), R = (uint64_t) h.restart;
+    if (int e = krylov_query(h.op)) return e;
+    const uint64_t vb = (uint64_t) h.op.value_bytes, vec = align256((uint64_t) h.op.rows * vb), R = (uint64_t) h.restart;
     h.vstride = (long long) (vec / vb);
-    h.pstride = (long long) (((uint64_t) h.m * vb + 15) / 16 * 16 / vb);                                            // rows of partials 16-byte aligned
-    size_t mv = 0;
-    if (int e = mspmv_csrmv_prepare(nullptr, &mv, nullptr, h.rows, h.nnz, h.value_bytes, nullptr, 0)) return e;
-    h.mv_bytes = mv;
-    const bool jacobi = h.kind == MSPMV_GMRES_JACOBI, factor = h.kind == MSPMV_GMRES_FACTOR;
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) { const uint64_t at = o; o += bytes; return at; };
-    const uint64_t state_o = take(256), V_o = take((R + 1) * vec), w_o = take(vec), hat_o = take(jacobi || factor ? vec : 0), mid_o = take(factor ? vec : 0),
-                   diag_o = take(jacobi ? vec : 0), dpos_o = take(jacobi ? align256((uint64_t) h.rows * 4) : 0),
-                   part_o = take(align256((R + 1) * (uint64_t) h.pstride * vb)), small_o = take(align256((R * R + 7 * R + 1) * vb)),
-                   mv_o = take(align256(mv));
-    if (hipMalloc(reinterpret_cast<void **>(&h.base), o) != hipSuccess) return hipErrorOutOfMemory;
-    h.h_state.device_bytes = o;
+    h.pstride = (long long) (((uint64_t) h.op.m * vb + 15) / 16 * 16 / vb);                                         // rows of partials 16-byte aligned
+    const bool own_hat = h.op.kind != MSPMV_GMRES_NONE;             // NONE: z is v_j itself
+    KrylovCarve c;
+    const uint64_t state_o = c.take(256), V_o = c.take((R + 1) * vec), w_o = c.take(vec), hat_o = c.take(own_hat ? vec : 0);
+    c.precond(h.op, vec);
+    const uint64_t part_o = c.take(align256((R + 1) * (uint64_t) h.pstride * vb)), small_o = c.take(align256((R * R + 7 * R + 1) * vb));
+    c.product(h.op);
+    if (int e = krylov_build(h.op, h.base, c, off, cols, stream, dbg)) return e;
+    h.h_state.device_bytes = c.size;
     h.state = h.base + state_o; h.V = h.base + V_o; h.w = h.base + w_o;
-    h.hat = jacobi || factor ? h.base + hat_o : nullptr;            // NONE: z is v_j itself
-    h.mid = factor ? h.base + mid_o : nullptr;
-    h.diag = jacobi ? h.base + diag_o : nullptr;
-    h.dpos = jacobi ? reinterpret_cast<int *>(h.base + dpos_o) : nullptr;
-    h.part = h.base + part_o; h.small = h.base + small_o; h.mv_temp = h.base + mv_o;
-    if (hipMemsetAsync(h.state, 0, 256, stream) != hipSuccess) return hipErrorInvalidValue;
-    size_t bytes = mv;
-    if (int e = mspmv_csrmv_prepare(h.mv_temp, &bytes, off, h.rows, h.nnz, h.value_bytes, reinterpret_cast<mspmv_stream_t>(stream), dbg)) return e;
-    if (jacobi) {
-        unsigned *bad = reinterpret_cast<unsigned *>(h.base + state_o + 128);
-        if (hipMemsetAsync(bad, 0xff, 4, stream) != hipSuccess) return hipErrorInvalidValue;
-        const unsigned grid = grid_for(h.rows, 256);
-        hipLaunchKernelGGL(gmres_diag_kernel, dim3(grid), dim3(256), 0, stream, off, cols, (int) h.rows, h.dpos, bad);
-        if (int e = lv_launched(stream, dbg, "gmres_diag_kernel", grid, 256)) return e;
-        if (hipMemcpyAsync(&h.bad_diagonal_row, bad, 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return hipErrorInvalidValue;
-    }
-    return (int) hipStreamSynchronize(stream);
+    h.hat = own_hat ? h.base + hat_o : nullptr;
+    h.part = h.base + part_o; h.small = h.base + small_o;
+    return hipSuccess;
 }
 
 }  // namespace
@@ -649,45 +589,21 @@ int mspmv_gmres_create(mspmv_gmres_t **solver, const int32_t *d_row_offsets, con
 {
     if (!solver) return hipErrorInvalidValue;
     *solver = nullptr;
-    if (rows < 0 || nnz < 0 || (long long) rows + nnz > MAX_ITEMS || rows > VEC_MAX_N) return hipErrorInvalidValue;
-    if ((value_bytes != 4 && value_bytes != 8) || precond_kind < MSPMV_GMRES_NONE || precond_kind > MSPMV_GMRES_FACTOR) return hipErrorInvalidValue;
+    if (int e = krylov_refuse_create(d_row_offsets, d_column_indices, rows, nnz, value_bytes, precond_kind)) return e;
     if (restart < 1 || restart > MSPMV_GMRES_MAX_RESTART) return hipErrorInvalidValue;
-    if (nnz > 0 && rows == 0) return hipErrorInvalidValue;
-    if (rows > 0 && (!d_row_offsets || (nnz > 0 && !d_column_indices))) return hipErrorInvalidValue;
-    mspmv_gmres *h = new (std::nothrow) mspmv_gmres;
-    if (!h) return hipErrorOutOfMemory;
-    h->rows = rows; h->nnz = nnz; h->value_bytes = value_bytes; h->kind = precond_kind; h->restart = restart;
-    h->m = vec_partials(rows);
-    h->h_state.restart = restart;
-    h->h_state.launches_per_iteration = GMRES_LAUNCHES;
-    h->h_state.launches_per_cycle = GMRES_CYCLE_LAUNCHES + (precond_kind == MSPMV_GMRES_FACTOR ? 1 : 0);
-    h->h_state.precond_kind = precond_kind;
-    h->h_state.bad_diagonal_row = -1;
-    if (rows > 0) {
-        if (int e = gmres_build(*h, d_row_offsets, d_column_indices, reinterpret_cast<hipStream_t>(stream), debug_sync)) {
-            (void) hipGetLastError();
-            (void) mspmv_gmres_destroy(h);
-            return e;
-        }
-        h->h_state.bad_diagonal_row = h->bad_diagonal_row;
-    }
-    *solver = h;
-    return hipSuccess;
+    return krylov_create(solver, rows, nnz, value_bytes, precond_kind, [&](mspmv_gmres &h) {
+        h.restart = restart;
+        h.h_state.restart = restart;
+        h.h_state.launches_per_iteration = GMRES_LAUNCHES;
+        h.h_state.launches_per_cycle = GMRES_CYCLE_LAUNCHES + (precond_kind == MSPMV_GMRES_FACTOR ? 1 : 0);
+        return rows > 0 ? gmres_build(h, d_row_offsets, d_column_indices, reinterpret_cast<hipStream_t>(stream), debug_sync) : (int) hipSuccess;
+    });
 }
 
 int mspmv_gmres_set_factor(mspmv_gmres_t *solver, mspmv_csrsv_plan_t *first_plan, mspmv_csrsv_plan_t *second_plan, const void *d_factor_values,
                            const int32_t *d_row_offsets, const int32_t *d_column_indices)
 {
-    if (!solver || solver->kind != MSPMV_GMRES_FACTOR || !first_plan || !second_plan) return hipErrorInvalidValue;
-    for (const mspmv_csrsv_plan_t *plan : {first_plan, second_plan}) {
-        mspmv_csrsv_info_t info;
-        if (int e = mspmv_csrsv_plan_info(plan, &info)) return e;
-        if (info.rows != solver->rows || info.bad_diagonal_row >= 0) return hipErrorInvalidValue;
-        if (info.nnz > 0 && (!d_factor_values || !d_row_offsets || !d_column_indices)) return hipErrorInvalidValue;
-    }
-    solver->first = first_plan; solver->second = second_plan;
-    solver->f_vals = d_factor_values; solver->f_off = d_row_offsets; solver->f_cols = d_column_indices;
-    return hipSuccess;
+    return krylov_set_factor(solver ? &solver->op : nullptr, first_plan, second_plan, d_factor_values, d_row_offsets, d_column_indices);
 }
 
 int mspmv_gmres_solve_f32(mspmv_gmres_t *solver, const float *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices,
@@ -710,17 +626,11 @@ int mspmv_gmres_state(mspmv_gmres_t *solver, mspmv_gmres_state_t *state, mspmv_s
 {
     if (!solver || !state) return hipErrorInvalidValue;
     *state = solver->h_state;
-    if (solver->rows == 0) return hipSuccess;
+    if (solver->op.rows == 0) return hipSuccess;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return solver->value_bytes == 4 ? gmres_read<float>(solver, state, s) : gmres_read<double>(solver, state, s);
+    return solver->op.value_bytes == 4 ? gmres_read<float>(solver, state, s) : gmres_read<double>(solver, state, s);
 }
 
-int mspmv_gmres_destroy(mspmv_gmres_t *solver)
-{
-    if (!solver) return hipErrorInvalidValue;
-    if (solver->base) (void) hipFree(solver->base);
-    delete solver;
-    return hipSuccess;
-}
+int mspmv_gmres_destroy(mspmv_gmres_t *solver) { return krylov_destroy(solver); }
 
 }  // extern "C"

@@ -13,13 +13,11 @@
 // and with check_every == 0 never.  THE FREEZE: every kernel here but the two that start a solve reads the status first and returns
 // unless it is RUNNING, so iterations enqueued past the end change neither x nor the state nor the history.
 // The dots are the defined reduction of mspmv_vec.hpp: chunk sums where the products are made, the fold in the one-workgroup step.
+// What the solver knows about A and M^-1 (the product, the sweeps, the refusals, the operator's part of the carve) is
+// mspmv_krylov_op.hpp, shared with BiCGStab and GMRES; the recurrence, its kernels and the state block are here.
 #include <hip/hip_runtime.h>
 
-#include <new>
-
-#include "../../include/mspmv.h"
-#include "mspmv_levels.hpp"     // lv_launched, mspmv_csrsv_plan
-#include "mspmv_vec.hpp"
+#include "mspmv_krylov_op.hpp"
 
 #pragma clang fp contract(off)
 
@@ -30,15 +28,9 @@ struct PcgDev {                                                     // the state
 };
 
 struct mspmv_pcg {
-    int32_t rows = 0, nnz = 0, value_bytes = 0, kind = 0, bad_diagonal_row = -1;
-    long long m = 0;                                                // level-1 partials of a dot
-    char *base = nullptr;                                           // the one allocation the arrays below are carved from
-    void *q = nullptr, *z = nullptr, *p = nullptr, *r = nullptr, *mid = nullptr, *diag = nullptr, *part[3] = {}, *state = nullptr, *mv_temp = nullptr;
-    int *dpos = nullptr;
-    size_t mv_bytes = 0;
-    mspmv_csrsv_plan_t *first = nullptr, *second = nullptr;         // FACTOR: the two sweeps (not owned)
-    const void *f_vals = nullptr;
-    const int32_t *f_off = nullptr, *f_cols = nullptr;
+    mspmv::KrylovOp op;                                             // A and M^-1
+    char *base = nullptr;                                           // the one allocation the arrays below (and op's) are carved from
+    void *q = nullptr, *z = nullptr, *p = nullptr, *r = nullptr, *part[3] = {}, *state = nullptr;
     mspmv_pcg_state_t h_state{};                                    // rows == 0: what a solve leaves (no device)
 };
 
@@ -46,23 +38,11 @@ namespace {
 
 using namespace mspmv;
 
+static_assert(MSPMV_PCG_NONE == KRYLOV_NONE && MSPMV_PCG_JACOBI == KRYLOV_JACOBI && MSPMV_PCG_FACTOR == KRYLOV_FACTOR, "the kinds of mspmv_krylov_op.hpp");
+
 enum { PCG_START = 0, PCG_PQ = 1, PCG_RR = 2, PCG_RZ = 3, PCG_RZ_FIRST = 4 };
 
 static int pcg_launches_per_iteration(int kind) { return kind == MSPMV_PCG_FACTOR ? 7 : 5; }
-
-// one lane per row: where the row's diagonal entry is; the smallest row with none or more than one goes to *bad (all ones: none)
-__global__ __launch_bounds__(256) void pcg_diag_kernel(const int *__restrict__ off, const int *__restrict__ cols, int rows, int *__restrict__ dpos,
-                                                       unsigned *__restrict__ bad)
-{
-    const long long t = (long long) blockIdx.x * 256 + threadIdx.x;
-    if (t >= rows) return;
-    const int r = (int) t;
-    int at = 0, count = 0;
-    for (int e = off[r]; e < off[r + 1]; ++e)
-        if (cols[e] == r) { at = e; ++count; }
-    dpos[r] = at;
-    if (count != 1) atomicMin(bad, (unsigned) r);
-}
 
 // the start of a solve: r = b - q (q = A x for a guess; NULL: x = +0, r = b), the chunk sums of b.b and r.r; JACOBI: d, z = r / d, r.z
 template <typename T, int KIND>
@@ -258,29 +238,12 @@ struct PcgRun {
     T *arr(void *a) const { return static_cast<T *>(a); }
     PcgDev<T> *st() const { return static_cast<PcgDev<T> *>(h->state); }
 
-    int product(const T *in, T *out) const
-    {
-        size_t bytes = h->mv_bytes;
-        const mspmv_stream_t s = reinterpret_cast<mspmv_stream_t>(stream);
-        if constexpr (sizeof(T) == 4) return mspmv_csrmv_prepared_f32(h->mv_temp, &bytes, vals, off, cols, in, out, h->rows, h->rows, h->nnz, 1.0f, 0.0f, s, dbg);
-        else return mspmv_csrmv_prepared_f64(h->mv_temp, &bytes, vals, off, cols, in, out, h->rows, h->rows, h->nnz, 1.0, 0.0, s, dbg);
-    }
-    int sweeps() const                                               // z = second^-1 (first^-1 r)
-    {
-        const mspmv_stream_t s = reinterpret_cast<mspmv_stream_t>(stream);
-        const T *fv = static_cast<const T *>(h->f_vals);
-        if constexpr (sizeof(T) == 4) {
-            if (int e = mspmv_csrsv_solve_f32(h->first, fv, h->f_off, h->f_cols, 1.0f, arr(h->r), arr(h->mid), s, dbg)) return e;
-            return mspmv_csrsv_solve_f32(h->second, fv, h->f_off, h->f_cols, 1.0f, arr(h->mid), arr(h->z), s, dbg);
-        } else {
-            if (int e = mspmv_csrsv_solve_f64(h->first, fv, h->f_off, h->f_cols, 1.0, arr(h->r), arr(h->mid), s, dbg)) return e;
-            return mspmv_csrsv_solve_f64(h->second, fv, h->f_off, h->f_cols, 1.0, arr(h->mid), arr(h->z), s, dbg);
-        }
-    }
+    int product(const T *in, T *out) const { return krylov_product(h->op, vals, off, cols, in, out, stream, dbg); }
+    int sweeps() const { return krylov_sweeps<T>(h->op, arr(h->r), arr(h->z), stream, dbg); }        // z = second^-1 (first^-1 r)
     int step(int mode) const
     {
-        hipLaunchKernelGGL(pcg_step_kernel<T>, dim3(1), dim3(VEC_FOLD_BLOCK), 0, stream, st(), arr(h->part[0]), arr(h->part[1]), arr(h->part[2]), h->m,
-                           mode, (int) h->kind, rtol2, atol2, history);
+        hipLaunchKernelGGL(pcg_step_kernel<T>, dim3(1), dim3(VEC_FOLD_BLOCK), 0, stream, st(), arr(h->part[0]), arr(h->part[1]), arr(h->part[2]), h->op.m,
+                           mode, (int) h->op.kind, rtol2, atol2, history);
         return lv_launched(stream, dbg, "pcg_step_kernel", 1, VEC_FOLD_BLOCK);
     }
     int dot(const T *a, const T *b) const
@@ -296,15 +259,15 @@ struct PcgRun {
     template <int KIND>
     int init(const T *b, const T *q) const
     {
-        hipLaunchKernelGGL((pcg_init_kernel<T, KIND>), dim3(grid), dim3(VEC_BLOCK), 0, stream, b, q, x, arr(h->r), arr(h->z), arr(h->diag), vals,
-                           (const int *) h->dpos, n, arr(h->part[0]), arr(h->part[1]), arr(h->part[2]));
+        hipLaunchKernelGGL((pcg_init_kernel<T, KIND>), dim3(grid), dim3(VEC_BLOCK), 0, stream, b, q, x, arr(h->r), arr(h->z), arr(h->op.diag), vals,
+                           (const int *) h->op.dpos, n, arr(h->part[0]), arr(h->part[1]), arr(h->part[2]));
         return lv_launched(stream, dbg, "pcg_init_kernel", grid, VEC_BLOCK);
     }
     template <int KIND>
     int update() const
     {
         hipLaunchKernelGGL((pcg_update_kernel<T, KIND>), dim3(grid), dim3(VEC_BLOCK), 0, stream, (const PcgDev<T> *) st(), (const T *) arr(h->p),
-                           (const T *) arr(h->q), x, arr(h->r), arr(h->z), (const T *) arr(h->diag), n, arr(h->part[0]), arr(h->part[1]));
+                           (const T *) arr(h->q), x, arr(h->r), arr(h->z), (const T *) arr(h->op.diag), n, arr(h->part[0]), arr(h->part[1]));
         return lv_launched(stream, dbg, "pcg_update_kernel", grid, VEC_BLOCK);
     }
 
@@ -315,9 +278,9 @@ struct PcgRun {
             if (int e = product(x, arr(h->q))) return e;
             q = arr(h->q);
         }
-        if (int e = h->kind == MSPMV_PCG_JACOBI ? init<MSPMV_PCG_JACOBI>(b, q) : init<MSPMV_PCG_NONE>(b, q)) return e;
+        if (int e = h->op.kind == MSPMV_PCG_JACOBI ? init<MSPMV_PCG_JACOBI>(b, q) : init<MSPMV_PCG_NONE>(b, q)) return e;
         if (int e = step(PCG_START)) return e;
-        if (h->kind == MSPMV_PCG_FACTOR) {
+        if (h->op.kind == MSPMV_PCG_FACTOR) {
             if (int e = sweeps()) return e;
             if (int e = dot(arr(h->r), arr(h->z))) return e;
             if (int e = step(PCG_RZ_FIRST)) return e;
@@ -329,9 +292,9 @@ struct PcgRun {
         if (int e = product(arr(h->p), arr(h->q))) return e;
         if (int e = dot(arr(h->p), arr(h->q))) return e;
         if (int e = step(PCG_PQ)) return e;
-        if (int e = h->kind == MSPMV_PCG_JACOBI ? update<MSPMV_PCG_JACOBI>() : update<MSPMV_PCG_NONE>()) return e;
+        if (int e = h->op.kind == MSPMV_PCG_JACOBI ? update<MSPMV_PCG_JACOBI>() : update<MSPMV_PCG_NONE>()) return e;
         if (int e = step(PCG_RR)) return e;
-        if (h->kind == MSPMV_PCG_FACTOR) {
+        if (h->op.kind == MSPMV_PCG_FACTOR) {
             if (int e = sweeps()) return e;
             if (int e = dot(arr(h->r), arr(h->z))) return e;
             if (int e = step(PCG_RZ)) return e;
@@ -344,9 +307,7 @@ template <typename T>
 int pcg_read(const mspmv_pcg *h, mspmv_pcg_state_t *out, hipStream_t stream)
 {
     PcgDev<T> d;
-    hipError_t e = hipMemcpyAsync(&d, h->state, sizeof(d), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return (int) e;
+    if (int e = krylov_read(h->state, d, stream)) return e;
     out->status = d.status; out->iterations = d.iterations;
     out->rr = (double) d.rr; out->bb = (double) d.bb; out->stop2 = (double) d.stop2; out->rz = (double) d.rz;
     return hipSuccess;
@@ -356,66 +317,34 @@ template <typename T>
 int pcg_solve(mspmv_pcg *h, const T *vals, const int32_t *off, const int32_t *cols, const T *b, T *x, int guess, double rtol, double atol,
               int32_t max_iterations, int32_t check_every, T *history, hipStream_t stream, int dbg)
 {
-    if (!h || h->value_bytes != (int32_t) sizeof(T)) return hipErrorInvalidValue;
-    if (!(rtol >= 0) || !(atol >= 0) || max_iterations < 0 || check_every < 0) return hipErrorInvalidValue;       // (a NaN fails both)
-    if (h->kind == MSPMV_PCG_FACTOR && !h->first) return hipErrorInvalidValue;
-    if (h->kind == MSPMV_PCG_JACOBI && h->bad_diagonal_row >= 0) return hipErrorInvalidValue;
-    if (h->rows > 0 && (!b || !x || !off || (h->nnz > 0 && (!vals || !cols)))) return hipErrorInvalidValue;
-    const T rt = (T) rtol, at = (T) atol;
-    const T rtol2 = rt * rt, atol2 = at * at;
-    if (h->rows == 0) {
+    T rtol2, atol2;
+    if (int e = krylov_refuse_solve(h ? &h->op : nullptr, vals, off, cols, b, x, rtol, atol, max_iterations, check_every, rtol2, atol2)) return e;
+    if (h->op.rows == 0) {
         h->h_state.status = MSPMV_PCG_CONVERGED; h->h_state.iterations = 0;
         h->h_state.rr = 0; h->h_state.bb = 0; h->h_state.rz = 0; h->h_state.stop2 = (double) atol2;
         return hipSuccess;
     }
-    const PcgRun<T> run{h, stream, dbg, vals, off, cols, x, rtol2, atol2, history, (long long) h->rows, (unsigned) h->m};
+    const PcgRun<T> run{h, stream, dbg, vals, off, cols, x, rtol2, atol2, history, (long long) h->op.rows, (unsigned) h->op.m};
     if (int e = run.start(b, guess)) return e;
-    for (int done = 0; done < max_iterations;) {
-        const int group = check_every > 0 ? std::min(check_every, max_iterations - done) : max_iterations - done;
-        for (int i = 0; i < group; ++i)
-            if (int e = run.iteration()) return e;
-        done += group;
-        if (check_every > 0) {
-            mspmv_pcg_state_t now{};
-            if (int e = pcg_read<T>(h, &now, stream)) return e;
-            if (now.status != MSPMV_PCG_RUNNING) break;
-        }
-    }
-    return hipSuccess;
+    return krylov_groups<PcgDev<T>>(run, max_iterations, check_every);
 }
 
 static int pcg_build(mspmv_pcg &h, const int32_t *off, const int32_t *cols, hipStream_t stream, int dbg)
 {
-    const uint64_t vb = (uint64_t) h.value_bytes, vec = align256((uint64_t) h.rows * vb), part = align256((uint64_t) h.m * vb);
-    size_t mv = 0;
-    if (int e = mspmv_csrmv_prepare(nullptr, &mv, nullptr, h.rows, h.nnz, h.value_bytes, nullptr, 0)) return e;
-    h.mv_bytes = mv;
-    const bool jacobi = h.kind == MSPMV_PCG_JACOBI, factor = h.kind == MSPMV_PCG_FACTOR;
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) { const uint64_t at = o; o += bytes; return at; };
-    const uint64_t state_o = take(256), q_o = take(vec), p_o = take(vec), r_o = take(vec), z_o = take(jacobi || factor ? vec : 0),
-                   mid_o = take(factor ? vec : 0), diag_o = take(jacobi ? vec : 0), dpos_o = take(jacobi ? align256((uint64_t) h.rows * 4) : 0),
-                   p0_o = take(part), p1_o = take(part), p2_o = take(part), mv_o = take(align256(mv));
-    if (hipMalloc(reinterpret_cast<void **>(&h.base), o) != hipSuccess) return hipErrorOutOfMemory;
-    h.h_state.device_bytes = o;
+    if (int e = krylov_query(h.op)) return e;
+    const uint64_t vb = (uint64_t) h.op.value_bytes, vec = align256((uint64_t) h.op.rows * vb), part = align256((uint64_t) h.op.m * vb);
+    const bool own_z = h.op.kind != MSPMV_PCG_NONE;                 // NONE: z is r
+    KrylovCarve c;
+    const uint64_t state_o = c.take(256), q_o = c.take(vec), p_o = c.take(vec), r_o = c.take(vec), z_o = c.take(own_z ? vec : 0);
+    c.precond(h.op, vec);
+    const uint64_t p0_o = c.take(part), p1_o = c.take(part), p2_o = c.take(part);
+    c.product(h.op);
+    if (int e = krylov_build(h.op, h.base, c, off, cols, stream, dbg)) return e;
+    h.h_state.device_bytes = c.size;
     h.state = h.base + state_o; h.q = h.base + q_o; h.p = h.base + p_o; h.r = h.base + r_o;
-    h.z = jacobi || factor ? h.base + z_o : h.r;                    // NONE: z is r
-    h.mid = factor ? h.base + mid_o : nullptr;
-    h.diag = jacobi ? h.base + diag_o : nullptr;
-    h.dpos = jacobi ? reinterpret_cast<int *>(h.base + dpos_o) : nullptr;
-    h.part[0] = h.base + p0_o; h.part[1] = h.base + p1_o; h.part[2] = h.base + p2_o; h.mv_temp = h.base + mv_o;
-    if (hipMemsetAsync(h.state, 0, 256, stream) != hipSuccess) return hipErrorInvalidValue;
-    size_t bytes = mv;
-    if (int e = mspmv_csrmv_prepare(h.mv_temp, &bytes, off, h.rows, h.nnz, h.value_bytes, reinterpret_cast<mspmv_stream_t>(stream), dbg)) return e;
-    if (jacobi) {
-        unsigned *bad = reinterpret_cast<unsigned *>(h.base + state_o + 128);
-        if (hipMemsetAsync(bad, 0xff, 4, stream) != hipSuccess) return hipErrorInvalidValue;
-        const unsigned grid = grid_for(h.rows, 256);
-        hipLaunchKernelGGL(pcg_diag_kernel, dim3(grid), dim3(256), 0, stream, off, cols, (int) h.rows, h.dpos, bad);
-        if (int e = lv_launched(stream, dbg, "pcg_diag_kernel", grid, 256)) return e;
-        if (hipMemcpyAsync(&h.bad_diagonal_row, bad, 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return hipErrorInvalidValue;
-    }
-    return (int) hipStreamSynchronize(stream);
+    h.z = own_z ? h.base + z_o : h.r;
+    h.part[0] = h.base + p0_o; h.part[1] = h.base + p1_o; h.part[2] = h.base + p2_o;
+    return hipSuccess;
 }
 
 }  // namespace
@@ -427,40 +356,17 @@ int mspmv_pcg_create(mspmv_pcg_t **pcg, const int32_t *d_row_offsets, const int3
 {
     if (!pcg) return hipErrorInvalidValue;
     *pcg = nullptr;
-    if (rows < 0 || nnz < 0 || (long long) rows + nnz > MAX_ITEMS || rows > VEC_MAX_N) return hipErrorInvalidValue;
-    if ((value_bytes != 4 && value_bytes != 8) || precond_kind < MSPMV_PCG_NONE || precond_kind > MSPMV_PCG_FACTOR) return hipErrorInvalidValue;
-    if (nnz > 0 && rows == 0) return hipErrorInvalidValue;
-    if (rows > 0 && (!d_row_offsets || (nnz > 0 && !d_column_indices))) return hipErrorInvalidValue;
-    mspmv_pcg *h = new (std::nothrow) mspmv_pcg;
-    if (!h) return hipErrorOutOfMemory;
-    h->rows = rows; h->nnz = nnz; h->value_bytes = value_bytes; h->kind = precond_kind;
-    h->m = vec_partials(rows);
-    h->h_state.launches_per_iteration = pcg_launches_per_iteration(precond_kind);
-    h->h_state.precond_kind = precond_kind;
-    h->h_state.bad_diagonal_row = -1;
-    if (rows > 0) {
-        if (int e = pcg_build(*h, d_row_offsets, d_column_indices, reinterpret_cast<hipStream_t>(stream), debug_sync)) {
-            (void) hipGetLastError();
-            (void) mspmv_pcg_destroy(h);
-            return e;
-        }
-        h->h_state.bad_diagonal_row = h->bad_diagonal_row;
-    }
-    *pcg = h;
-    return hipSuccess;
+    if (int e = krylov_refuse_create(d_row_offsets, d_column_indices, rows, nnz, value_bytes, precond_kind)) return e;
+    return krylov_create(pcg, rows, nnz, value_bytes, precond_kind, [&](mspmv_pcg &h) {
+        h.h_state.launches_per_iteration = pcg_launches_per_iteration(precond_kind);
+        return rows > 0 ? pcg_build(h, d_row_offsets, d_column_indices, reinterpret_cast<hipStream_t>(stream), debug_sync) : (int) hipSuccess;
+    });
 }
 
 int mspmv_pcg_set_factor(mspmv_pcg_t *pcg, mspmv_csrsv_plan_t *first_plan, mspmv_csrsv_plan_t *second_plan, const void *d_factor_values,
                          const int32_t *d_row_offsets, const int32_t *d_column_indices)
 {
-    if (!pcg || pcg->kind != MSPMV_PCG_FACTOR || !first_plan || !second_plan) return hipErrorInvalidValue;
-    for (const mspmv_csrsv_plan_t *plan : {first_plan, second_plan}) {
-        if (plan->info.rows != pcg->rows || plan->info.bad_diagonal_row >= 0) return hipErrorInvalidValue;
-        if (plan->info.nnz > 0 && (!d_factor_values || !d_row_offsets || !d_column_indices)) return hipErrorInvalidValue;
-    }
-    pcg->first = first_plan; pcg->second = second_plan;
-    pcg->f_vals = d_factor_values; pcg->f_off = d_row_offsets; pcg->f_cols = d_column_indices;
-    return hipSuccess;
+    return krylov_set_factor(pcg ? &pcg->op : nullptr, first_plan, second_plan, d_factor_values, d_row_offsets, d_column_indices);
 }
 
 int mspmv_pcg_solve_f32(mspmv_pcg_t *pcg, const float *d_values, const int32_t *d_row_offsets, const int32_t *d_column_indices, const float *d_b,
@@ -483,17 +389,11 @@ int mspmv_pcg_state(mspmv_pcg_t *pcg, mspmv_pcg_state_t *state, mspmv_stream_t s
 {
     if (!pcg || !state) return hipErrorInvalidValue;
     *state = pcg->h_state;
-    if (pcg->rows == 0) return hipSuccess;
+    if (pcg->op.rows == 0) return hipSuccess;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return pcg->value_bytes == 4 ? pcg_read<float>(pcg, state, s) : pcg_read<double>(pcg, state, s);
+    return pcg->op.value_bytes == 4 ? pcg_read<float>(pcg, state, s) : pcg_read<double>(pcg, state, s);
 }
 
-int mspmv_pcg_destroy(mspmv_pcg_t *pcg)
-{
-    if (!pcg) return hipErrorInvalidValue;
-    if (pcg->base) (void) hipFree(pcg->base);
-    delete pcg;
-    return hipSuccess;
-}
+int mspmv_pcg_destroy(mspmv_pcg_t *pcg) { return krylov_destroy(pcg); }
 
 }  // extern "C"
